@@ -25,6 +25,10 @@ was carried by anything else).
       scaling: per-GPU work fixed); value = mesh^3 x (sources x N) x K / max-over-ranks time.
   --workload config4 (BASELINE configs[3]): 1024 seeded sources over a log-normal 256^3 box, neutral start,
       dealt to the ranks as do_grid_static does (1+rank, NumSrc, N): strong scaling, the north star's 2/4/8 case.
+
+A plain run sets up, warms up, times the steps and prints the result line.  --full adds what takes time of its own
+beyond that: the CPU baselines (the oracle and the reference timed on the host cores; minutes at 256^3).
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (dump_outputs).
 """
 from __future__ import annotations
 
@@ -234,6 +238,26 @@ def cpu_baseline_reference_at_size(mesh=256, iterations=2):
                       "(sub-boxes still small: an upper bound of its rate; at the mesh limit see cpu_baseline_reference_at_size)"}
 
 
+def dump_outputs(e, conv, out_dir, sample=1 << 18, seed=2026):
+    """What the timed path computed in its last step, as a caller of it receives it: the rate grids, photon loss and
+    sub-box count of the pass (download_rates), the iteration state of the chemistry (download_iter_state) and the
+    convergence flag of the global pass, as DIR/<name>.npy in float64.  A grid is written as (components, cells); on a mesh
+    of more than `sample` cells only the same seeded `sample` cells of every component are kept (14 components x 2 MB)."""
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    n = e.ncell
+    idx = np.sort(np.random.default_rng(seed).choice(n, sample, replace=False)) if n > sample else None
+    np.save(out / "conv_flag.npy", np.array(conv, dtype=np.float64))
+    for fetch in (e.download_rates, e.download_iter_state):
+        for name, v in fetch().items():
+            v = np.asarray(v, dtype=np.float64)
+            if v.ndim == 1 and v.size >= n and v.size % n == 0:
+                v = v.reshape(-1, n)
+                if idx is not None:
+                    v = v[:, idx]
+            np.save(out / f"{name}.npy", v)
+
+
 def launch_children(a):
     """`python bench.py --gpus N --launcher children`: start the N ranks as a CHILD torch.distributed.run and relay the one
     result line.  Runs before this process has imported torch or touched HIP (a process that has may not exec or be
@@ -263,7 +287,12 @@ def main():
     ap.add_argument("--mesh", type=int, default=256)
     ap.add_argument("--sources", type=int, default=None, help="config3: sources per GPU (default 8); config4: total (default 1024)")
     ap.add_argument("--batch", type=int, default=None)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baselines out")
+    ap.add_argument("--full", action="store_true",
+                    help="also time the CPU baselines (the oracle and the reference on the host cores) after the timed steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float64, a seeded sample of the cells "
+                         "of a large mesh)")
     ap.add_argument("--heating", action="store_true",
                     help="non-isothermal variant (heating tables, thermal evolution); not the headline config")
     ap.add_argument("--neutral-start", action="store_true",
@@ -405,9 +434,10 @@ def main():
     rates_launches = 0
     ndev_here = a.gpus if one_process else 1
     other = [{"swept": 0, "sweep_ms": 0.0, "rates_ms": 0.0, "chem_ms": 0.0} for _ in range(ndev_here - 1)]
+    conv = None
     t0 = time.perf_counter()
     for _ in range(a.steps):
-        step()
+        conv = step()
         tm = e.timing()
         sweep_ms += tm.sweep_ms
         rates_ms += tm.rates_ms
@@ -430,6 +460,9 @@ def main():
         allr = [mine] + [{"elapsed": elapsed, **o} for o in other]
     elapsed = max(r["elapsed"] for r in allr)
     swept_total = sum(r["swept"] for r in allr)
+
+    if rank == 0 and a.dump_outputs:
+        dump_outputs(e, conv, a.dump_outputs)
 
     if rank == 0:
         units = n ** 3 * total_src * a.steps
@@ -565,7 +598,7 @@ def main():
                     "value": rj.get("cell_updates_per_s_at_mesh_limit"), "s_per_iteration": rj.get("s_per_iteration"),
                     "sample": rj.get("what"), "how": rj.get("how"),
                     "where": rj.get("where", "dev container host cores"), "s_per_iteration_at_mesh_limit": rj.get("s_per_iteration_at_mesh_limit")}
-        if not a.no_cpu_baseline and world == 1 and not cfg4:
+        if a.full and not a.no_cpu_baseline and world == 1 and not cfg4:
             out["cpu_baseline"] = cpu_baseline(pkg)
             ref = cpu_baseline_reference()
             if ref is not None:

@@ -235,3 +235,39 @@ def test_rccl_comm_init_watchdog_ends_the_process(monkeypatch):
             if p.is_alive():
                 p.kill()
             p.join(timeout=30)
+
+
+def test_bench_dump_outputs_sample(tmp_path):
+    """bench.py --dump-outputs: every grid as (components, cells), at the same seeded cells in every run once the mesh has more
+    cells than the sample (at 256^3: 14 components x 2**18 cells of float64, 28 MB), whole on a smaller mesh."""
+    import bench
+
+    class Engine:
+        ncell = 5000
+
+        def download_rates(self):
+            n = self.ncell
+            return dict(phih_grid=np.arange(n) * 1.0, phihe_grid=np.arange(2 * n) * 2.0, phiheat=np.zeros(n),
+                        photon_loss=np.ones(47), sum_nbox=12)
+
+        def download_iter_state(self):
+            n = self.ncell
+            return dict(xh_av=np.arange(2 * n) + 0.5, xhe_av=np.arange(3 * n) + 0.25, xh_intermed=np.ones(2 * n), xhe_intermed=np.ones(3 * n))
+
+    def dump(name, sample):
+        bench.dump_outputs(Engine(), 1, tmp_path / name, sample=sample)
+        return {f.stem: np.load(f) for f in (tmp_path / name).glob("*.npy")}
+
+    a, b, whole = dump("a", 300), dump("b", 300), dump("whole", 5000)
+    assert all(v.dtype == np.float64 for v in a.values()) and a["conv_flag"] == 1 and a["sum_nbox"] == 12
+    assert a["photon_loss"].shape == (47,) and whole["xhe_av"].shape == (3, 5000)
+    assert np.array_equal(whole["xhe_av"].reshape(-1), np.arange(15000) + 0.25)
+    idx = a["phih_grid"][0].astype(np.int64)                     # phih_grid holds its own cell index
+    assert a["phih_grid"].shape == (1, 300) and len(set(idx)) == 300 and np.all(np.diff(idx) > 0)
+    assert np.array_equal(a["phihe_grid"], np.stack([2.0 * idx, 2.0 * (5000 + idx)]))
+    assert np.array_equal(a["xhe_av"], np.stack([c * 5000 + idx + 0.25 for c in range(3)]))
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k
+    import inspect
+    sample = inspect.signature(bench.dump_outputs).parameters["sample"].default
+    assert 14 * sample * 8 + 8 * (47 + 2) <= 64 << 20 < 14 * 256 ** 3 * 8   # at 256^3 the default sample stays under 64 MB
