@@ -1883,13 +1883,7 @@ extern "C" int c2r_create(c2r_ctx **out, int device, const int mesh[3]) {
     CR(hipStreamCreateWithPriority(&c->stream, hipStreamNonBlocking, hi));
     CR(hipStreamCreateWithPriority(&c->stream2, hipStreamNonBlocking, lo));
     CR(hipStreamCreateWithPriority(&c->stream3, hipStreamNonBlocking, lo));
-    {
-      // C2R_PROBE_PRIO (diagnostic): 0 = the sweep stream's (high) priority, 1 = default priority, 2 = low
-      const char *e = getenv("C2R_PROBE_PRIO");
-      const int mode = e ? atoi(e) : 0;
-      if (mode == 1) CR(hipStreamCreateWithFlags(&c->stream_probe, hipStreamNonBlocking));
-      else CR(hipStreamCreateWithPriority(&c->stream_probe, hipStreamNonBlocking, mode == 2 ? lo : hi));
-    }
+    CR(hipStreamCreateWithPriority(&c->stream_probe, hipStreamNonBlocking, hi));
     CR(hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
     CR(hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
     CR(hipEventCreateWithFlags(&c->ev_transposed, hipEventDisableTiming));
@@ -2641,7 +2635,6 @@ static int set_batch_one(c2r_ctx *c, int nbatch) {
 
 // host-side sub-box bookkeeping of one source (do_source, evolve_source.F90:96-144, 233-236)
 struct SrcRun {
-  int known_before = 0;   // prev_nbox of the source when the batch was first put together
   int ns;                 // 1-based source number
   int nbox = 0;
   double total_flux = 0, loss = 0;
@@ -2697,30 +2690,30 @@ static int pool_event(c2r_ctx *c, hipEvent_t *out) {
 }
 
 
-// Photon loss of the round's box for the sources h_list[set][list_off .. +n) (positions in the batch), full
-// (sample = 1) or sampled, into c->h_loss[0..n).  Synchronises the sweep stream.
-static int boundary_loss(c2r_ctx *c, int set, size_t list_off, int n, int s_lo, int s_hi, const Box &box, int sample,
+// A surface cell has one coordinate on a face of the box, so its shell is at least the nearest face's distance: the shells
+// of [s_lo, s_hi] before that hold none.  Their blocks (this many) are not launched and their partial sums are set to zero.
+static int blocks_before_surface(const c2r_ctx *c, const Box &box, int s_lo, int s_hi) {
+  int s_first = 1 << 30;
+  for (int d = 0; d < 3; d++) s_first = std::min(s_first, std::min(std::abs(box.lo[d]), std::abs(box.hi[d])));
+  s_first = std::min(std::max(s_first, s_lo), s_hi);
+  return c->block_base[s_first] - c->block_base[s_lo];
+}
+
+// Photon loss of the round's box for the sources h_list[set][list_off .. +n) (positions in the batch) into
+// c->h_loss[0..n).  Synchronises the sweep stream.
+static int boundary_loss(c2r_ctx *c, int set, size_t list_off, int n, int s_lo, int s_hi, const Box &box,
                          const StepScalars &sc, const SedSet &ss, bool multi) {
-  const int count = c->block_base[s_hi + 1] - c->block_base[s_lo];
-  const int nblk = (count + sample - 1) / sample;
+  const int nblk = c->block_base[s_hi + 1] - c->block_base[s_lo];
   const size_t need = (size_t)nblk * n;
   if (c->loss_partial_cap < need) {
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (ensure_pair<double>(c, &c->d_loss_partial, (double **)nullptr, &c->loss_partial_cap, need)) return 1;
   }
-  // a surface cell has one coordinate on a face of the box, so its shell is at least the nearest face's distance:
-  // the shells before that hold none, their blocks are not launched and their partial sums are set to zero
-  int first_block = 0;
-  if (sample == 1) {
-    int s_first = 1 << 30;
-    for (int d = 0; d < 3; d++) s_first = std::min(s_first, std::min(std::abs(box.lo[d]), std::abs(box.hi[d])));
-    s_first = std::min(std::max(s_first, s_lo), s_hi);
-    first_block = c->block_base[s_first] - c->block_base[s_lo];
-    if (first_block > 0) HIPCHK(c, zero_device(c->d_loss_partial, sizeof(double) * need, c->stream));
-  }
+  const int first_block = blocks_before_surface(c, box, s_lo, s_hi);
+  if (first_block > 0) HIPCHK(c, zero_device(c->d_loss_partial, sizeof(double) * need, c->stream));
   hipLaunchKernelGGL(k_loss, dim3(nblk - first_block, n), dim3(BLOCK), 0, c->stream, c->g, c->d_src[set], c->d_list[set] + list_off,
                      multi ? 1 : 0, s_lo, s_hi, box, sc, c->d_bands, ss, c->d_block_base, c->d_loss_partial, nblk,
-                     sample, first_block);
+                     1, first_block);
   hipLaunchKernelGGL(k_loss_finish, dim3(n), dim3(BLOCK), 0, c->stream, c->d_loss_partial, nblk, nblk, c->d_loss_acc);
   c->tm.sweep_launches += 2;
   HIPCHK(c, hipGetLastError());
@@ -2745,14 +2738,47 @@ struct RoundRec {
   Box box{};
 };
 
-// Queue the probes of the rounds recs[from .. to) (lower bounds of their boundary losses, k_loss_probe_rounds) on the probe
-// stream, behind everything queued on the sweep stream so far, and the copy of all their results to h_probe; ev_probe
+// What the batches of one pass share.
+struct PassCtx {
+  c2r_ctx *c;
+  StepScalars sc;
+  SedSet ss;
+  bool multi;
+  Reach reach;
+  bool generic_sweep;           // C2R_SWEEP_GENERIC=1 (diagnostic): every shell through the general per-cell code, one launch per shell
+  bool arena_log;               // C2R_ARENA_LOG: say when a batch is cut or starts over
+  bool packed_early = false;    // the mesh-ordered products need not wait for anything
+  bool transposed_seen = false; // the sweep stream has waited for ev_transposed
+  int nslab = 0;                // rate-grid slabs of the last batch (0: one rates launch)
+  std::vector<hipEvent_t> tev;  // per batch: sweep start, sweep end, rates start, rates end
+};
+
+// One batch: the sources mine[b0 .. b0 + nb) on scratch set `set`.
+struct Batch {
+  int set = 0, nb = 0;
+  size_t b0 = 0;
+  std::vector<int> known0; // what the last pass knew about the batch's sources (a batch that starts over raises prev_nbox)
+  int restarts = 0;
+  hipEvent_t ev[4] = {};   // timing: sweep start, sweep end, rates start, rates end
+  // one attempt: a batch that starts over begins these anew
+  std::vector<SrcRun> run;
+  size_t list_used = 0;             // entries of h_list[set] / d_list[set] in use
+  std::vector<RoundRec> recs;       // the rounds swept so far
+  size_t settled = 0, launched = 0; // recs[0, settled): while-test applied; recs[settled, launched): probes in flight
+  bool sweep_started = false;       // ev[0] goes in front of the first shell launch, behind the uploads of records and lists
+  int ntiles = 0;                   // tiles in the rates launch's list h_tiles[set] (0: none, every tile of the mesh)
+};
+
+// Queue the probes of the batch's rounds recs[launched ..) (lower bounds of their boundary losses, k_loss_probe_rounds) on
+// the probe stream, behind everything queued on the sweep stream so far, and the copy of all their results to h_probe; ev_probe
 // marks the end.  Does not wait.  One event on the sweep stream for all of them: the rounds of a batch whose
 // sources are all expected to go on (prev_nbox) are probed together, late, and the sweep stream sees no probe
 // kernel, no copy and no other event between its shells.  Whoever then changes what a probe reads -- the SrcDev
 // entries, when a block moves -- waits for ev_probe first.
-static int launch_probes(c2r_ctx *c, int set, const std::vector<RoundRec> &recs, size_t from, size_t to, const StepScalars &sc,
-                         const SedSet &ss, bool multi) {
+static int launch_probes(const PassCtx &P, Batch &B) {
+  c2r_ctx *c = P.c;
+  const std::vector<RoundRec> &recs = B.recs;
+  const size_t from = B.launched, to = recs.size();
   if (from >= to) return 0;
   size_t need = 0;
   for (size_t i = from; i < to; i++) {
@@ -2766,13 +2792,9 @@ static int launch_probes(c2r_ctx *c, int set, const std::vector<RoundRec> &recs,
     HIPCHK(c, hipStreamSynchronize(c->stream_probe)); // earlier probes may still use the old buffer
     if (ensure_pair<double>(c, &c->d_probe_partial, (double **)nullptr, &c->probe_partial_cap, need)) return 1;
   }
-#ifdef C2R_PROBE_INLINE
-  hipStream_t st = c->stream;
-#else
   hipStream_t st = c->stream_probe;
   HIPCHK(c, hipEventRecord(c->ev_round, c->stream));
   HIPCHK(c, hipStreamWaitEvent(st, c->ev_round, 0));
-#endif
   // descriptors of the rounds, then one probe launch and one finishing launch for all of them
   const size_t nr = to - from;
   if (c->probe_rounds_cap < nr) {
@@ -2801,8 +2823,8 @@ static int launch_probes(c2r_ctx *c, int set, const std::vector<RoundRec> &recs,
     max_nact = std::max(max_nact, P.nact);
   }
   HIPCHK(c, hipMemcpyAsync(c->d_probe_rounds, hr, sizeof(ProbeRound) * nr, hipMemcpyHostToDevice, st));
-  hipLaunchKernelGGL(k_loss_probe_rounds, dim3(max_nblk, max_nact, (unsigned)nr), dim3(BLOCK), 0, st, c->g, c->d_src[set], c->d_list[set],
-                     static_cast<const ProbeRound *>(c->d_probe_rounds), multi ? 1 : 0, sc, c->d_bands, ss, c->d_block_base,
+  hipLaunchKernelGGL(k_loss_probe_rounds, dim3(max_nblk, max_nact, (unsigned)nr), dim3(BLOCK), 0, st, c->g, c->d_src[B.set], c->d_list[B.set],
+                     static_cast<const ProbeRound *>(c->d_probe_rounds), P.multi ? 1 : 0, P.sc, c->d_bands, P.ss, c->d_block_base,
                      c->d_probe_partial, PROBE_SAMPLE);
   hipLaunchKernelGGL(k_loss_finish_rounds, dim3(max_nact, (unsigned)nr), dim3(BLOCK), 0, st,
                      static_cast<const ProbeRound *>(c->d_probe_rounds), c->d_probe_partial, c->d_probe_acc);
@@ -2811,6 +2833,7 @@ static int launch_probes(c2r_ctx *c, int set, const std::vector<RoundRec> &recs,
   const size_t a0 = recs[from].acc_off;
   HIPCHK(c, hipMemcpyAsync(c->h_probe + a0, c->d_probe_acc + a0, sizeof(double) * (acc_need - a0), hipMemcpyDeviceToHost, st));
   HIPCHK(c, hipEventRecord(c->ev_probe, st));
+  B.launched = to;
   return 0;
 }
 
@@ -2820,7 +2843,6 @@ static int launch_probes(c2r_ctx *c, int set, const std::vector<RoundRec> &recs,
 // batch's sweep overlaps it (scratch sets ping-pong).  Rates launches are ordered on their stream,
 // so the accumulation over sources keeps the reference's order.
 static int pass_finish(c2r_ctx *c);
-static int flush_rates_zero(c2r_ctx *c);
 
 // the losses of set `set`'s batches that were still on their way from the device (the caller has waited for the
 // set's last rates launch and what follows it)
@@ -2831,6 +2853,574 @@ static void resolve_tails(c2r_ctx *c, int set) {
       if (bt.slot[b] >= 0) bt.loss[b] = c->h_final[set][bt.slot[b]];
     bt.resolved = true;
   }
+}
+
+constexpr int START_OVER = 2; // sweep_batch: the batch has to start over (0: swept, 1: error)
+
+// The products neufrac * ndens the sweep reads (k_pack_state; xh_av, xhe_av change every iteration), in mesh order and in
+// (j,i,k) order: made on the third stream while the inner shells, which do without them, are already on their way.
+static int queue_state_products(c2r_ctx *c) {
+  const Grid &g = c->g;
+  HIPCHK(c, hipStreamWaitEvent(c->stream3, c->ev_sweep_done[0], 0));
+  // both valid: nothing to make, the global pass transposed its own products (ev_transposed is on record since then)
+  const bool make = !(c->packed_valid && c->transposed_valid);
+  if (make && c->packed_valid)
+    hipLaunchKernelGGL(k_transpose_packed, dim3((g.n1 + 31) / 32, (g.n2 + 31) / 32, 3 * g.n3), dim3(BLOCK), 0, c->stream3, g,
+                       c->d_stateT, c->d_stateT + 3 * g.ncell);
+  else if (make)
+    hipLaunchKernelGGL(k_pack_state, dim3((g.n1 + 31) / 32, (g.n2 + 31) / 32, g.n3), dim3(BLOCK), 0, c->stream3, g, c->d_ndens, c->d_xh_av,
+                       c->d_xhe_av, c->d_stateT, c->d_stateT + 3 * g.ncell);
+  HIPCHK(c, hipGetLastError());
+  if (make) HIPCHK(c, hipEventRecord(c->ev_transposed, c->stream3));
+  return 0;
+}
+
+// Column blocks of the batch (predicted_shells), their SrcDev entries and the sources' fluxes; B.nb becomes what fits.
+// Segments are kept from batch to batch and pass to pass (allocation is slow), so what the set holds may be cut for other
+// block sizes than this batch needs (many small segments of a pass with small boxes).  When the blocks do not fit although
+// less than half of what the set holds is in use, its segments are given back and made anew in one piece; otherwise the
+// batch is what did fit.
+static int place_batch(const PassCtx &P, const std::vector<int> &mine, Batch &B) {
+  c2r_ctx *c = P.c;
+  const int set = B.set;
+  SrcDev *hs = c->h_src[set];
+  B.run.assign((size_t)B.nb, SrcRun());
+  for (bool released = false;;) {
+    c->seg_cur[set] = 0;
+    c->seg_used[set] = 0;
+    c->vacated[set].clear();
+    size_t total = 0;
+    for (int b = 0; b < B.nb; b++) total += block_doubles(predicted_shells(c, mine[B.b0 + b]));
+    int placed = 0;
+    size_t placed_doubles = 0;
+    for (; placed < B.nb; placed++) {
+      SrcRun &r = B.run[placed];
+      r.ns = mine[B.b0 + placed];
+      r.cap = predicted_shells(c, r.ns);
+      const size_t w = (size_t)(2 * r.cap + 1);
+      hs[placed].cz = w * w * w;
+      hs[placed].cols = arena_alloc(c, set, 6 * hs[placed].cz, total);
+      if (!hs[placed].cols) break;
+      total -= 6 * hs[placed].cz;
+      placed_doubles += 6 * hs[placed].cz;
+    }
+    if (placed == B.nb) break;
+    size_t have = 0;
+    for (const c2r_ctx::Segment &sg : c->segs[set]) have += sg.n;
+    if (!released && have > 0 && placed_doubles < have / 2) {
+      released = true;
+      arena_release(c, set);
+      continue;
+    }
+    if (placed == 0) return fail(c, "column scratch: one source of this mesh does not fit in device memory");
+    // A batch cut to exactly what fits has no room for a source that outgrows its block (the deeper block is needed
+    // while the old one is still in use) and starts over at the first such move -- at 512^3, where a block at the mesh
+    // limit is 6.4 GB and a set holds some twenty, 615 times in six passes (round 5).  So the cut leaves room for a third
+    // of the sources that can still grow to move once; sources at the mesh limit need none.
+    int keep = placed;
+    for (;;) {
+      size_t used = 0, reserve = 0;
+      for (int b = 0; b < keep; b++) {
+        used += 6 * hs[b].cz;
+        if (B.run[b].cap < c->g.smax) reserve += block_doubles(std::min(c->g.smax, 2 * B.run[b].cap));
+      }
+      if (keep <= 1 || used + reserve / 3 <= placed_doubles) break;
+      keep--;
+    }
+    if (P.arena_log) fprintf(stderr, "c2ray_hip: column scratch, set %d: batch of %d cut to %d sources (%d fit)\n", set, B.nb, keep, placed);
+    B.nb = keep; // the same calls place the same blocks again
+    B.run.resize((size_t)B.nb);
+  }
+  for (int b = 0; b < B.nb; b++) {
+    SrcRun &r = B.run[b];
+    r.total_flux = c->normflux[r.ns - 1] * c->s_star; // evolve_source.F90:122-128
+    for (int k = 0; k < 2; k++)
+      if (P.multi && !c->normflux_sed[k].empty())
+        r.total_flux = r.total_flux + c->normflux_sed[k][r.ns - 1] * c->s_star_sed[k];
+    r.loss = r.total_flux;
+    SrcDev &S = hs[b];
+    const int *p = &c->srcpos[3 * (size_t)(r.ns - 1)];
+    S.i0 = p[0]; S.j0 = p[1]; S.k0 = p[2];
+    for (int d = 0; d < 3; d++) { S.lo[d] = 0; S.hi[d] = 0; }
+    S.nflux = c->normflux[r.ns - 1];
+    for (int k = 0; k < 2; k++) S.nflux_sed[k] = c->normflux_sed[k].empty() ? 0.0 : c->normflux_sed[k][r.ns - 1];
+  }
+  // coldensh_out = 0 for every new source (evolve_source.F90:94-95) serves two purposes in the
+  // reference: the "already done" marker (replaced here by the shell order: every cell is visited
+  // once) and finite values for corners whose interpolation weight is exactly 0.  The arena is
+  // zeroed once at allocation and only ever holds finite columns afterwards, so 0*w stays 0.
+  HIPCHK(c, hipMemcpyAsync(c->d_src[set], hs, sizeof(SrcDev) * B.nb, hipMemcpyHostToDevice, c->stream));
+  return 0;
+}
+
+// Read the probes of all rounds not yet decided, replace what a probe leaves undecided by the full sum, apply the while-test
+// round by round: sources that stop get active = false and that round as their last.
+static int settle_rounds(const PassCtx &P, Batch &B) {
+  c2r_ctx *c = P.c;
+  if (B.settled == B.recs.size()) return 0;
+  if (launch_probes(P, B)) return 1;
+  HIPCHK(c, hipEventSynchronize(c->ev_probe));
+  int *hl = c->h_list[B.set];
+  for (; B.settled < B.recs.size(); B.settled++) {
+    const RoundRec &R = B.recs[B.settled];
+    const double *probe = c->h_probe + R.acc_off;
+    const int *lst = hl + R.off;
+    std::vector<int> undecided;
+    for (int a = 0; a < R.nact; a++) {
+      SrcRun &r = B.run[lst[a]];
+      if (!r.active) continue; // stopped at an earlier round: swept this one on trust, to no effect
+      r.loss = probe[a];
+      if (!(r.loss > 2.0 * (C2R_F(1e-10) * r.total_flux))) undecided.push_back(lst[a]);
+    }
+    if (!undecided.empty()) {
+      int *ul = hl + B.list_used;
+      std::copy(undecided.begin(), undecided.end(), ul);
+      HIPCHK(c, hipMemcpyAsync(c->d_list[B.set] + B.list_used, ul, sizeof(int) * undecided.size(), hipMemcpyHostToDevice, c->stream));
+      if (boundary_loss(c, B.set, B.list_used, (int)undecided.size(), R.s_lo, R.s_hi, R.box, P.sc, P.ss, P.multi)) return 1;
+      B.list_used += undecided.size();
+      for (size_t j = 0; j < undecided.size(); j++) B.run[undecided[j]].loss = c->h_loss[j];
+    }
+    for (int a = 0; a < R.nact; a++) {
+      SrcRun &r = B.run[lst[a]];
+      if (!r.active) continue;
+      if (!(r.loss > C2R_F(1e-10) * r.total_flux)) { // evolve_source.F90:136: the box does not grow any more
+        r.active = false;
+        r.nbox = R.round;
+      }
+    }
+  }
+  return 0;
+}
+
+// every source still active reached at least round `round` in the previous pass
+static bool all_reached(const c2r_ctx *c, const Batch &B, int round) {
+  for (const SrcRun &r : B.run)
+    if (r.active && c->prev_nbox[(size_t)r.ns - 1] < round) return false;
+  return true;
+}
+
+// Source b's column block moves to `ncols`, made for shells 0..ncap (the shells stored so far are a prefix of every array).
+static int move_block(const PassCtx &P, Batch &B, int b, int ncap, double *ncols) {
+  c2r_ctx *c = P.c;
+  SrcRun &r = B.run[b];
+  // probes in flight read this source's SrcDev entry: they must be through before the entry changes
+  if (B.launched > B.settled) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_probe, 0));
+  SrcDev &S = c->h_src[B.set][b];
+  const size_t wn = (size_t)(2 * ncap + 1), ncz = wn * wn * wn;
+  const size_t wp = (size_t)(2 * r.smax_prev + 1), have = r.smax_prev >= 0 ? wp * wp * wp : 0;
+  // the shells stored so far are a prefix of each array (or of each array of triples)
+  for (int half = 0; half < 2 && have > 0; half++) {
+    const bool triples = C2R_COLS_AOS == 1 || C2R_COLS_AOS == (half ? 3 : 2);
+    for (int k = 0; k < (triples ? 1 : 3); k++) {
+      const size_t at = (size_t)(3 * half + k);
+      HIPCHK(c, hipMemcpyAsync(ncols + at * ncz, S.cols + at * S.cz, sizeof(double) * (triples ? 3 : 1) * have,
+                               hipMemcpyDeviceToDevice, c->stream));
+    }
+  }
+  if (S.cz > 0) c->vacated[B.set].push_back(c2r_ctx::Segment{S.cols, 6 * S.cz}); // free for the batch's later moves
+  S.cols = ncols;
+  S.cz = ncz;
+  r.cap = ncap;
+  c->arena_stats[3]++;
+  HIPCHK(c, hipMemcpyAsync(c->d_src[B.set] + b, &S, sizeof(SrcDev), hipMemcpyHostToDevice, c->stream));
+  return 0;
+}
+
+// No room left on the device in the middle of a sweep.  Nothing of this batch has reached the rate grids yet, so the
+// batch starts over with what this attempt has taught (sources that have stopped get the block they needed, those still
+// growing the mesh limit) and, since even that did not fit, with fewer sources.  Returns START_OVER or 1 (error).
+static int start_over(const PassCtx &P, Batch &B, int round) {
+  c2r_ctx *c = P.c;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream_probe));
+  // (round 5: a source still growing when the room ran out is given the mesh limit, not two rounds more -- at 512^3
+  // the fronts of a whole batch race there together, and "two more" made every batch start over twice)
+  const int limit_rounds = (c->g.smax + SUBBOXSIZE - 1) / SUBBOXSIZE;
+  for (const SrcRun &r : B.run) {
+    int &pn = c->prev_nbox[(size_t)r.ns - 1];
+    pn = std::max(pn, r.active ? limit_rounds : r.nbox);
+  }
+  if (B.nb == 1) return fail(c, "column scratch: one source of this mesh does not fit in device memory");
+  if (P.arena_log) fprintf(stderr, "c2ray_hip: column scratch, set %d: no room to grow in round %d, batch of %d starts over\n", B.set, round, B.nb);
+  // the first time with the same sources: blocks made for what is known now need no moves, and what a move leaves
+  // behind is most of what filled the set; a batch that runs out of room again is halved
+  if (B.restarts++ > 0) B.nb = (B.nb + 1) / 2;
+  c->arena_stats[4]++;
+  return START_OVER;
+}
+
+// the shells s_lo..s_hi of `box` for the nact sources of d_list[set][act_off ..), on the sweep stream
+static int launch_shells(PassCtx &P, Batch &B, const Box &box, int s_lo, int s_hi, size_t act_off, int nact) {
+  c2r_ctx *c = P.c;
+  SweepArgs SA;
+  SA.g = c->g; SA.box = box; SA.sc = P.sc;
+  SA.ndens = c->d_ndens; SA.xh_av = c->d_xh_av; SA.xhe_av = c->d_xhe_av;
+  SA.lls_grid = c->lls_on_grid ? c->d_lls : nullptr;
+  if (c->timing && !B.sweep_started) {
+    HIPCHK(c, hipEventRecord(B.ev[0], c->stream));
+    B.sweep_started = true;
+  }
+  for (int s = s_lo; s <= s_hi; s++) {
+    // (a large batch waits at once: its many small faces would pay more for strided reads than the wait costs)
+    if ((s >= TRANSPOSED_FROM_SHELL || B.nb > 16) && !P.transposed_seen) {
+      HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_transposed, 0));
+      P.transposed_seen = true;
+    }
+    SA.packed = SA.packedT = nullptr;
+    if (P.transposed_seen || P.packed_early) SA.packed = c->d_stateT;
+    if (P.transposed_seen) SA.packedT = c->d_stateT + 3 * c->g.ncell;
+    const int nblk = c->block_base[s + 1] - c->block_base[s];
+    // from 64 blocks on: a multiple of 8 blocks, one contiguous eighth of the shell per XCD (see the kernel)
+    const int nlaunch = nblk >= 64 ? ((nblk + 7) & ~7) : nblk;
+    if (s >= 2 && s <= SHELL_FAST_MAX && !P.generic_sweep)
+      hipLaunchKernelGGL(k_sweep_shell_fast, dim3(nlaunch, nact), dim3(BLOCK), 0, c->stream, SA, c->d_src[B.set],
+                         c->d_list[B.set] + act_off, c->shell_geom[(size_t)s]);
+    else
+      hipLaunchKernelGGL(k_sweep_shell, dim3(nlaunch, nact), dim3(BLOCK), 0, c->stream, SA, c->d_src[B.set], c->d_list[B.set] + act_off, s);
+    c->tm.sweep_launches++;
+  }
+  HIPCHK(c, hipGetLastError());
+  return 0;
+}
+
+// The sub-box loop (evolve_source.F90:136-144).  After the shells of round r the loss through the box surface decides who
+// sweeps round r+1; a quick lower bound of it (k_loss_probe_rounds) nearly always does.  When every active source went
+// beyond round r in the previous pass (prev_nbox), round r+1 is launched at once for all of them, on trust, and the probe of
+// round r is not even queued yet: the probes of all such rounds go out together, on their own stream, when a decision is
+// really needed -- before a round that some source did not reach last time, or before the round that is everybody's last
+// for geometric reasons -- so that the sweep stream carries shells and nothing else (a probe per round cost it an event,
+// and 13-24 us of gap at each of the 12 round boundaries of a 256^3 sweep).  A source that turns out to have stopped at r
+// keeps round r as its last -- its shells of later rounds are never looked at (the rates launch only sees the final box),
+// so a wrong guess costs time, never a bit.  Returns 0, 1 (error) or START_OVER.
+static int sweep_batch(PassCtx &P, Batch &B) {
+  c2r_ctx *c = P.c;
+  const Reach &reach = P.reach;
+  B.list_used = 0;
+  B.recs.clear();
+  B.settled = B.launched = 0;
+  B.sweep_started = false;
+  const size_t acc_need = (size_t)B.nb * (size_t)(c->g.smax / SUBBOXSIZE + 3);
+  if (c->probe_acc_cap < acc_need) {
+    HIPCHK(c, hipStreamSynchronize(c->stream_probe));
+    if (ensure_pair<double>(c, &c->d_probe_acc, &c->h_probe, &c->probe_acc_cap, acc_need)) return 1;
+  }
+  int *hl = c->h_list[B.set];
+  size_t cur_off = 0; // the active list of the last round launched
+  int cur_nact = 0;
+  size_t acc_used = 0;
+  for (int round = 1;; round++) {
+    const Box box = round_box(reach, round);
+    const int s_hi = box_smax(box);
+    // may this round start before the losses of the rounds before it are known?
+    const bool ahead = round > 1 && cur_nact > 0 && all_reached(c, B, round);
+    if (!ahead && settle_rounds(P, B)) return 1;
+    // who sweeps this round: the while-test of evolve_source.F90:136-139 (its loss part taken on trust when ahead)
+    int nact = 0;
+    int *act = hl + B.list_used;
+    int s_lo = 1 << 30;
+    for (int b = 0; b < B.nb; b++) {
+      SrcRun &r = B.run[b];
+      if (!r.active) continue;
+      if (!box_can_grow(reach, round_box(reach, r.nbox)) || !(ahead || r.loss > C2R_F(1e-10) * r.total_flux)) {
+        r.active = false;
+        continue;
+      }
+      r.nbox = round;
+      act[nact++] = b;
+      s_lo = std::min(s_lo, r.smax_prev + 1);
+    }
+    if (nact == 0) return settle_rounds(P, B);
+    if (s_hi > c->g.smax) return fail(c, "internal: shell %d beyond smax %d", s_hi, c->g.smax);
+    // blocks too small for this round move to larger ones
+    for (int a = 0; a < nact; a++) {
+      const int cap = B.run[act[a]].cap;
+      if (cap >= s_hi) continue;
+      const int ncap = std::min(c->g.smax, std::max(s_hi, 2 * cap));
+      double *ncols = arena_alloc(c, B.set, block_doubles(ncap));
+      if (!ncols) return start_over(P, B, round);
+      if (move_block(P, B, act[a], ncap, ncols)) return 1;
+    }
+    // the same sources as in the last round: the list is on the device already
+    size_t act_off = B.list_used;
+    if (cur_nact == nact && round > 1 && std::equal(act, act + nact, hl + cur_off)) {
+      act_off = cur_off;
+    } else {
+      HIPCHK(c, hipMemcpyAsync(c->d_list[B.set] + B.list_used, act, sizeof(int) * nact, hipMemcpyHostToDevice, c->stream));
+      B.list_used += (size_t)nact;
+    }
+    cur_off = act_off;
+    cur_nact = nact;
+    if (launch_shells(P, B, box, s_lo, s_hi, act_off, nact)) return 1;
+    for (int a = 0; a < nact; a++) B.run[hl[act_off + a]].smax_prev = s_hi;
+    if (!box_can_grow(reach, box)) {
+      // The while-test after this round fails whatever the loss: the round is every active source's last, and
+      // its loss (the one that is kept, evolve_source.F90:233) is queued behind the rates launch (queue_kept_losses).
+      // The rounds before it are decided now; their probes were queued before this round's shells.
+      if (settle_rounds(P, B)) return 1;
+      for (int a = 0; a < nact; a++) {
+        SrcRun &r = B.run[hl[act_off + a]];
+        if (!r.active) continue; // stopped a round earlier after all
+        r.final_loss_due = true;
+        r.active = false;
+      }
+      return 0;
+    }
+    // The loss of this round decides whether a source goes on.
+    RoundRec R;
+    R.round = round; R.nact = nact; R.s_lo = s_lo; R.s_hi = s_hi; R.off = act_off; R.acc_off = acc_used; R.box = box;
+    acc_used += (size_t)nact;
+    B.recs.push_back(R);
+    // Its probe goes out now if the next round needs the answer before it can start (somebody may stop here) or if
+    // the next round is the last for geometric reasons (the probes then run beside its shells, and the answers
+    // are there when the rates launch has to be put together); otherwise it waits for company.
+    const bool next_is_last = !box_can_grow(reach, round_box(reach, round + 1));
+    if ((!all_reached(c, B, round + 1) || next_is_last) && launch_probes(P, B)) return 1;
+  }
+}
+
+// Final sub-boxes for the rates launch, what the next pass learns from this one (prev_nbox, prev_grow), the upload of the
+// SrcDev entries; then the rates stream takes the batch over.
+static int close_boxes(PassCtx &P, Batch &B) {
+  c2r_ctx *c = P.c;
+  for (int b = 0; b < B.nb; b++) {
+    const SrcRun &r = B.run[b];
+    SrcDev &S = c->h_src[B.set][b];
+    const Box fb = round_box(P.reach, r.nbox);
+    for (int d = 0; d < 3; d++) { S.lo[d] = fb.lo[d]; S.hi[d] = fb.hi[d]; }
+    // a source whose while-test failed before the first sub-box (a mesh only two cells deep) traced nothing:
+    // an empty box, so that no cell passes the in-box test
+    if (r.nbox == 0) { S.lo[0] = 1; S.hi[0] = 0; }
+    // the terms of the kept loss of a round that was the last for geometric reasons come out of the rates launch: the
+    // surface cells in the shells of that round (heating kernels do not keep photo_out, see k_rates)
+    S.loss_lo = -1;
+    if (r.final_loss_due && c->isothermal) S.loss_lo = r.nbox > 1 ? box_smax(round_box(P.reach, r.nbox - 1)) + 1 : 0;
+    // (known0: what was known before this batch -- a batch that started over has raised prev_nbox meanwhile)
+    const int known = B.known0[(size_t)b];
+    c->prev_grow[(size_t)r.ns - 1] = known > 0 ? std::max(0, r.nbox - known) : 0;
+    c->prev_nbox[(size_t)r.ns - 1] = r.nbox;
+  }
+  if (c->timing) { // the sweep's span: from the first shell launch to the last, record uploads on either side left out
+    if (!B.sweep_started) HIPCHK(c, hipEventRecord(B.ev[0], c->stream));
+    HIPCHK(c, hipEventRecord(B.ev[1], c->stream));
+  }
+  HIPCHK(c, hipMemcpyAsync(c->d_src[B.set], c->h_src[B.set], sizeof(SrcDev) * B.nb, hipMemcpyHostToDevice, c->stream));
+  if (!P.transposed_seen) {
+    // small boxes only: nobody needed the copies, but whatever follows this sweep (the global pass rewrites the
+    // state) has to come after the kernel that reads it
+    HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_transposed, 0));
+    P.transposed_seen = true;
+  }
+  HIPCHK(c, hipEventRecord(c->ev_sweep_done[B.set], c->stream));
+  // rates of the whole batch, in source order, on the second stream
+  HIPCHK(c, hipStreamWaitEvent(c->stream2, c->ev_sweep_done[B.set], 0));
+  if (c->timing) HIPCHK(c, hipEventRecord(B.ev[2], c->stream2));
+  return 0;
+}
+
+// Tiles (8 x 8 x 4 cells) that intersect the final sub-box of some source of the batch, and per tile the sources that do,
+// copied to the device on the rates stream; B.ntiles = 0 when every tile of the mesh walks every source of the batch.
+static int build_tile_lists(const PassCtx &P, Batch &B) {
+  c2r_ctx *c = P.c;
+  const Grid &g = c->g;
+  const int mesh[3] = {g.n1, g.n2, g.n3};
+  const int nt1 = (g.n1 + 7) / 8, nt2 = (g.n2 + 7) / 8, nt3 = (g.n3 + 3) / 4;
+  const int nblk = nt1 * nt2 * nt3;
+  B.ntiles = 0;
+  bool full = false;
+  for (int b = 0; b < B.nb && !full; b++) {
+    const Box fb = round_box(P.reach, B.run[b].nbox);
+    full = B.run[b].nbox > 0;
+    for (int d = 0; d < 3; d++) full = full && (fb.hi[d] - fb.lo[d] + 1 >= mesh[d]);
+  }
+  // few sources one of which fills the mesh: every cell simply walks all of them
+  if (full && B.nb <= 16) return 0;
+  std::vector<int> &cnt = c->tile_count;
+  cnt.assign((size_t)nblk, 0);
+  std::vector<int> cov[3];
+  const int tsz[3] = {8, 8, 4}, ntd[3] = {nt1, nt2, nt3};
+  auto covered = [&](int b) {
+    const Box fb = round_box(P.reach, B.run[b].nbox);
+    const int *p = &c->srcpos[3 * (size_t)(B.run[b].ns - 1)];
+    for (int d = 0; d < 3; d++) {
+      cov[d].clear();
+      int last = -1;
+      std::vector<unsigned char> seen((size_t)ntd[d], 0);
+      for (int o = fb.lo[d]; o <= fb.hi[d]; o++) {
+        int x = (p[d] - 1 + o) % mesh[d];
+        if (x < 0) x += mesh[d];
+        const int t = x / tsz[d];
+        if (t != last && !seen[t]) { seen[t] = 1; cov[d].push_back(t); }
+        last = t;
+      }
+    }
+  };
+  size_t total = 0;
+  for (int b = 0; b < B.nb; b++) {
+    if (B.run[b].nbox == 0) continue;
+    covered(b);
+    for (int tk : cov[2])
+      for (int tj_ : cov[1]) {
+        int *row = &cnt[((size_t)tk * nt2 + tj_) * nt1];
+        for (int ti_ : cov[0]) row[ti_]++;
+      }
+    total += cov[0].size() * cov[1].size() * cov[2].size();
+  }
+  const int set = B.set;
+  if (ensure_pair<int>(c, &c->d_tsrc[set], &c->h_tsrc[set], &c->tsrc_cap[set], total + 1)) return 1;
+  int *list = c->h_tiles[set], *tp = c->h_tptr[set], *tsrc = c->h_tsrc[set];
+  int ntl = 0;
+  size_t acc = 0;
+  for (int t = 0; t < nblk; t++) {
+    if (!cnt[t]) { cnt[t] = -1; continue; }
+    list[ntl] = t;
+    tp[ntl] = (int)acc;
+    acc += (size_t)cnt[t];
+    cnt[t] = ntl++; // from count to position in the list
+  }
+  if (ntl == 0) { list[0] = 0; tp[0] = 0; ntl = 1; }
+  tp[ntl] = (int)acc;
+  std::vector<int> fill(tp, tp + ntl);
+  for (int b = 0; b < B.nb; b++) { // ascending b: every tile's sources end up in source order
+    if (B.run[b].nbox == 0) continue;
+    covered(b);
+    for (int tk : cov[2])
+      for (int tj_ : cov[1]) {
+        const int *row = &cnt[((size_t)tk * nt2 + tj_) * nt1];
+        for (int ti_ : cov[0]) tsrc[fill[row[ti_]]++] = b;
+      }
+  }
+  HIPCHK(c, hipMemcpyAsync(c->d_tiles[set], list, sizeof(int) * (size_t)ntl, hipMemcpyHostToDevice, c->stream2));
+  HIPCHK(c, hipMemcpyAsync(c->d_tptr[set], tp, sizeof(int) * (size_t)(ntl + 1), hipMemcpyHostToDevice, c->stream2));
+  if (acc > 0) HIPCHK(c, hipMemcpyAsync(c->d_tsrc[set], tsrc, sizeof(int) * acc, hipMemcpyHostToDevice, c->stream2));
+  B.ntiles = ntl;
+  return 0;
+}
+
+// The rates of the batch on the rates stream: a pending zeroing of the rate grids first, then one launch, or for the last
+// batch of a pass the caller takes slab by slab, one launch per slab with an event behind each.
+static int launch_rates(const PassCtx &P, Batch &B, bool last_batch) {
+  c2r_ctx *c = P.c;
+  const bool lists = B.ntiles > 0;
+  const size_t nc = c->g.ncell;
+  // a pending set_rates_to_zero: this launch writes the grids if it covers every cell, else they are zeroed now
+  // (on the rates stream, which this batch's launches follow)
+  int fresh = 0;
+  if (c->rates_zero_pending) {
+    if (!lists) {
+      fresh = 1;
+      c->rates_zero_pending = false;
+      if (c->isothermal && c->phiheat_dirty) { // phiheat of an earlier heating step: not written by this launch
+        HIPCHK(c, zero_device(c->d_rates + 3 * nc, sizeof(double) * nc, c->stream2));
+        c->phiheat_dirty = false;
+      }
+    } else {
+      c->rates_zero_pending = false;
+      c->phiheat_dirty = false;
+      // (the four grids only: the tail of the buffer is written at the end of this pass, on the other stream)
+      HIPCHK(c, zero_device(c->d_rates, sizeof(double) * 4 * nc, c->stream2));
+    }
+  }
+  if (!c->isothermal) c->phiheat_dirty = true;
+  const bool slabs = last_batch && P.nslab > 0;
+  const int pieces = slabs ? P.nslab : 1;
+  const int per_layer = ((c->g.n1 + 7) / 8) * ((c->g.n2 + 7) / 8), nt3 = (c->g.n3 + 3) / 4;
+  // slabs alternate between two streams so that the thin tail of one launch overlaps the start of the
+  // next; the third stream is forked from (and joined back into) the rates stream, which carries the
+  // dependencies on the sweep, on earlier batches and on the tile-list copy
+  if (pieces > 1) {
+    HIPCHK(c, hipEventRecord(c->ev_fork, c->stream2));
+    HIPCHK(c, hipStreamWaitEvent(c->stream3, c->ev_fork, 0));
+  }
+  for (int piece = 0; piece < pieces; piece++) {
+    hipStream_t st = (pieces > 1 && (piece & 1)) ? c->stream3 : c->stream2;
+    // tiles of the layers [l0, l1): a contiguous range of tile ids, hence of the (sorted) list too
+    const int l0 = pieces == 1 ? 0 : c->slab_k[piece] / 4;
+    const int l1 = pieces == 1 ? nt3 : (c->slab_k[piece + 1] + 3) / 4;
+    int base, cnt;
+    if (lists) {
+      const int *list = c->h_tiles[B.set];
+      base = (int)(std::lower_bound(list, list + B.ntiles, l0 * per_layer) - list);
+      cnt = (int)(std::lower_bound(list, list + B.ntiles, l1 * per_layer) - list) - base;
+    } else {
+      base = l0 * per_layer;
+      cnt = (l1 - l0) * per_layer;
+    }
+    auto go = [&](auto kernel) {
+      hipLaunchKernelGGL(kernel, dim3(cnt), dim3(BLOCK), 0, st, c->g, c->d_src[B.set], B.nb, P.sc, c->d_ndens, c->d_xh_av, c->d_xhe_av,
+                         c->d_bands, P.ss, c->d_rates, lists ? c->d_tiles[B.set] : nullptr, lists ? c->d_tptr[B.set] : nullptr,
+                         lists ? c->d_tsrc[B.set] : nullptr, base, fresh);
+    };
+    if (cnt > 0 && c->isothermal) P.multi ? go(k_rates<false, true>) : go(k_rates<false, false>);
+    if (cnt > 0 && !c->isothermal) P.multi ? go(k_rates<true, true>) : go(k_rates<true, false>);
+    if (slabs) HIPCHK(c, hipEventRecord(c->ev_slab[piece], st));
+  }
+  if (pieces > 1) {
+    HIPCHK(c, hipEventRecord(c->ev_join, c->stream3));
+    HIPCHK(c, hipStreamWaitEvent(c->stream2, c->ev_join, 0));
+  }
+  HIPCHK(c, hipGetLastError());
+  c->tm.rates_launches++;
+  if (c->timing) HIPCHK(c, hipEventRecord(B.ev[3], c->stream2));
+  return 0;
+}
+
+// The losses that are kept but decided nothing (rounds that were a source's last for geometric reasons), one group of sources
+// per such round (the same for every source of a mesh, so one group).  Isothermal: the rates launch has left their terms in
+// the column blocks; they are added up behind it, on its stream, and the sums go to the host to be resolved later
+// (resolve_tails).  Heating: boundary_loss evaluates them now.  The batch's losses and sub-box counts join c->tails.
+static int queue_kept_losses(const PassCtx &P, Batch &B) {
+  c2r_ctx *c = P.c;
+  const int set = B.set;
+  c2r_ctx::BatchTail bt;
+  bt.set = set;
+  bt.slot.assign((size_t)B.nb, -1);
+  for (const SrcRun &r : B.run) {
+    bt.loss.push_back(r.loss);
+    bt.nbox.push_back(r.nbox);
+  }
+  int nslot = 0;
+  for (;;) {
+    int fr = -1;
+    for (int b = 0; b < B.nb && fr < 0; b++)
+      if (B.run[b].final_loss_due) fr = B.run[b].nbox;
+    if (fr < 0) break;
+    int *fl = c->h_list[set] + B.list_used;
+    int nf = 0;
+    for (int b = 0; b < B.nb; b++)
+      if (B.run[b].final_loss_due && B.run[b].nbox == fr) {
+        fl[nf++] = b;
+        B.run[b].final_loss_due = false;
+      }
+    const Box fb = round_box(P.reach, fr);
+    const int f_lo = fr > 1 ? box_smax(round_box(P.reach, fr - 1)) + 1 : 0, f_hi = box_smax(fb);
+    if (c->isothermal) {
+      HIPCHK(c, hipMemcpyAsync(c->d_list[set] + B.list_used, fl, sizeof(int) * nf, hipMemcpyHostToDevice, c->stream2));
+      const int nblk = c->block_base[f_hi + 1] - c->block_base[f_lo];
+      const size_t need = (size_t)nblk * (size_t)nf;
+      if (c->final_partial_cap[set] < need) {
+        HIPCHK(c, hipStreamSynchronize(c->stream2));
+        if (ensure_pair<double>(c, &c->d_final_partial[set], (double **)nullptr, &c->final_partial_cap[set], need)) return 1;
+      }
+      const int first_block = blocks_before_surface(c, fb, f_lo, f_hi);
+      if (first_block > 0) HIPCHK(c, zero_device(c->d_final_partial[set], sizeof(double) * need, c->stream2));
+      hipLaunchKernelGGL(k_loss_stored, dim3(nblk - first_block, nf), dim3(BLOCK), 0, c->stream2, c->g, c->d_src[set],
+                         c->d_list[set] + B.list_used, f_lo, f_hi, fb, c->d_block_base, c->d_final_partial[set], nblk, first_block);
+      hipLaunchKernelGGL(k_loss_finish, dim3(nf), dim3(BLOCK), 0, c->stream2, c->d_final_partial[set], nblk, nblk,
+                         c->d_final_acc[set] + nslot);
+      HIPCHK(c, hipGetLastError());
+      for (int j = 0; j < nf; j++) bt.slot[(size_t)fl[j]] = nslot + j;
+      nslot += nf;
+    } else {
+      HIPCHK(c, hipMemcpyAsync(c->d_list[set] + B.list_used, fl, sizeof(int) * nf, hipMemcpyHostToDevice, c->stream));
+      if (boundary_loss(c, set, B.list_used, nf, f_lo, f_hi, fb, P.sc, P.ss, P.multi)) return 1;
+      for (int j = 0; j < nf; j++) bt.loss[(size_t)fl[j]] = c->h_loss[j];
+    }
+    B.list_used += (size_t)nf;
+  }
+  if (nslot > 0) HIPCHK(c, hipMemcpyAsync(c->h_final[set], c->d_final_acc[set], sizeof(double) * nslot, hipMemcpyDeviceToHost, c->stream2));
+  bt.resolved = nslot == 0;
+  c->tails.push_back(std::move(bt));
+  return 0;
 }
 
 // nslab > 0: the caller wants to consume the rate grids slab by slab (z ranges) while later slabs are
@@ -2844,13 +3434,10 @@ static int pass_list(c2r_ctx *c, const std::vector<int> &mine, int nslab = 0) {
     explicit InPass(c2r_ctx *c_) : c(c_) { c->in_pass = true; }
     ~InPass() { c->in_pass = false; }
   } in_pass_guard(c);
-  const Grid g = c->g;
-  const size_t nc = g.ncell;
-  const StepScalars sc = scalars(c);
-  bool multi = false;
-  const SedSet ss = sedset(c, &multi);
-  const int mesh[3] = {g.n1, g.n2, g.n3};
-  const Reach reach = mesh_reach(g);
+  static const bool generic_sweep = getenv("C2R_SWEEP_GENERIC") && atoi(getenv("C2R_SWEEP_GENERIC")) > 0;
+  static const bool arena_log = getenv("C2R_ARENA_LOG") != nullptr;
+  PassCtx P{c, scalars(c), SedSet(), false, mesh_reach(c->g), generic_sweep, arena_log};
+  P.ss = sedset(c, &P.multi);
   c->tm.sweep_ms = c->tm.rates_ms = 0.0;
   c->tm.sweep_launches = c->tm.rates_launches = 0;
   c->tm.cells_swept = 0;
@@ -2859,641 +3446,67 @@ static int pass_list(c2r_ctx *c, const std::vector<int> &mine, int nslab = 0) {
   // this list; entries still here belong to a pass that ended in an error and must not be added to this one
   c->tails.clear();
   if (c->prev_nbox.size() != (size_t)c->nsrc) c->prev_nbox.assign((size_t)c->nsrc, 0);
-  std::vector<hipEvent_t> tev; // per batch: sweep start, sweep end, rates start, rates end
   // a rank without sources writes nothing: a pending zeroing of the rate grids has to happen for real
   if (mine.empty() && flush_rates_zero(c)) return 1;
   // everything queued earlier on the main stream (state upload, zeroing of the rates) must be
   // visible to the rates stream
   HIPCHK(c, hipEventRecord(c->ev_sweep_done[0], c->stream));
   HIPCHK(c, hipStreamWaitEvent(c->stream2, c->ev_sweep_done[0], 0));
-
-  {
-    // the products neufrac * ndens the sweep reads (k_pack_state; xh_av, xhe_av change every iteration), in mesh
-    // order and in (j,i,k) order: made on the third stream while the inner shells, which do without them, are
-    // already on their way
-    HIPCHK(c, hipStreamWaitEvent(c->stream3, c->ev_sweep_done[0], 0));
-    if (c->packed_valid && c->transposed_valid) {
-      // nothing to make: the global pass transposed its own products (ev_transposed is on record since then)
-    } else if (c->packed_valid)
-      hipLaunchKernelGGL(k_transpose_packed, dim3((g.n1 + 31) / 32, (g.n2 + 31) / 32, 3 * g.n3), dim3(BLOCK), 0, c->stream3, g,
-                         c->d_stateT, c->d_stateT + 3 * nc);
-    else
-      hipLaunchKernelGGL(k_pack_state, dim3((g.n1 + 31) / 32, (g.n2 + 31) / 32, g.n3), dim3(BLOCK), 0, c->stream3, g, c->d_ndens, c->d_xh_av,
-                         c->d_xhe_av, c->d_stateT, c->d_stateT + 3 * nc);
-    HIPCHK(c, hipGetLastError());
-    if (!(c->packed_valid && c->transposed_valid)) HIPCHK(c, hipEventRecord(c->ev_transposed, c->stream3));
-  }
-  bool transposed_seen = false; // the sweep stream has waited for ev_transposed
-  const bool packed_early = c->packed_valid; // the mesh-ordered products need not wait for anything
-  // slabs: tile layers (4 planes each) [slab_layer[s], slab_layer[s+1])
-  const int nt3_all = (g.n3 + 3) / 4;
-  const int ns_eff = nslab > 0 ? std::min(nslab, nt3_all) : 0;
+  if (queue_state_products(c)) return 1;
+  P.packed_early = c->packed_valid;
+  // slabs: tile layers (4 planes each) [slab_k[s] / 4, slab_k[s + 1] / 4), and an event for each
+  const int nt3_all = (c->g.n3 + 3) / 4;
+  P.nslab = nslab > 0 ? std::min(nslab, nt3_all) : 0;
   c->slab_k.assign(1, 0);
-  for (int sidx = 1; sidx <= ns_eff; sidx++) c->slab_k.push_back(std::min(g.n3, 4 * (int)((long long)nt3_all * sidx / ns_eff)));
-  while (c->ev_slab.size() < (size_t)ns_eff) {
+  for (int sidx = 1; sidx <= P.nslab; sidx++) c->slab_k.push_back(std::min(c->g.n3, 4 * (int)((long long)nt3_all * sidx / P.nslab)));
+  while (c->ev_slab.size() < (size_t)P.nslab) {
     hipEvent_t e;
     HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
     c->ev_slab.push_back(e);
   }
-  // column blocks: what a source needed in the last pass plus one round, or four rounds when nothing is known;
-  // never less than one round, never more than the mesh
   if (c->prev_grow.size() != (size_t)c->nsrc) c->prev_grow.assign((size_t)c->nsrc, 0);
-  auto predicted_cap = [&](int ns) { return predicted_shells(c, ns); };
-  int bi = 0;
-  int batch_limit = std::min(c->batch, BATCH_MAX);
-  for (size_t b0 = 0; b0 < mine.size(); bi++) {
-    int nb = (int)std::min<size_t>((size_t)batch_limit, mine.size() - b0);
-    const int set = bi & 1;
+  const int batch_limit = std::min(c->batch, BATCH_MAX);
+  for (size_t b0 = 0, bi = 0; b0 < mine.size(); bi++) {
+    Batch B;
+    B.set = (int)(bi & 1);
+    B.b0 = b0;
+    B.nb = (int)std::min<size_t>((size_t)batch_limit, mine.size() - b0);
     // this set's scratch may still be read by the rates launch of two batches ago, and its pinned lists may
     // still feed copies queued then
-    if (c->set_busy[set]) {
-      HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_rates_done[set], 0));
-      HIPCHK(c, hipEventSynchronize(c->ev_rates_done[set]));
-      resolve_tails(c, set); // h_final[set] is about to be written again
+    if (c->set_busy[B.set]) {
+      HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_rates_done[B.set], 0));
+      HIPCHK(c, hipEventSynchronize(c->ev_rates_done[B.set]));
+      resolve_tails(c, B.set); // h_final[set] is about to be written again
     }
-    std::vector<SrcRun> run;
-    std::vector<int> known0((size_t)nb); // what the last pass knew about the batch's sources (a batch that starts over raises prev_nbox)
-    for (int b = 0; b < nb; b++) known0[(size_t)b] = c->prev_nbox[(size_t)mine[b0 + b] - 1];
-    int restarts = 0;
-  restart_batch:
-    run.assign((size_t)nb, SrcRun());
-    for (int b = 0; b < nb; b++) run[(size_t)b].known_before = known0[(size_t)b];
-    {
-      // Blocks of this batch.  Segments are kept from batch to batch and pass to pass (allocation is slow), so what
-      // the set holds may be cut for other block sizes than this batch needs (many small segments of a pass with
-      // small boxes).  When the blocks do not fit although less than half of what the set holds is in use, its
-      // segments are given back and made anew in one piece; otherwise the batch is what did fit.
-      for (bool released = false;;) {
-        c->seg_cur[set] = 0;
-        c->seg_used[set] = 0;
-        c->vacated[set].clear();
-        SrcDev *hs = c->h_src[set];
-        size_t total = 0;
-        for (int b = 0; b < nb; b++) total += block_doubles(predicted_cap(mine[b0 + b]));
-        int placed = 0;
-        size_t placed_doubles = 0;
-        for (; placed < nb; placed++) {
-          SrcRun &r = run[placed];
-          r.ns = mine[b0 + placed];
-          r.cap = predicted_cap(r.ns);
-          const size_t w = (size_t)(2 * r.cap + 1);
-          hs[placed].cz = w * w * w;
-          hs[placed].cols = arena_alloc(c, set, 6 * hs[placed].cz, total);
-          if (!hs[placed].cols) break;
-          total -= 6 * hs[placed].cz;
-          placed_doubles += 6 * hs[placed].cz;
-        }
-        if (placed == nb) break;
-        size_t have = 0;
-        for (const c2r_ctx::Segment &sg : c->segs[set]) have += sg.n;
-        if (!released && have > 0 && placed_doubles < have / 2) {
-          released = true;
-          arena_release(c, set);
-          continue;
-        }
-        if (placed == 0) return fail(c, "column scratch: one source of this mesh does not fit in device memory");
-        // A batch cut to exactly what fits has no room for a source that outgrows its block (the deeper block is needed
-        // while the old one is still in use) and starts over at the first such move -- at 512^3, where a block at the mesh
-        // limit is 6.4 GB and a set holds some twenty, 615 times in six passes (round 5).  So the cut leaves room for a third
-        // of the sources that can still grow to move once; sources at the mesh limit need none.
-        int keep = placed;
-        for (;;) {
-          size_t used = 0, reserve = 0;
-          for (int b = 0; b < keep; b++) {
-            used += 6 * hs[b].cz;
-            if (run[b].cap < g.smax) reserve += block_doubles(std::min(g.smax, 2 * run[b].cap));
-          }
-          if (keep <= 1 || used + reserve / 3 <= placed_doubles) break;
-          keep--;
-        }
-        if (getenv("C2R_ARENA_LOG")) fprintf(stderr, "c2ray_hip: column scratch, set %d: batch of %d cut to %d sources (%d fit)\n", set, nb, keep, placed);
-        nb = keep; // the same calls place the same blocks again
-        run.resize((size_t)nb);
-      }
-      SrcDev *hs = c->h_src[set];
-      for (int b = 0; b < nb; b++) {
-        SrcRun &r = run[b];
-        r.total_flux = c->normflux[r.ns - 1] * c->s_star; // evolve_source.F90:122-128
-        for (int k = 0; k < 2; k++)
-          if (multi && !c->normflux_sed[k].empty())
-            r.total_flux = r.total_flux + c->normflux_sed[k][r.ns - 1] * c->s_star_sed[k];
-        r.loss = r.total_flux;
-        SrcDev &S = hs[b];
-        const int *p = &c->srcpos[3 * (size_t)(r.ns - 1)];
-        S.i0 = p[0]; S.j0 = p[1]; S.k0 = p[2];
-        for (int d = 0; d < 3; d++) { S.lo[d] = 0; S.hi[d] = 0; }
-        S.nflux = c->normflux[r.ns - 1];
-        for (int k = 0; k < 2; k++) S.nflux_sed[k] = c->normflux_sed[k].empty() ? 0.0 : c->normflux_sed[k][r.ns - 1];
-      }
-      HIPCHK(c, hipMemcpyAsync(c->d_src[set], hs, sizeof(SrcDev) * nb, hipMemcpyHostToDevice, c->stream));
+    for (int b = 0; b < B.nb; b++) B.known0.push_back(c->prev_nbox[(size_t)mine[b0 + b] - 1]);
+    for (hipEvent_t &e : B.ev)
+      if (c->timing && pool_event(c, &e)) return 1;
+    for (;;) {
+      if (place_batch(P, mine, B)) return 1;
+      const int r = sweep_batch(P, B);
+      if (r == 0) break;
+      if (r != START_OVER) return 1;
     }
-    // coldensh_out = 0 for every new source (evolve_source.F90:94-95) serves two purposes in the
-    // reference: the "already done" marker (replaced here by the shell order: every cell is visited
-    // once) and finite values for corners whose interpolation weight is exactly 0.  The arena is
-    // zeroed once at allocation and only ever holds finite columns afterwards, so 0*w stays 0.
-    hipEvent_t e_s0 = nullptr, e_s1 = nullptr, e_r0 = nullptr, e_r1 = nullptr;
-    if (c->timing) {
-      if (pool_event(c, &e_s0) || pool_event(c, &e_s1) || pool_event(c, &e_r0) || pool_event(c, &e_r1)) return 1;
-    }
-    bool sweep_started = false; // e_s0 goes in front of the first shell launch, behind the uploads of records and lists
-    size_t list_used = 0;
-    long long batch_cells = 0;
-    int *hl = c->h_list[set];
-    // The sub-box loop (evolve_source.F90:136-144).  After the shells of round r the loss through the box surface
-    // decides who sweeps round r+1; a quick lower bound of it (k_loss_probe_rounds) nearly always does.  When every active
-    // source went beyond round r in the previous pass (prev_nbox), round r+1 is launched at once for all of them, on
-    // trust, and the probe of round r is not even queued yet: the probes of all such rounds go out together, on
-    // their own stream, when a decision is really needed -- before a round that some source did not reach last time,
-    // or before the round that is everybody's last for geometric reasons -- so that the sweep stream carries shells
-    // and nothing else (a probe per round cost it an event, and 13-24 us of gap at each of the 12 round boundaries
-    // of a 256^3 sweep).  A source that turns out to have stopped at r keeps round r as its last -- its shells
-    // of later rounds are never looked at (the rates launch only sees the final box), so a wrong guess costs time,
-    // never a bit.
-    std::vector<RoundRec> recs;       // the rounds swept so far
-    size_t settled = 0, launched = 0; // recs[0, settled): while-test applied; recs[settled, launched): probes in flight
-    {
-      const size_t acc_need = (size_t)nb * (size_t)(g.smax / SUBBOXSIZE + 3);
-      if (c->probe_acc_cap < acc_need) {
-        HIPCHK(c, hipStreamSynchronize(c->stream_probe));
-        if (ensure_pair<double>(c, &c->d_probe_acc, &c->h_probe, &c->probe_acc_cap, acc_need)) return 1;
-      }
-    }
-    auto launch = [&]() -> int {
-      if (launch_probes(c, set, recs, launched, recs.size(), sc, ss, multi)) return 1;
-      launched = recs.size();
-      return 0;
-    };
-    // read the probes of all rounds not yet decided, replace what a probe leaves undecided by the full sum, apply
-    // the while-test round by round: sources that stop get active = false and that round as their last
-    auto settle = [&]() -> int {
-      if (settled == recs.size()) return 0;
-      if (launch()) return 1;
-      HIPCHK(c, hipEventSynchronize(c->ev_probe));
-      for (; settled < recs.size(); settled++) {
-        const RoundRec &P = recs[settled];
-        const double *probe = c->h_probe + P.acc_off;
-        const int *lst = hl + P.off;
-        std::vector<int> undecided;
-        for (int a = 0; a < P.nact; a++) {
-          SrcRun &r = run[lst[a]];
-          if (!r.active) continue; // stopped at an earlier round: swept this one on trust, to no effect
-          r.loss = probe[a];
-          if (!(r.loss > 2.0 * (C2R_F(1e-10) * r.total_flux))) undecided.push_back(lst[a]);
-        }
-        if (!undecided.empty()) {
-          int *ul = hl + list_used;
-          std::copy(undecided.begin(), undecided.end(), ul);
-          HIPCHK(c, hipMemcpyAsync(c->d_list[set] + list_used, ul, sizeof(int) * undecided.size(), hipMemcpyHostToDevice, c->stream));
-          if (boundary_loss(c, set, list_used, (int)undecided.size(), P.s_lo, P.s_hi, P.box, 1, sc, ss, multi)) return 1;
-          list_used += undecided.size();
-          for (size_t j = 0; j < undecided.size(); j++) run[undecided[j]].loss = c->h_loss[j];
-        }
-        for (int a = 0; a < P.nact; a++) {
-          SrcRun &r = run[lst[a]];
-          if (!r.active) continue;
-          if (!(r.loss > C2R_F(1e-10) * r.total_flux)) { // evolve_source.F90:136: the box does not grow any more
-            r.active = false;
-            r.nbox = P.round;
-          }
-        }
-      }
-      return 0;
-    };
-    // every source still active reached at least round `round` in the previous pass
-    auto all_reached = [&](int round) {
-      bool yes = true;
-      for (int b = 0; b < nb && yes; b++)
-        if (run[b].active) yes = c->prev_nbox[(size_t)run[b].ns - 1] >= round;
-      return yes;
-    };
-    size_t cur_off = 0; // the active list of the last round launched
-    int cur_nact = 0;
-    size_t acc_used = 0;
-    for (int round = 1;; round++) {
-      const Box box = round_box(reach, round);
-      const int s_hi = box_smax(box);
-      // may this round start before the losses of the rounds before it are known?
-      const bool ahead = round > 1 && cur_nact > 0 && all_reached(round);
-      if (!ahead && settle()) return 1;
-      // who sweeps this round: the while-test of evolve_source.F90:136-139 (its loss part taken on trust when ahead)
-      int nact = 0;
-      int *act = hl + list_used;
-      int s_lo = 1 << 30;
-      for (int b = 0; b < nb; b++) {
-        SrcRun &r = run[b];
-        if (!r.active) continue;
-        if (!box_can_grow(reach, round_box(reach, r.nbox)) || !(ahead || r.loss > C2R_F(1e-10) * r.total_flux)) {
-          r.active = false;
-          continue;
-        }
-        r.nbox = round;
-        act[nact++] = b;
-        s_lo = std::min(s_lo, r.smax_prev + 1);
-      }
-      if (nact == 0) {
-        if (settle()) return 1;
-        break;
-      }
-      if (s_hi > g.smax) return fail(c, "internal: shell %d beyond smax %d", s_hi, g.smax);
-      // blocks too small for this round move to larger ones (the shells stored so far are a prefix of every array)
-      for (int a = 0; a < nact; a++) {
-        SrcRun &r = run[act[a]];
-        if (r.cap >= s_hi) continue;
-        const int ncap = std::min(g.smax, std::max(s_hi, 2 * r.cap));
-        const size_t nd = block_doubles(ncap);
-        double *ncols = arena_alloc(c, set, nd);
-        if (!ncols) {
-          // No room left on the device in the middle of a sweep.  Nothing of this batch has reached the rate
-          // grids yet, so the batch starts over with what this attempt has taught (sources that have stopped get
-          // the block they needed, those still growing two rounds more than they have come to) and, since even
-          // that did not fit, with fewer sources.
-          HIPCHK(c, hipStreamSynchronize(c->stream));
-          HIPCHK(c, hipStreamSynchronize(c->stream_probe));
-          // (round 5: a source still growing when the room ran out is given the mesh limit, not two rounds more -- at 512^3
-          // the fronts of a whole batch race there together, and "two more" made every batch start over twice)
-          const int limit_rounds = (g.smax + SUBBOXSIZE - 1) / SUBBOXSIZE;
-          for (int b = 0; b < nb; b++) {
-            int &pn = c->prev_nbox[(size_t)run[b].ns - 1];
-            pn = std::max(pn, run[b].active ? limit_rounds : run[b].nbox);
-          }
-          if (nb == 1) return fail(c, "column scratch: one source of this mesh does not fit in device memory");
-          if (getenv("C2R_ARENA_LOG")) fprintf(stderr, "c2ray_hip: column scratch, set %d: no room to grow in round %d, batch of %d starts over\n", set, round, nb);
-          // the first time with the same sources: blocks made for what is known now need no moves, and what a move leaves
-          // behind is most of what filled the set; a batch that runs out of room again is halved
-          if (restarts++ > 0) nb = (nb + 1) / 2;
-          c->arena_stats[4]++;
-          goto restart_batch;
-        }
-        // probes in flight read this source's SrcDev entry: they must be through before the entry changes
-        if (launched > settled) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_probe, 0));
-        SrcDev &S = c->h_src[set][act[a]];
-        const size_t wn = (size_t)(2 * ncap + 1), ncz = wn * wn * wn;
-        const size_t wp = (size_t)(2 * r.smax_prev + 1), have = r.smax_prev >= 0 ? wp * wp * wp : 0;
-        // the shells stored so far are a prefix of each array (or of each array of triples)
-        for (int half = 0; half < 2 && have > 0; half++) {
-          const bool triples = C2R_COLS_AOS == 1 || C2R_COLS_AOS == (half ? 3 : 2);
-          for (int k = 0; k < (triples ? 1 : 3); k++) {
-            const size_t at = (size_t)(3 * half + k);
-            HIPCHK(c, hipMemcpyAsync(ncols + at * ncz, S.cols + at * S.cz, sizeof(double) * (triples ? 3 : 1) * have,
-                                     hipMemcpyDeviceToDevice, c->stream));
-          }
-        }
-        if (S.cz > 0) c->vacated[set].push_back(c2r_ctx::Segment{S.cols, 6 * S.cz}); // free for the batch's later moves
-        S.cols = ncols;
-        S.cz = ncz;
-        r.cap = ncap;
-        c->arena_stats[3]++;
-        HIPCHK(c, hipMemcpyAsync(c->d_src[set] + act[a], &S, sizeof(SrcDev), hipMemcpyHostToDevice, c->stream));
-      }
-      // the same sources as in the last round: the list is on the device already
-      size_t act_off = list_used;
-      if (cur_nact == nact && round > 1 && std::equal(act, act + nact, hl + cur_off)) {
-        act_off = cur_off;
-      } else {
-        HIPCHK(c, hipMemcpyAsync(c->d_list[set] + list_used, act, sizeof(int) * nact, hipMemcpyHostToDevice, c->stream));
-        list_used += (size_t)nact;
-      }
-      cur_off = act_off;
-      cur_nact = nact;
-      // C2R_SWEEP_GENERIC=1 (diagnostic): every shell through the general per-cell code, one launch per shell
-      static const bool generic_sweep = getenv("C2R_SWEEP_GENERIC") && atoi(getenv("C2R_SWEEP_GENERIC")) > 0;
-      SweepArgs SA;
-      SA.g = g; SA.box = box; SA.sc = sc;
-      SA.ndens = c->d_ndens; SA.xh_av = c->d_xh_av; SA.xhe_av = c->d_xhe_av;
-      SA.lls_grid = c->lls_on_grid ? c->d_lls : nullptr;
-      if (c->timing && !sweep_started) {
-        HIPCHK(c, hipEventRecord(e_s0, c->stream));
-        sweep_started = true;
-      }
-      for (int s = s_lo; s <= s_hi; s++) {
-        // (a large batch waits at once: its many small faces would pay more for strided reads than the wait costs)
-        if ((s >= TRANSPOSED_FROM_SHELL || nb > 16) && !transposed_seen) {
-          HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_transposed, 0));
-          transposed_seen = true;
-        }
-        SA.packed = SA.packedT = nullptr;
-        if (transposed_seen || packed_early) SA.packed = c->d_stateT;
-        if (transposed_seen) SA.packedT = c->d_stateT + 3 * nc;
-        const int nblk = c->block_base[s + 1] - c->block_base[s];
-        // from 64 blocks on: a multiple of 8 blocks, one contiguous eighth of the shell per XCD (see the kernel)
-        const int nlaunch = nblk >= 64 ? ((nblk + 7) & ~7) : nblk;
-        if (s >= 2 && s <= SHELL_FAST_MAX && !generic_sweep)
-          hipLaunchKernelGGL(k_sweep_shell_fast, dim3(nlaunch, nact), dim3(BLOCK), 0, c->stream, SA, c->d_src[set],
-                             c->d_list[set] + act_off, c->shell_geom[(size_t)s]);
-        else
-          hipLaunchKernelGGL(k_sweep_shell, dim3(nlaunch, nact), dim3(BLOCK), 0, c->stream, SA, c->d_src[set], c->d_list[set] + act_off, s);
-        c->tm.sweep_launches++;
-      }
-      HIPCHK(c, hipGetLastError());
-      for (int a = 0; a < nact; a++) run[hl[act_off + a]].smax_prev = s_hi;
-      if (!box_can_grow(reach, box)) {
-        // The while-test after this round fails whatever the loss: the round is every active source's last, and
-        // its loss (the one that is kept, evolve_source.F90:233) comes out of the rates launch (SrcDev::loss_lo).
-        // The rounds before it are decided now; their probes were queued before this round's shells.
-        if (settle()) return 1;
-        for (int a = 0; a < nact; a++) {
-          SrcRun &r = run[hl[act_off + a]];
-          if (!r.active) continue; // stopped a round earlier after all
-          r.final_loss_due = true;
-          r.active = false;
-        }
-        break;
-      }
-      // The loss of this round decides whether a source goes on.
-      RoundRec R;
-      R.round = round; R.nact = nact; R.s_lo = s_lo; R.s_hi = s_hi; R.off = act_off; R.acc_off = acc_used; R.box = box;
-      acc_used += (size_t)nact;
-      recs.push_back(R);
-      // Its probe goes out now if the next round needs the answer before it can start (somebody may stop here) or if
-      // the next round is the last for geometric reasons (the probes then run beside its shells, and the answers
-      // are there when the rates launch has to be put together); otherwise it waits for company.
-      const bool next_is_last = !box_can_grow(reach, round_box(reach, round + 1));
-      // C2R_PROBE_EACH_ROUND=1 (diagnostic): queue every round's probe right behind its shells
-      static const bool each_round = getenv("C2R_PROBE_EACH_ROUND") && atoi(getenv("C2R_PROBE_EACH_ROUND")) > 0;
-      if ((each_round || !all_reached(round + 1) || next_is_last) && launch()) return 1;
-    }
-    for (int b = 0; b < nb; b++) batch_cells += run[b].nbox > 0 ? box_cells(round_box(reach, run[b].nbox)) : 0;
-    // final sub-boxes for the rates launch
-    bool any_final = false;
-    // C2R_FINAL_LOSS_KERNEL=1 (diagnostic): evaluate the kept losses of final rounds with k_loss, beside the rates
-    // launch, as rounds 1 and 2 of this library did, instead of taking them from the rates launch
-    static const bool legacy_env = getenv("C2R_FINAL_LOSS_KERNEL") && atoi(getenv("C2R_FINAL_LOSS_KERNEL")) > 0;
-    const bool legacy_final_loss = legacy_env || !c->isothermal; // heating kernels do not keep photo_out (see k_rates)
-    for (int b = 0; b < nb; b++) {
-      SrcDev &S = c->h_src[set][b];
-      const Box fb = round_box(reach, run[b].nbox);
-      for (int d = 0; d < 3; d++) { S.lo[d] = fb.lo[d]; S.hi[d] = fb.hi[d]; }
-      // a source whose while-test failed before the first sub-box (a mesh only two cells deep) traced nothing:
-      // an empty box, so that no cell passes the in-box test
-      if (run[b].nbox == 0) { S.lo[0] = 1; S.hi[0] = 0; }
-      // the kept loss of a round that was the last for geometric reasons comes out of the rates launch: the
-      // surface cells in the shells of that round
-      S.loss_lo = -1;
-      if (run[b].final_loss_due && !legacy_final_loss) {
-        any_final = true;
-        S.loss_lo = run[b].nbox > 1 ? box_smax(round_box(reach, run[b].nbox - 1)) + 1 : 0;
-      }
-      {
-        int &pn = c->prev_nbox[(size_t)run[b].ns - 1];
-        // (first_try_nbox: what was known before this batch -- a batch that started over has raised prev_nbox meanwhile)
-        c->prev_grow[(size_t)run[b].ns - 1] = run[b].known_before > 0 ? std::max(0, run[b].nbox - run[b].known_before) : 0;
-        pn = run[b].nbox;
-      }
-    }
-    if (c->timing) { // the sweep's span: from the first shell launch to the last, record uploads on either side left out
-      if (!sweep_started) HIPCHK(c, hipEventRecord(e_s0, c->stream));
-      HIPCHK(c, hipEventRecord(e_s1, c->stream));
-    }
-    HIPCHK(c, hipMemcpyAsync(c->d_src[set], c->h_src[set], sizeof(SrcDev) * nb, hipMemcpyHostToDevice, c->stream));
-    if (!transposed_seen) {
-      // small boxes only: nobody needed the copies, but whatever follows this sweep (the global pass rewrites the
-      // state) has to come after the kernel that reads it
-      HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_transposed, 0));
-      transposed_seen = true;
-    }
-    HIPCHK(c, hipEventRecord(c->ev_sweep_done[set], c->stream));
-
-    // rates of the whole batch, in source order, on the second stream
-    HIPCHK(c, hipStreamWaitEvent(c->stream2, c->ev_sweep_done[set], 0));
-    if (c->timing) HIPCHK(c, hipEventRecord(e_r0, c->stream2));
-    // tiles (8 x 8 x 4 cells) that intersect the final sub-box of some source of the batch, and per tile the
-    // sources that do
-    const int nt1 = (g.n1 + 7) / 8, nt2 = (g.n2 + 7) / 8, nt3 = (g.n3 + 3) / 4;
-    int nblk = nt1 * nt2 * nt3;
-    const int *d_tiles = nullptr, *d_tptr = nullptr, *d_tsrc = nullptr;
-    {
-      bool full = false;
-      for (int b = 0; b < nb && !full; b++) {
-        const Box fb = round_box(reach, run[b].nbox);
-        full = run[b].nbox > 0;
-        for (int d = 0; d < 3; d++) full = full && (fb.hi[d] - fb.lo[d] + 1 >= mesh[d]);
-      }
-      // few sources one of which fills the mesh: every cell simply walks all of them
-      if (!(full && nb <= 16)) {
-        std::vector<int> &cnt = c->tile_count;
-        cnt.assign((size_t)nblk, 0);
-        std::vector<int> cov[3];
-        const int tsz[3] = {8, 8, 4}, ntd[3] = {nt1, nt2, nt3};
-        auto covered = [&](int b) {
-          const Box fb = round_box(reach, run[b].nbox);
-          const int *p = &c->srcpos[3 * (size_t)(run[b].ns - 1)];
-          for (int d = 0; d < 3; d++) {
-            cov[d].clear();
-            int last = -1;
-            std::vector<unsigned char> seen((size_t)ntd[d], 0);
-            for (int o = fb.lo[d]; o <= fb.hi[d]; o++) {
-              int x = (p[d] - 1 + o) % mesh[d];
-              if (x < 0) x += mesh[d];
-              const int t = x / tsz[d];
-              if (t != last && !seen[t]) { seen[t] = 1; cov[d].push_back(t); }
-              last = t;
-            }
-          }
-        };
-        size_t total = 0;
-        for (int b = 0; b < nb; b++) {
-          if (run[b].nbox == 0) continue;
-          covered(b);
-          for (int tk : cov[2])
-            for (int tj_ : cov[1]) {
-              int *row = &cnt[((size_t)tk * nt2 + tj_) * nt1];
-              for (int ti_ : cov[0]) row[ti_]++;
-            }
-          total += cov[0].size() * cov[1].size() * cov[2].size();
-        }
-        if (ensure_pair<int>(c, &c->d_tsrc[set], &c->h_tsrc[set], &c->tsrc_cap[set], total + 1)) return 1;
-        int *list = c->h_tiles[set], *tp = c->h_tptr[set], *tsrc = c->h_tsrc[set];
-        int ntl = 0;
-        size_t acc = 0;
-        for (int t = 0; t < nblk; t++) {
-          if (!cnt[t]) { cnt[t] = -1; continue; }
-          list[ntl] = t;
-          tp[ntl] = (int)acc;
-          acc += (size_t)cnt[t];
-          cnt[t] = ntl++; // from count to position in the list
-        }
-        if (ntl == 0) { list[0] = 0; tp[0] = 0; ntl = 1; }
-        tp[ntl] = (int)acc;
-        std::vector<int> fill(tp, tp + ntl);
-        for (int b = 0; b < nb; b++) { // ascending b: every tile's sources end up in source order
-          if (run[b].nbox == 0) continue;
-          covered(b);
-          for (int tk : cov[2])
-            for (int tj_ : cov[1]) {
-              const int *row = &cnt[((size_t)tk * nt2 + tj_) * nt1];
-              for (int ti_ : cov[0]) tsrc[fill[row[ti_]]++] = b;
-            }
-        }
-        HIPCHK(c, hipMemcpyAsync(c->d_tiles[set], list, sizeof(int) * (size_t)ntl, hipMemcpyHostToDevice, c->stream2));
-        HIPCHK(c, hipMemcpyAsync(c->d_tptr[set], tp, sizeof(int) * (size_t)(ntl + 1), hipMemcpyHostToDevice, c->stream2));
-        if (acc > 0) HIPCHK(c, hipMemcpyAsync(c->d_tsrc[set], tsrc, sizeof(int) * acc, hipMemcpyHostToDevice, c->stream2));
-        d_tiles = c->d_tiles[set];
-        d_tptr = c->d_tptr[set];
-        d_tsrc = c->d_tsrc[set];
-        nblk = ntl;
-      }
-    }
-    // a pending set_rates_to_zero: this launch writes the grids if it covers every cell, else they are zeroed now
-    // (on the rates stream, which this batch's launches follow)
-    int fresh = 0;
-    if (c->rates_zero_pending) {
-      if (!d_tiles) {
-        fresh = 1;
-        c->rates_zero_pending = false;
-        if (c->isothermal && c->phiheat_dirty) { // phiheat of an earlier heating step: not written by this launch
-          HIPCHK(c, zero_device(c->d_rates + 3 * nc, sizeof(double) * nc, c->stream2));
-          c->phiheat_dirty = false;
-        }
-      } else {
-        c->rates_zero_pending = false;
-        c->phiheat_dirty = false;
-        // (the four grids only: the tail of the buffer is written at the end of this pass, on the other stream)
-        HIPCHK(c, zero_device(c->d_rates, sizeof(double) * 4 * nc, c->stream2));
-      }
-    }
-    if (!c->isothermal) c->phiheat_dirty = true;
-#define C2R_LAUNCH_RATES(H, M)                                                                               \
-  hipLaunchKernelGGL((k_rates<H, M>), dim3(cnt_), dim3(BLOCK), 0, st_, g, c->d_src[set], nb, sc, c->d_ndens, c->d_xh_av, \
-                     c->d_xhe_av, c->d_bands, ss, c->d_rates, d_tiles, d_tptr, d_tsrc, base_, fresh)
-    const bool last_batch = b0 + nb >= mine.size();
-    const int pieces = (last_batch && ns_eff > 0) ? ns_eff : 1;
-    const int per_layer = nt1 * nt2;
-    // slabs alternate between two streams so that the thin tail of one launch overlaps the start of the
-    // next; the third stream is forked from (and joined back into) the rates stream, which carries the
-    // dependencies on the sweep, on earlier batches and on the tile-list copy
-    if (pieces > 1) {
-      HIPCHK(c, hipEventRecord(c->ev_fork, c->stream2));
-      HIPCHK(c, hipStreamWaitEvent(c->stream3, c->ev_fork, 0));
-    }
-    for (int piece = 0; piece < pieces; piece++) {
-      hipStream_t st_ = (pieces > 1 && (piece & 1)) ? c->stream3 : c->stream2;
-      // tiles of the layers [l0, l1): a contiguous range of tile ids, hence of the (sorted) list too
-      const int l0 = pieces == 1 ? 0 : c->slab_k[piece] / 4;
-      const int l1 = pieces == 1 ? nt3 : (c->slab_k[piece + 1] + 3) / 4;
-      int base_, cnt_;
-      if (d_tiles) {
-        const int *list = c->h_tiles[set];
-        base_ = (int)(std::lower_bound(list, list + nblk, l0 * per_layer) - list);
-        cnt_ = (int)(std::lower_bound(list, list + nblk, l1 * per_layer) - list) - base_;
-      } else {
-        base_ = l0 * per_layer;
-        cnt_ = (l1 - l0) * per_layer;
-      }
-      if (cnt_ > 0) {
-        if (c->isothermal) {
-          if (multi) C2R_LAUNCH_RATES(false, true); else C2R_LAUNCH_RATES(false, false);
-        } else {
-          if (multi) C2R_LAUNCH_RATES(true, true); else C2R_LAUNCH_RATES(true, false);
-        }
-      }
-      if (last_batch && ns_eff > 0) HIPCHK(c, hipEventRecord(c->ev_slab[piece], st_));
-    }
-    if (pieces > 1) {
-      HIPCHK(c, hipEventRecord(c->ev_join, c->stream3));
-      HIPCHK(c, hipStreamWaitEvent(c->stream2, c->ev_join, 0));
-    }
-#undef C2R_LAUNCH_RATES
-    HIPCHK(c, hipGetLastError());
-    c->tm.rates_launches++;
-    if (c->timing) {
-      HIPCHK(c, hipEventRecord(e_r1, c->stream2));
-      tev.push_back(e_s0); tev.push_back(e_s1); tev.push_back(e_r0); tev.push_back(e_r1);
-    }
-    // The losses that are kept but decided nothing (rounds that were a source's last for geometric reasons): the
-    // rates launch has left their terms in the column blocks; add them up behind it, on its stream, one launch per
-    // final round (the same for every source of a mesh, so one launch), and send the sums to the host.
-    c2r_ctx::BatchTail bt;
-    bt.set = set;
-    bt.loss.resize((size_t)nb);
-    bt.slot.assign((size_t)nb, -1);
-    bt.nbox.resize((size_t)nb);
-    for (int b = 0; b < nb; b++) {
-      bt.loss[(size_t)b] = run[b].loss;
-      bt.nbox[(size_t)b] = run[b].nbox;
-    }
-    if (any_final) {
-      int nslot = 0;
-      for (;;) {
-        int fr = -1;
-        for (int b = 0; b < nb; b++)
-          if (run[b].final_loss_due) { fr = run[b].nbox; break; }
-        if (fr < 0) break;
-        int *fl = hl + list_used;
-        int nf = 0;
-        for (int b = 0; b < nb; b++)
-          if (run[b].final_loss_due && run[b].nbox == fr) {
-            bt.slot[(size_t)b] = nslot + nf;
-            fl[nf++] = b;
-            run[b].final_loss_due = false;
-          }
-        HIPCHK(c, hipMemcpyAsync(c->d_list[set] + list_used, fl, sizeof(int) * nf, hipMemcpyHostToDevice, c->stream2));
-        const Box fb = round_box(reach, fr);
-        const int f_lo = fr > 1 ? box_smax(round_box(reach, fr - 1)) + 1 : 0, f_hi = box_smax(fb);
-        const int nblk_l = c->block_base[f_hi + 1] - c->block_base[f_lo];
-        const size_t need = (size_t)nblk_l * (size_t)nf;
-        if (c->final_partial_cap[set] < need) {
-          HIPCHK(c, hipStreamSynchronize(c->stream2));
-          if (ensure_pair<double>(c, &c->d_final_partial[set], (double **)nullptr, &c->final_partial_cap[set], need)) return 1;
-        }
-        // a surface cell has one coordinate on a face of the box, so its shell is at least the nearest face's
-        // distance: the shells before that hold none, their blocks are not launched and their partial sums are zero
-        int s_first = 1 << 30;
-        for (int d = 0; d < 3; d++) s_first = std::min(s_first, std::min(std::abs(fb.lo[d]), std::abs(fb.hi[d])));
-        s_first = std::min(std::max(s_first, f_lo), f_hi);
-        const int first_block = c->block_base[s_first] - c->block_base[f_lo];
-        if (first_block > 0) HIPCHK(c, zero_device(c->d_final_partial[set], sizeof(double) * need, c->stream2));
-        hipLaunchKernelGGL(k_loss_stored, dim3(nblk_l - first_block, nf), dim3(BLOCK), 0, c->stream2, c->g, c->d_src[set],
-                           c->d_list[set] + list_used, f_lo, f_hi, fb, c->d_block_base, c->d_final_partial[set], nblk_l, first_block);
-        hipLaunchKernelGGL(k_loss_finish, dim3(nf), dim3(BLOCK), 0, c->stream2, c->d_final_partial[set], nblk_l, nblk_l,
-                           c->d_final_acc[set] + nslot);
-        HIPCHK(c, hipGetLastError());
-        list_used += (size_t)nf;
-        nslot += nf;
-      }
-      HIPCHK(c, hipMemcpyAsync(c->h_final[set], c->d_final_acc[set], sizeof(double) * nslot, hipMemcpyDeviceToHost, c->stream2));
-    } else {
-      if (legacy_final_loss)
-        for (;;) {
-          int fr = -1;
-          for (int b = 0; b < nb; b++)
-            if (run[b].final_loss_due) { fr = run[b].nbox; break; }
-          if (fr < 0) break;
-          int *fl = hl + list_used;
-          int nf = 0;
-          for (int b = 0; b < nb; b++)
-            if (run[b].final_loss_due && run[b].nbox == fr) fl[nf++] = b;
-          HIPCHK(c, hipMemcpyAsync(c->d_list[set] + list_used, fl, sizeof(int) * nf, hipMemcpyHostToDevice, c->stream));
-          const Box fb = round_box(reach, fr);
-          const int f_lo = fr > 1 ? box_smax(round_box(reach, fr - 1)) + 1 : 0;
-          if (boundary_loss(c, set, list_used, nf, f_lo, box_smax(fb), fb, 1, sc, ss, multi)) return 1;
-          for (int j = 0; j < nf; j++) {
-            bt.loss[(size_t)fl[j]] = c->h_loss[j];
-            run[fl[j]].final_loss_due = false;
-          }
-          list_used += (size_t)nf;
-        }
-      bt.resolved = true;
-    }
-    c->tails.push_back(std::move(bt));
-    HIPCHK(c, hipEventRecord(c->ev_rates_done[set], c->stream2));
-    c->set_busy[set] = true;
-    c->tm.cells_swept += batch_cells;
-    c->last_src = run[nb - 1].ns;
-    c->last_cols = c->h_src[set][nb - 1].cols;
-    c->last_cz = c->h_src[set][nb - 1].cz;
-    {
-      const SrcDev &S = c->h_src[set][nb - 1];
-      for (int d = 0; d < 3; d++) { c->last_lo[d] = S.lo[d]; c->last_hi[d] = S.hi[d]; }
-    }
-    b0 += (size_t)nb;
+    if (close_boxes(P, B)) return 1;
+    if (build_tile_lists(P, B) || launch_rates(P, B, b0 + B.nb >= mine.size()) || queue_kept_losses(P, B)) return 1;
+    if (c->timing) P.tev.insert(P.tev.end(), B.ev, B.ev + 4);
+    HIPCHK(c, hipEventRecord(c->ev_rates_done[B.set], c->stream2));
+    c->set_busy[B.set] = true;
+    for (const SrcRun &r : B.run) c->tm.cells_swept += r.nbox > 0 ? box_cells(round_box(P.reach, r.nbox)) : 0;
+    const SrcDev &S = c->h_src[B.set][B.nb - 1];
+    c->last_src = B.run[B.nb - 1].ns;
+    c->last_cols = S.cols;
+    c->last_cz = S.cz;
+    for (int d = 0; d < 3; d++) { c->last_lo[d] = S.lo[d]; c->last_hi[d] = S.hi[d]; }
+    b0 += (size_t)B.nb;
   }
-  if (!transposed_seen) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_transposed, 0));
+  if (!P.transposed_seen) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_transposed, 0));
   // a rank without sources of its own still owes the caller its slab events
   if (mine.empty())
-    for (int sidx = 0; sidx < ns_eff; sidx++) HIPCHK(c, hipEventRecord(c->ev_slab[sidx], c->stream2));
-  c->pass_tev = tev;
+    for (int sidx = 0; sidx < P.nslab; sidx++) HIPCHK(c, hipEventRecord(c->ev_slab[sidx], c->stream2));
+  c->pass_tev = P.tev;
   c->pass_open = true;
-  c->pass_slabs = ns_eff;
+  c->pass_slabs = P.nslab;
   if (nslab > 0) return 0;
   return pass_finish(c);
 }
@@ -3607,9 +3620,7 @@ static int launch_chemistry(c2r_ctx *c, hipStream_t st, double dt, size_t first,
   if (count == 0) return 0;
   const Grid g = c->g;
   const StepScalars sc = scalars(c);
-  // C2R_CHEM_LDS=0 (diagnostic): tables from global memory in every tier
-  static const bool lds_tiers = !(getenv("C2R_CHEM_LDS") && atoi(getenv("C2R_CHEM_LDS")) == 0);
-  const bool lds = !c->isothermal && list != nullptr && lds_tiers; // the repacked tiers of a heating pass
+  const bool lds = !c->isothermal && list != nullptr; // the repacked tiers of a heating pass
   const int bs = lds ? CHEM_BLOCK_LDS : C2R_CHEM_BLOCK;
   const int nblk = (int)((count + bs - 1) / bs);
   // a range of whole k-planes on a mesh whose sizes are multiples of 4: waves take cubes (see the kernel)
@@ -3839,12 +3850,8 @@ extern "C" int c2r_global_pass_finish(c2r_ctx *c, int *conv_flag) {
   if (c->timing) HIPCHK(c, hipEventRecord(c->ev[4], c->stream));
   // every cell's products for the next column sweep are up to date if the pieces of this pass covered the mesh
   // (pieces that overlap or leave gaps, a caller's business, leave the flag down: the next pass then packs anew)
-  // C2R_PACK_AT_PASS_START=1 (diagnostic): never rely on the global pass's copy
-  static const bool pack_always = getenv("C2R_PACK_AT_PASS_START") && atoi(getenv("C2R_PACK_AT_PASS_START")) > 0;
-  const bool packed_now = c->chem_cells == c->g.ncell && !pack_always;
-  // C2R_TRANSPOSE_AT_PASS_START=1 (diagnostic): the transposition at the start of the next pass, as before round 3
-  static const bool transpose_late = getenv("C2R_TRANSPOSE_AT_PASS_START") && atoi(getenv("C2R_TRANSPOSE_AT_PASS_START")) > 0;
-  if (packed_now && !transpose_late) {
+  const bool packed_now = c->chem_cells == c->g.ncell;
+  if (packed_now) {
     // ... and their (j,i,k)-ordered copy is made right away, on the third stream, while the host reads this pass's
     // results: at the start of the next pass it would share the device with the sweep's innermost shells (measured: 9-14
     // us each beside it, 5-7 us alone)
@@ -3876,8 +3883,7 @@ extern "C" int c2r_global_pass_finish(c2r_ctx *c, int *conv_flag) {
   }
   if (conv_flag) *conv_flag = *c->h_conv;
   c->last_conv = *c->h_conv;
-  c->packed_valid = packed_now;
-  c->transposed_valid = packed_now && !transpose_late;
+  c->packed_valid = c->transposed_valid = packed_now;
   return 0;
 }
 
