@@ -664,24 +664,6 @@ struct PhotoOut {
 struct Ricotti {
   double y1R[3], y2R[3];
 };
-// The six numbers are used by the heating bands only, a few times per band; a kernel short of registers may keep them
-// somewhere cheaper than twelve vector registers for the whole of its source loop (k_rates: LDS, one column per lane):
-// RicottiParked points at y1R[0] of this lane, component n (y1R[0..2], y2R[0..2]) lies n * stride doubles further on.
-#if defined(__HIP_DEVICE_COMPILE__)
-// LDS, said so in the type: a volatile access through a generic pointer is a flat_load with system scope
-typedef const volatile __attribute__((address_space(3))) double *ParkedPtr;
-#else
-typedef const volatile double *ParkedPtr;
-#endif
-struct RicottiParked {
-  ParkedPtr p;
-  int stride;
-};
-C2R_HD double ric_y1(const Ricotti &r, int i) { return r.y1R[i]; }
-C2R_HD double ric_y2(const Ricotti &r, int i) { return r.y2R[i]; }
-// (volatile: read where it is used -- hoisted out of the band loops the values would be back in registers)
-C2R_HD double ric_y1(const RicottiParked &r, int i) { return r.p[i * r.stride]; }
-C2R_HD double ric_y2(const RicottiParked &r, int i) { return r.p[(3 + i) * r.stride]; }
 C2R_HD Ricotti ricotti_parameters(double i_state) {
   const double CR1[3] = {0.3908, 0.0554, 1.0}, bR1[3] = {0.4092, 0.4614, 0.2663},
                dR1[3] = {1.7592, 1.6660, 1.3163};
@@ -734,7 +716,7 @@ template <int N>
 C2R_HD void div_by_vol(const Recip &R, const double (&a)[N], double (&d)[N]) {
   double q[N];
   bool doubt = !R.ok_big;
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(C2R_DIV_GUARD_F64)
+#if defined(__HIP_DEVICE_COMPILE__)
   // the guard on the high words: for q >= 0, q >= 2^-900 exactly when its high word, read as a signed integer, is >=
   // 0x07B00000; a negative quotient has a negative high word and lands in the doubt branch, whose own test -- the
   // one below, on the magnitudes -- then decides as it always did.  One v_min3_i32 and one compare for up to three
@@ -748,7 +730,7 @@ C2R_HD void div_by_vol(const Recip &R, const double (&a)[N], double (&d)[N]) {
     m = hi < m ? hi : m;
   }
   doubt = doubt || m < 0x07B00000;
-#else
+#else // host: a compare per quotient
 #pragma unroll
   for (int n = 0; n < N; n++) {
     q[n] = a[n] * R.y;
@@ -784,9 +766,9 @@ struct BandShared {
   TauPos pin, pout;
   double sc_HI, sc_HeI, sc_HeII;
 };
-template <bool HEAT, int CLS, class RIC, class BD = BandData>
+template <bool HEAT, int CLS, class BD = BandData>
 C2R_HD void band_sed(const BD &bd, const double *photo_thick, const double *photo_thin, const double *heat_thick,
-                     const double *heat_thin, int b, const CellSrc &c, double NFlux, const BandShared &B, const RIC &ric,
+                     const double *heat_thin, int b, const CellSrc &c, double NFlux, const BandShared &B, const Ricotti &ric,
                      SedSums &o) {
   const double sHI = B.sHI, sHeI = B.sHeI, sHeII = B.sHeII, dtau = B.dtau;
   const bool thick = B.thick, hthick = B.hthick;
@@ -871,9 +853,9 @@ const double fra_sum1 = band_f(bd, b, 0) * h_HI + band_f(bd, b, 1) * h_HeI;
       const double fra_sum2 = band_f(bd, b, 3) * h_HI + band_f(bd, b, 4) * h_HeI;
       const double fra_sum3 = band_f(bd, b, 6) * h_HI + band_f(bd, b, 7) * h_HeI;
       const double fra_sum4 = band_f(bd, b, 9) * h_HI + band_f(bd, b, 10) * h_HeI;
-      o.df_ion_HeI = ric_y1(ric, 1) * fra_sum1 - ric_y2(ric, 1) * fra_sum2;
-      o.df_ion_HI = ric_y1(ric, 0) * fra_sum1 - ric_y2(ric, 0) * fra_sum2;
-      df_heat = df_heat - ric_y1(ric, 2) * fra_sum3 + ric_y2(ric, 2) * fra_sum4;
+      o.df_ion_HeI = ric.y1R[1] * fra_sum1 - ric.y2R[1] * fra_sum2;
+      o.df_ion_HI = ric.y1R[0] * fra_sum1 - ric.y2R[0] * fra_sum2;
+      df_heat = df_heat - ric.y1R[2] * fra_sum3 + ric.y2R[2] * fra_sum4;
     } else {
       const int cH = 3 * (b + 1) - NB2 - NB1 * 2 - 2 - 1;
       double a[3];
@@ -901,9 +883,9 @@ const double fra_sum1 = band_f(bd, b, 0) * h_HI + band_f(bd, b, 1) * h_HeI + ban
       const double fra_sum2 = band_f(bd, b, 3) * h_HI + band_f(bd, b, 4) * h_HeI + band_f(bd, b, 5) * h_HeII;
       const double fra_sum3 = band_f(bd, b, 6) * h_HI + band_f(bd, b, 7) * h_HeI + band_f(bd, b, 8) * h_HeII;
       const double fra_sum4 = band_f(bd, b, 9) * h_HI + band_f(bd, b, 10) * h_HeI + band_f(bd, b, 11) * h_HeII;
-      o.df_ion_HeI = ric_y1(ric, 1) * fra_sum1 - ric_y2(ric, 1) * fra_sum2;
-      o.df_ion_HI = ric_y1(ric, 0) * fra_sum1 - ric_y2(ric, 0) * fra_sum2;
-      df_heat = df_heat - ric_y1(ric, 2) * fra_sum3 + ric_y2(ric, 2) * fra_sum4;
+      o.df_ion_HeI = ric.y1R[1] * fra_sum1 - ric.y2R[1] * fra_sum2;
+      o.df_ion_HI = ric.y1R[0] * fra_sum1 - ric.y2R[0] * fra_sum2;
+      df_heat = df_heat - ric.y1R[2] * fra_sum3 + ric.y2R[2] * fra_sum4;
     }
     o.f_heat = o.f_heat + df_heat;
     o.f_ion_HI = o.f_ion_HI + o.df_ion_HI;
@@ -967,10 +949,10 @@ C2R_HD void band_positions(const LT *logtab, const CellSrc &c, double tau_in, do
 // `look_for_zero`: test whether the band is beyond the last non-zero table entry (band_tau_zero); returns
 // whether it was.  Within a class the optical depth falls from band to band, so once no lane of a wave has
 // found a band dead the caller stops asking (a missed skip costs time, never a bit).
-template <bool HEAT, int CLS, class LT, class RIC, class BD = BandData>
+template <bool HEAT, int CLS, class LT, class BD = BandData>
 C2R_HD bool band_rates(const BD &bd, const double *photo_thick, const double *photo_thin, const double *heat_thick,
                        const double *heat_thin, const LT *logtab, const double *tau_zero, bool look_for_zero, int b,
-                       const CellSrc &c, const RIC &ric, SedSums &o) {
+                       const CellSrc &c, const Ricotti &ric, SedSums &o) {
   BandShared B;
   double tau_in, tau_out;
   band_depths<CLS>(bd, b, c, B, tau_in, tau_out);
@@ -989,11 +971,11 @@ C2R_HD bool band_rates(const BD &bd, const double *photo_thick, const double *ph
 // their band range): optical depths, logs, table positions and species split once, then each SED's look-ups and sums
 // exactly as band_rates makes them -- every sum sees the same operands in the same order.  dead[k]: band_rates' return
 // value for SED k.
-template <bool HEAT, int CLS, class LT, class RIC, class BD = BandData>
+template <bool HEAT, int CLS, class LT, class BD = BandData>
 C2R_HD void band_rates_pair(const BD &bd, const double *const (&photo_thick)[2], const double *const (&photo_thin)[2],
                             const double *const (&heat_thick)[2], const double *const (&heat_thin)[2], const LT *logtab,
                             const double *const (&tau_zero)[2], const bool (&look_for_zero)[2], int b, const CellSrc &c,
-                            const double (&NFlux)[2], const RIC &ric, SedSums (&o)[2], bool (&dead)[2]) {
+                            const double (&NFlux)[2], const Ricotti &ric, SedSums (&o)[2], bool (&dead)[2]) {
   BandShared B;
   double tau_in, tau_out;
   band_depths<CLS>(bd, b, c, B, tau_in, tau_out);
@@ -1020,11 +1002,11 @@ struct SedAcc {
 // heat_lookuptable (:470-779), scale_int2/3 (:787-823) fused into one pass over the active bands
 // [blo, bhi) (0-based), in three stretches by band class; every sum runs in band order as in the reference.
 // HEAT selects the non-isothermal path.  `logtab`: see tau_table_position.
-template <bool HEAT, class LT, class RIC, class BD = BandData>
+template <bool HEAT, class LT, class BD = BandData>
 C2R_HD void sed_rates(const BD &bd, const double *photo_thick, const double *photo_thin,
                       const double *heat_thick, const double *heat_thin, int blo, int bhi, double cin_HI,
                       double cout_HI, double cin_HeI, double cout_HeI, double cin_HeII, double cout_HeII, double vol,
-                      double NFlux, const RIC &ric, SedAcc &out, const LT *logtab, const double *tau_zero,
+                      double NFlux, const Ricotti &ric, SedAcc &out, const LT *logtab, const double *tau_zero,
                       const gm::LogPins *pins = nullptr) {
   out.photo_HI = out.photo_HeI = out.photo_HeII = 0.0;
   out.photo_out = 0.0;
@@ -1075,11 +1057,11 @@ C2R_HD void sed_rates(const BD &bd, const double *photo_thick, const double *pho
 
 // sed_rates for two SEDs with the same band range at once (band_rates_pair): out[k] is bit for bit what
 // sed_rates(tables of k, NFlux[k]) returns
-template <bool HEAT, class LT, class RIC, class BD = BandData>
+template <bool HEAT, class LT, class BD = BandData>
 C2R_HD void sed_rates_pair(const BD &bd, const double *const (&photo_thick)[2], const double *const (&photo_thin)[2],
                            const double *const (&heat_thick)[2], const double *const (&heat_thin)[2], int blo, int bhi,
                            double cin_HI, double cout_HI, double cin_HeI, double cout_HeI, double cin_HeII, double cout_HeII,
-                           double vol, const double (&NFlux)[2], const RIC &ric, SedAcc (&out)[2], const LT *logtab,
+                           double vol, const double (&NFlux)[2], const Ricotti &ric, SedAcc (&out)[2], const LT *logtab,
                            const double *const (&tau_zero)[2], const gm::LogPins *pins = nullptr) {
   CellSrc c;
   c.cin_HI = cin_HI; c.cin_HeI = cin_HeI; c.cin_HeII = cin_HeII;
@@ -1125,11 +1107,11 @@ C2R_HD void sed_rates_pair(const BD &bd, const double *const (&photo_thick)[2], 
 }
 
 // photoion_rates for a source with the black-body SED only
-template <bool HEAT, class LT = double, class RIC = Ricotti, class BD = BandData>
+template <bool HEAT, class LT = double, class BD = BandData>
 C2R_HD void photoion_rates(const BD &bd, const double *photo_thick, const double *photo_thin,
                            const double *heat_thick, const double *heat_thin, double cin_HI, double cout_HI,
                            double cin_HeI, double cout_HeI, double cin_HeII, double cout_HeII, double vol,
-                           double NFlux, const RIC &ric, PhotoOut &o, const LT *logtab = C2R_LOGTAB_DEFAULT,
+                           double NFlux, const Ricotti &ric, PhotoOut &o, const LT *logtab = C2R_LOGTAB_DEFAULT,
                            const gm::LogPins *pins = nullptr) {
   SedAcc a;
   sed_rates<HEAT, LT>(bd, photo_thick, photo_thin, heat_thick, heat_thin, 0, bd.bb_upper, cin_HI, cout_HI, cin_HeI, cout_HeI,
@@ -1158,10 +1140,10 @@ struct SedSet {
   int lo[NSED], hi[NSED]; // 0-based first band, one past the last band; lo == hi: SED absent
 };
 
-template <bool HEAT, class LT = double, class RIC = Ricotti, class BD = BandData>
+template <bool HEAT, class LT = double, class BD = BandData>
 C2R_HD void photoion_rates_multi(const BD &bd, const SedSet &ss, double cin_HI, double cout_HI, double cin_HeI,
                                  double cout_HeI, double cin_HeII, double cout_HeII, double vol, const double *NFlux,
-                                 const RIC &ric, PhotoOut &o, const LT *logtab = C2R_LOGTAB_DEFAULT,
+                                 const Ricotti &ric, PhotoOut &o, const LT *logtab = C2R_LOGTAB_DEFAULT,
                                  const gm::LogPins *pins = nullptr) {
   o.photo_HI = o.photo_HeI = o.photo_HeII = 0.0;
   o.heat = 0.0;
@@ -1177,16 +1159,8 @@ C2R_HD void photoion_rates_multi(const BD &bd, const SedSet &ss, double cin_HI, 
   // Isothermal kernels only (round 4): with heating the pair's second set of running sums costs the rates kernel its
   // fourth wave per SIMD -- measured on one box, 256^3, 128 sources per pass: every source with three SEDs 866 (pair,
   // 2 waves) / 905 (no pair, 2 waves) / 868 ms (no pair, 4 waves); a third of the sources with a power law and a fifth
-  // with a quasar component 378 / 372 / 358 ms.  -DC2R_SED_PAIR_HEAT=1 brings it back, -DC2R_NO_SED_PAIR switches
-  // the pair off everywhere (diagnostic builds).
-#if defined(C2R_NO_SED_PAIR)
-  const bool pair = false;
-#else
-#if !defined(C2R_SED_PAIR_HEAT)
-#define C2R_SED_PAIR_HEAT 0
-#endif
-  const bool pair = (!HEAT || C2R_SED_PAIR_HEAT) && act1 && act2 && ss.lo[1] == ss.lo[2] && ss.hi[1] == ss.hi[2];
-#endif
+  // with a quasar component 378 / 372 / 358 ms.
+  const bool pair = !HEAT && act1 && act2 && ss.lo[1] == ss.lo[2] && ss.hi[1] == ss.hi[2];
   // phi = phi + photo_lookuptable(B) [+ (P)] [+ (Q)] runs along with the loops: every sum still receives BB, PL, QPL in
   // that order.  The heat_lookuptable results are added after ALL the photo terms (:247-271), so f_ion of each SED
   // waits in f_HI* / f_HeI*; o.heat only ever receives f_heat, in SED order as well.

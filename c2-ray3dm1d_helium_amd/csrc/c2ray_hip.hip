@@ -112,57 +112,31 @@ __device__ __forceinline__ double sc_path(int idel, int jdel, int kdel) {
 
 // A pointer that comes out of a record in memory (SrcDev::cols) is a generic pointer to the compiler, which then uses
 // flat loads and stores; the column blocks are device memory.
-#ifdef C2R_FLAT_COLS
-typedef double global_double;
-#else
 typedef __attribute__((address_space(1))) double global_double;
-#endif
 
 // Where the six columns of the cell at shell position p live in a source's block of 6 cz doubles: the three incoming
 // columns of a cell side by side (24 bytes), then all outgoing ones likewise.  The rates kernel, whose 4 x 4 x 4 cubes
 // read rows of four cells, then uses 96 of every 128 bytes it touches instead of 32 (-0.3..0.5 ms per launch at
 // 256^3 x 8); the sweep's stores become three strided ones per triple (+0.05..0.1 ms per pass).
-#ifndef C2R_COLS_AOS
-#define C2R_COLS_AOS 1
-#endif
-// 0: six arrays; 1: both triples side by side; 2: only the incoming ones; 3: only the outgoing ones
-__host__ __device__ inline size_t col_in(size_t p, int k, size_t cz) {
-  return (C2R_COLS_AOS == 1 || C2R_COLS_AOS == 2) ? 3 * p + (size_t)k : p + (size_t)k * cz;
-}
-__host__ __device__ inline size_t col_out(size_t p, int k, size_t cz) {
-  return (C2R_COLS_AOS == 1 || C2R_COLS_AOS == 3) ? 3 * cz + 3 * p + (size_t)k : p + (size_t)(3 + k) * cz;
-}
+__host__ __device__ inline size_t col_in(size_t p, int k, size_t) { return 3 * p + (size_t)k; }
+__host__ __device__ inline size_t col_out(size_t p, int k, size_t cz) { return 3 * cz + 3 * p + (size_t)k; }
 
-// The sweep's stores of a cell's six columns.  C2R_SWEEP_NT: 1 = the incoming columns, which only the rates launch
-// reads, long after, as non-temporal stores: they then do not sit dirty in the L2s until the end of the launch, when
-// every XCD writes its cache back before the next shell may start (a launch per shell: up to 32 MB each time).
-// 2 = the outgoing ones as well.  Measured at 256^3 x 8, same box, ms per pass (sweep | rates): isothermal 0: 3.98-4.03
-// | 18.5, 1: 3.82 | 18.5, 2: 3.78-3.83 | 18.4; with heating 0: 3.86 | 27.9, 1: 3.63 | 28.0-28.1, 2: 3.69 | 28.3 -- the
-// rates launch reads non-temporally written columns a little slower, so only the incoming ones are stored that way.
+// The sweep's stores of a cell's six columns.  The incoming columns, which only the rates launch reads, long after, are
+// stored non-temporally: they then do not sit dirty in the L2s until the end of the launch, when every XCD writes its
+// cache back before the next shell may start (a launch per shell: up to 32 MB each time).  The outgoing ones, which the
+// next shells interpolate from, are stored plainly.  Measured at 256^3 x 8, same box, ms per pass (sweep | rates), with
+// plain stores / incoming ones non-temporal / all six non-temporal: isothermal 3.98-4.03 | 18.5, 3.82 | 18.5,
+// 3.78-3.83 | 18.4; with heating 3.86 | 27.9, 3.63 | 28.0-28.1, 3.69 | 28.3 -- the rates launch reads non-temporally
+// written columns a little slower, so only the incoming ones are stored that way.
 // (Non-temporal LOADS of the columns in the rates kernel: +0.4 ms per launch, neighbouring cubes share their lines.)
-#ifndef C2R_SWEEP_NT
-#define C2R_SWEEP_NT 1
-#endif
 __device__ __forceinline__ void store_columns(global_double *cs, size_t p, size_t cz, double cin_HI, double cin_HeI, double cin_HeII,
                                               double cout_HI, double cout_HeI, double cout_HeII) {
-#if C2R_SWEEP_NT >= 1
   __builtin_nontemporal_store(cin_HI, &cs[col_in(p, 0, cz)]);
   __builtin_nontemporal_store(cin_HeI, &cs[col_in(p, 1, cz)]);
   __builtin_nontemporal_store(cin_HeII, &cs[col_in(p, 2, cz)]);
-#else
-  cs[col_in(p, 0, cz)] = cin_HI;
-  cs[col_in(p, 1, cz)] = cin_HeI;
-  cs[col_in(p, 2, cz)] = cin_HeII;
-#endif
-#if C2R_SWEEP_NT >= 2
-  __builtin_nontemporal_store(cout_HI, &cs[col_out(p, 0, cz)]);
-  __builtin_nontemporal_store(cout_HeI, &cs[col_out(p, 1, cz)]);
-  __builtin_nontemporal_store(cout_HeII, &cs[col_out(p, 2, cz)]);
-#else
   cs[col_out(p, 0, cz)] = cout_HI;
   cs[col_out(p, 1, cz)] = cout_HeI;
   cs[col_out(p, 2, cz)] = cout_HeII;
-#endif
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -635,18 +609,6 @@ k_col_to_grid(Grid g, SrcDev S, const double *__restrict__ cs, double *__restric
 #ifndef C2R_RATES_WAVES_HEAT_MULTI
 #define C2R_RATES_WAVES_HEAT_MULTI 4
 #endif
-#ifndef C2R_RATES_XCD_CHUNK
-#define C2R_RATES_XCD_CHUNK 128
-#endif
-#ifndef C2R_RATES_BAND_ROWS
-#define C2R_RATES_BAND_ROWS 1
-#endif
-#ifndef C2R_RATES_PARK_RICOTTI
-#define C2R_RATES_PARK_RICOTTI 0
-#endif
-#ifndef C2R_RATES_PARK_SUMS
-#define C2R_RATES_PARK_SUMS 2
-#endif
 template <bool HEAT, bool MULTI>
 __global__ void __launch_bounds__(BLOCK, MULTI ? (HEAT ? C2R_RATES_WAVES_HEAT_MULTI : 4) : (HEAT ? C2R_RATES_WAVES_HEAT : C2R_RATES_WAVES_ISO))
 k_rates(Grid g, const SrcDev *__restrict__ src, int nsrc, StepScalars sc, const double *__restrict__ ndens,
@@ -665,16 +627,10 @@ k_rates(Grid g, const SrcDev *__restrict__ src, int nsrc, StepScalars sc, const 
   // `tile_ptr` / `tile_src`: for each listed tile the sources (positions in `src`, ascending = source order)
   // whose sub-box reaches into it, so that a batch of hundreds of faint sources costs a cell only the sources
   // near it.  Without lists every cell walks all nsrc sources of the batch (few sources, boxes that fill the mesh).
-  // the (invc, logc) table of the bit-exact log (2 KB) in LDS: two gathers per band iteration that no longer
-  // queue behind the photo-table gathers in the vector memory path
-#if !defined(C2R_NO_LOGTAB4)
-  // ... with the log's power of two folded in (gm::LogEntry, 8 KB)
+  // the (invc, logc) table of the bit-exact log in LDS, with the log's power of two folded in (gm::LogEntry, 8 KB): two
+  // gathers per band iteration that no longer queue behind the photo-table gathers in the vector memory path
   __shared__ gm::LogEntry s_logtab[256];
   s_logtab[threadIdx.x] = gm::make_log_entry((int)threadIdx.x);
-#else
-  __shared__ double s_logtab[256];
-  s_logtab[threadIdx.x] = gm::log_table()[threadIdx.x];
-#endif
   __syncthreads();
   // the band data as uploaded (a BandDataByRow: the plain arrays and, behind them, the same numbers band by band); a kernel
   // chooses its reading of them by the TYPE it hands down -- the base for the array form (an upcast, not a reinterpretation)
@@ -690,18 +646,16 @@ k_rates(Grid g, const SrcDev *__restrict__ src, int nsrc, StepScalars sc, const 
   const int ti = (g.n1 + 7) >> 3, tj = (g.n2 + 7) >> 3;
   // Workgroups are dealt to the 8 XCDs round-robin, and each XCD has its own L2.  A cube reads its columns as 32-byte
   // rows of shell faces, so the other half of every cache line belongs to the neighbouring cube: give each XCD a
-  // contiguous run of tiles (a slab of the mesh), so that the neighbour's request finds the line in the same L2.
+  // contiguous run of C = 128 tiles (a slab of the mesh), so that the neighbour's request finds the line in the same L2.
   int vb = (int)blockIdx.x;
-#if C2R_RATES_XCD_CHUNK > 0
   {
-    constexpr int C = C2R_RATES_XCD_CHUNK;
+    constexpr int C = 128;
     const int full = (int)(gridDim.x / (8 * C)) * (8 * C);
     if (vb < full) {
       const int r = vb >> 3, xcd = vb & 7;
       vb = (r / C) * (8 * C) + xcd * C + (r % C);
     }
   }
-#endif
   const int tile = tiles ? tiles[tile_base + vb] : tile_base + vb;
   const int bi = tile % ti, bj = (tile / ti) % tj, bk = tile / (ti * tj);
   const int lane = threadIdx.x & 63;
@@ -734,27 +688,16 @@ k_rates(Grid g, const SrcDev *__restrict__ src, int nsrc, StepScalars sc, const 
   }
   // secondary-ionisation parameters of this cell, i_state = h_av(1) (evolve_point.F90:255): once per cell,
   // not once per source
-  // Values of a cell that the band loops do not touch can wait in LDS, one column per lane, where the register
-  // allocation would otherwise spill them to scratch memory (bit 0 of the macros: the one-SED heating kernel, bit 1: the
-  // three-SED heating kernel).  C2R_RATES_PARK_SUMS: the cell's denominators and running sums, touched once per source
-  // (default: the three-SED kernel, which then fits four waves per SIMD without a private segment).
-  // C2R_RATES_PARK_RICOTTI: the secondary-ionisation parameters too (default: nowhere -- six LDS reads per heating band
-  // cost more than the registers: 369 against 357 ms per pass on one box).
-  constexpr bool PARK = HEAT && (((C2R_RATES_PARK_SUMS) >> (MULTI ? 1 : 0)) & 1) != 0;
-  constexpr bool PARK_RIC = HEAT && (((C2R_RATES_PARK_RICOTTI) >> (MULTI ? 1 : 0)) & 1) != 0;
-  __shared__ double s_ric[PARK_RIC ? 6 * BLOCK : 1];
+  Ricotti ric = {};
+  if (HEAT) ric = ricotti_parameters(h1);
+  // The three-SED heating kernel parks the cell's denominators and running sums, which the band loops do not touch, in
+  // LDS, one column per lane, where the register allocation would otherwise spill them to scratch memory: it then fits
+  // four waves per SIMD without a private segment.  (Parking the secondary-ionisation parameters as well costs more
+  // than their registers: six LDS reads per heating band, 369 against 357 ms per pass on one box.)
+  constexpr bool PARK = HEAT && MULTI;
   // the three denominators of the cell and its four running sums, touched once per source: [den_HI, den_HeI, den_HeII,
-  // a_HI, a_HeI, a_HeII, a_heat] x BLOCK
+  // a_HI, a_HeI, a_HeII, a_heat] x BLOCK (each lane reads back only what it wrote itself: no barrier)
   __shared__ double s_den[PARK ? 7 * BLOCK : 1];
-  Ricotti ric_ = {};
-  if (HEAT) ric_ = ricotti_parameters(h1);
-  if (PARK_RIC) {
-#pragma unroll
-    for (int n = 0; n < 3; n++) {
-      s_ric[n * BLOCK + threadIdx.x] = ric_.y1R[n];
-      s_ric[(3 + n) * BLOCK + threadIdx.x] = ric_.y2R[n];
-    }
-  }
   if (PARK) {
     s_den[threadIdx.x] = den_HI;
     s_den[BLOCK + threadIdx.x] = den_HeI;
@@ -764,11 +707,6 @@ k_rates(Grid g, const SrcDev *__restrict__ src, int nsrc, StepScalars sc, const 
     s_den[5 * BLOCK + threadIdx.x] = a_HeII;
     s_den[6 * BLOCK + threadIdx.x] = a_heat;
   }
-  const RicottiParked ric_parked = {(ParkedPtr)&s_ric[PARK_RIC ? threadIdx.x : 0], BLOCK};
-  // (each lane reads back only what it wrote itself: no barrier)
-  const auto &ric = [&]() -> const std::conditional_t<PARK_RIC, RicottiParked, Ricotti> & {
-    if constexpr (PARK_RIC) return ric_parked; else return ric_;
-  }();
   bool touched = false;
   const int slot = tile_base + vb;
   const int e0 = tile_ptr ? tile_ptr[slot] : 0, e1 = tile_ptr ? tile_ptr[slot + 1] : nsrc;
@@ -792,19 +730,6 @@ k_rates(Grid g, const SrcDev *__restrict__ src, int nsrc, StepScalars sc, const 
     const double cout_HI = cs[col_out(p, 0, cz)];
     const double cin_HI = cs[col_in(p, 0, cz)], cin_HeI = cs[col_in(p, 1, cz)], cin_HeII = cs[col_in(p, 2, cz)];
     const double cout_HeI = cs[col_out(p, 1, cz)], cout_HeII = cs[col_out(p, 2, cz)];
-#if defined(C2R_RATES_DUMMY_TRAFFIC)
-    // EXPERIMENT (never in the product): the column sweep's compulsory traffic -- 96 bytes per cell.source, half read, half
-    // written -- moved by this kernel on top of its own, to see what a fused sweep + rates kernel could hope to hide
-    // behind the band loops.  Reads come from another part of the source's block, the writes go back there unchanged.
-    {
-      const size_t p2 = (p + cz / 2) % cz;
-      double d0 = cs[col_in(p2, 0, cz)], d1 = cs[col_in(p2, 1, cz)], d2 = cs[col_in(p2, 2, cz)];
-      double d3 = cs[col_out(p2, 0, cz)], d4 = cs[col_out(p2, 1, cz)], d5 = cs[col_out(p2, 2, cz)];
-      asm volatile("" : "+v"(d0), "+v"(d1), "+v"(d2), "+v"(d3), "+v"(d4), "+v"(d5)); // opaque: the stores are not "the value just loaded"
-      cs[col_in(p2, 0, cz)] = d0; cs[col_in(p2, 1, cz)] = d1; cs[col_in(p2, 2, cz)] = d2;
-      cs[col_out(p2, 0, cz)] = d3; cs[col_out(p2, 1, cz)] = d4; cs[col_out(p2, 2, cz)] = d5;
-    }
-#endif
     double vol_ph;
     if (di == 0 && dj == 0 && dk == 0) {
       vol_ph = sc.cellvol;
@@ -823,7 +748,7 @@ k_rates(Grid g, const SrcDev *__restrict__ src, int nsrc, StepScalars sc, const 
         PhotoOut o;
         if (MULTI) {
           const double nf[NSED] = {S.nflux, S.nflux_sed[0], S.nflux_sed[1]};
-          if constexpr (HEAT && (C2R_RATES_BAND_ROWS)) // this kernel reads cross sections and factors band by band (BandDataByRow)
+          if constexpr (HEAT) // this kernel reads cross sections and factors band by band (BandDataByRow)
             photoion_rates_multi<HEAT>(*bdr, ss, cin_HI, cout_HI, cin_HeI, cout_HeI, cin_HeII, cout_HeII,
                                        vol_ph, nf, ric, o, &s_logtab[0], pins);
           else
@@ -903,12 +828,6 @@ constexpr int CHEM_CTL_MAXWORK = CHEM_HIST, CHEM_CTL_MAXNIT = CHEM_HIST + 1, CHE
 #ifndef C2R_CHEM_WAVES
 #define C2R_CHEM_WAVES 2
 #endif
-#ifndef C2R_CHEM_XCD_CHUNK
-#define C2R_CHEM_XCD_CHUNK 64
-#endif
-#ifndef C2R_CHEM_CUBES
-#define C2R_CHEM_CUBES 1
-#endif
 // LDSTAB (heating only): the five cooling curves (32 KB) and the log's table (2 KB) in LDS.  A thermal sub-step is one
 // long chain of dependent operations, two of whose links are memory round trips -- the table of log10(T), then ten
 // cooling-curve entries -- and with two waves per SIMD nothing hides them: from LDS they cost a sixth.  Filling 34 KB
@@ -933,7 +852,7 @@ k_chemistry(Grid g, StepScalars sc, double dt, const double *__restrict__ ndens,
   // do_chemistry iterations than their neighbours lie on surfaces (ionisation fronts, the edges of sub-boxes): a row of
   // 64 cells crosses such a surface in one or two cells, a cube in sixteen -- an eighth as many waves are held up
   // (profiles/r04_chem_nit.json: the first iteration of a time step in ionised gas has a mean of 2.2 iterations per cell
-  // and of 3.0 per row-shaped wave).  Cubes of one XCD are neighbours (runs of C2R_CHEM_XCD_CHUNK): the other three
+  // and of 3.0 per row-shaped wave).  Cubes of one XCD are neighbours (runs of 64 blocks): the other three
   // quarters of every 128-byte line a cube touches belong to the next cubes along i.
   // Heating runs: budget > 0 drops a cell whose thermal sub-cycling passes `budget` steps -- nothing of it is
   // stored -- and appends it to `deferred`, to be redone from scratch by a launch that holds only such cells
@@ -958,7 +877,7 @@ k_chemistry(Grid g, StepScalars sc, double dt, const double *__restrict__ ndens,
     constexpr int WPB = C2R_CHEM_BLOCK / 64; // waves per block
     int vb = (int)blockIdx.x;
     {
-      constexpr int C = C2R_CHEM_XCD_CHUNK;
+      constexpr int C = 64;
       const int full = (int)(gridDim.x / (8 * C)) * (8 * C);
       if (vb < full) {
         const int r = vb >> 3, xcd = vb & 7;
@@ -2723,10 +2642,7 @@ static int boundary_loss(c2r_ctx *c, int set, size_t list_off, int n, int s_lo, 
 }
 
 // shells below this one read the i-faces' state from the mesh-ordered grids (see pass_list)
-#ifndef C2R_TRANSPOSED_FROM_SHELL
-#define C2R_TRANSPOSED_FROM_SHELL 32
-#endif
-constexpr int TRANSPOSED_FROM_SHELL = C2R_TRANSPOSED_FROM_SHELL;
+constexpr int TRANSPOSED_FROM_SHELL = 32;
 
 constexpr int PROBE_SAMPLE = 16; // the probe looks at 8 cells of every 16th block of the round's shells
 
@@ -2999,7 +2915,7 @@ static bool all_reached(const c2r_ctx *c, const Batch &B, int round) {
   return true;
 }
 
-// Source b's column block moves to `ncols`, made for shells 0..ncap (the shells stored so far are a prefix of every array).
+// Source b's column block moves to `ncols`, made for shells 0..ncap (the shells stored so far are a prefix of each half).
 static int move_block(const PassCtx &P, Batch &B, int b, int ncap, double *ncols) {
   c2r_ctx *c = P.c;
   SrcRun &r = B.run[b];
@@ -3008,15 +2924,10 @@ static int move_block(const PassCtx &P, Batch &B, int b, int ncap, double *ncols
   SrcDev &S = c->h_src[B.set][b];
   const size_t wn = (size_t)(2 * ncap + 1), ncz = wn * wn * wn;
   const size_t wp = (size_t)(2 * r.smax_prev + 1), have = r.smax_prev >= 0 ? wp * wp * wp : 0;
-  // the shells stored so far are a prefix of each array (or of each array of triples)
-  for (int half = 0; half < 2 && have > 0; half++) {
-    const bool triples = C2R_COLS_AOS == 1 || C2R_COLS_AOS == (half ? 3 : 2);
-    for (int k = 0; k < (triples ? 1 : 3); k++) {
-      const size_t at = (size_t)(3 * half + k);
-      HIPCHK(c, hipMemcpyAsync(ncols + at * ncz, S.cols + at * S.cz, sizeof(double) * (triples ? 3 : 1) * have,
-                               hipMemcpyDeviceToDevice, c->stream));
-    }
-  }
+  // the shells stored so far are a prefix of each half, the incoming triples and the outgoing ones (col_in, col_out)
+  for (int half = 0; half < 2 && have > 0; half++)
+    HIPCHK(c, hipMemcpyAsync(ncols + 3 * half * ncz, S.cols + 3 * half * S.cz, sizeof(double) * 3 * have,
+                             hipMemcpyDeviceToDevice, c->stream));
   if (S.cz > 0) c->vacated[B.set].push_back(c2r_ctx::Segment{S.cols, 6 * S.cz}); // free for the batch's later moves
   S.cols = ncols;
   S.cz = ncz;
@@ -3632,7 +3543,7 @@ static int launch_chemistry(c2r_ctx *c, hipStream_t st, double dt, size_t first,
   // C2R_CHEM_CUBES=0 / 1 / 2 (environment): rows always / 4 x 4 x 4 always / 8 x 4 x 2 always; default: 8 x 4 x 2 by the rule.
   static const int cubes_env = getenv("C2R_CHEM_CUBES") ? atoi(getenv("C2R_CHEM_CUBES")) : -1;
   const bool busy = c->last_conv < 0 || c->last_conv * 64 > (long long)g.ncell;
-  const int cubes_want = cubes_env >= 0 ? cubes_env : (C2R_CHEM_CUBES && busy ? 2 : 0);
+  const int cubes_want = cubes_env >= 0 ? cubes_env : (busy ? 2 : 0);
   const int cubes = cubes_want && !list && g.n1 % 8 == 0 && g.n2 % 4 == 0 && first % plane == 0 && count % (4 * plane) == 0 ? cubes_want : 0;
   if (c->isothermal)
     hipLaunchKernelGGL(k_chemistry<false>, dim3(nblk), dim3(bs), 0, st, g, sc, dt, c->d_ndens, c->d_xh,
