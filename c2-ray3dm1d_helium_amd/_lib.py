@@ -34,6 +34,18 @@ class IterationReport(C.Structure):
                 ("minima_av", C.c_double * 2), ("reccoef", C.c_double * 12)]
 
 
+class CommSelftestReport(C.Structure):
+    """c2r_comm_selftest_report (include/c2ray_hip.h)."""
+    _fields_ = [("ranks", C.c_int), ("kind", C.c_int), ("devices", C.c_int), ("elements", C.c_longlong * 2),
+                ("mismatches", C.c_longlong * 2), ("bad_route", C.c_int), ("bad_rank", C.c_int), ("bad_index", C.c_longlong),
+                ("got", C.c_double), ("expected", C.c_double), ("ms", C.c_double * 2)]
+
+
+class CommTiming(C.Structure):
+    """c2r_comm_timing (include/c2ray_hip.h)."""
+    _fields_ = [("slabs", C.c_int), ("allreduce_ms", C.c_double), ("allreduce_exposed_ms", C.c_double), ("tail_ms", C.c_double)]
+
+
 class SedSetup(C.Structure):
     """struct c2r_sed_setup (include/c2ray_hip.h)."""
     _fields_ = [("nfreq", C.c_int), ("sed", C.c_int), ("freq_min", _dp), ("delta_freq", _dp), ("xsec_index", _dp),
@@ -113,6 +125,8 @@ SYMBOLS = {
     "c2r_comm_library": (C.c_int, [C.c_char_p, C.c_int]),
     "c2r_allreduce_rates": (C.c_int, [C.c_void_p]),
     "c2r_pass_allreduce_chemistry": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, _ip]),
+    "c2r_comm_selftest": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(CommSelftestReport)]),
+    "c2r_get_comm_timing": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(CommTiming)]),
     "c2r_iteration": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.POINTER(IterationReport)]),
     "c2r_get_timing": (C.c_int, [C.c_void_p, C.POINTER(Timing)]),
     "c2r_get_timing_device": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(Timing)]),

@@ -248,6 +248,133 @@ int with_comm_abort(c2r_ctx *c, const char *who, F body) {
   return rc;
 }
 
+// ---- c2r_comm_selftest: the pattern of include/c2ray_hip.h ------------------------------------------------------------
+// v(r, i) = (r + 1) a(i) 2^e(i); `mult` is r + 1 for what a rank contributes and n (n + 1) / 2 for the sum
+__host__ __device__ inline double selftest_value(unsigned long long i, unsigned long long mult) {
+  unsigned long long z = i + 0x9E3779B97F4A7C15ull; // splitmix64
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  const unsigned long long h = z ^ (z >> 31);
+  const unsigned long long a = ((1ull << 29) + (h & ((1ull << 29) - 1))) | 1ull;
+  const int e = (int)((h >> 32) % 121ull) - 60;
+  return ldexp((double)(mult * a), e); // mult * a < 2^53: exact
+}
+
+// buf[i] = v(rank, i) for the whole buffer; resets the route's record {mismatches, lowest mismatching index}
+__global__ void __launch_bounds__(BLOCK) k_selftest_fill(double *__restrict__ buf, size_t n, unsigned long long mult,
+                                                         unsigned long long *__restrict__ rec) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    rec[0] = 0ull;
+    rec[1] = ~0ull;
+  }
+  for (size_t i = (size_t)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (size_t)gridDim.x * BLOCK) buf[i] = selftest_value(i, mult);
+}
+
+// buf[off .. off+len) against the closed form of the sum: per block one count and one lowest index, one atomic each
+__global__ void __launch_bounds__(BLOCK) k_selftest_check(const double *__restrict__ buf, size_t off, size_t len,
+                                                          unsigned long long mult_sum, unsigned long long *__restrict__ rec) {
+  __shared__ unsigned long long s_bad[BLOCK], s_lo[BLOCK];
+  unsigned long long bad = 0ull, lo = ~0ull;
+  for (size_t j = (size_t)blockIdx.x * BLOCK + threadIdx.x; j < len; j += (size_t)gridDim.x * BLOCK) {
+    const size_t i = off + j;
+    if (!(buf[i] == selftest_value(i, mult_sum))) { // (a NaN is a mismatch)
+      bad++;
+      lo = lo < i ? lo : (unsigned long long)i;
+    }
+  }
+  s_bad[threadIdx.x] = bad;
+  s_lo[threadIdx.x] = lo;
+  __syncthreads();
+  for (int w = BLOCK / 2; w > 0; w >>= 1) {
+    if ((int)threadIdx.x < w) {
+      s_bad[threadIdx.x] += s_bad[threadIdx.x + w];
+      const unsigned long long o = s_lo[threadIdx.x + w];
+      if (o < s_lo[threadIdx.x]) s_lo[threadIdx.x] = o;
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0 && s_bad[0]) {
+    atomicAdd(&rec[0], s_bad[0]);
+    atomicMin(&rec[1], s_lo[0]);
+  }
+}
+
+int selftest_grid(size_t n) { return (int)std::max<size_t>(1, std::min<size_t>(4096, (n + BLOCK - 1) / BLOCK)); }
+
+// everything of the self-test that allocates, before its timed part
+int selftest_prepare(c2r_ctx *d, int nslab) {
+  HIPCHK(d, hipSetDevice(d->device));
+  if (!d->d_selftest) HIPCHK(d, hipMalloc(&d->d_selftest, sizeof(unsigned long long) * 4));
+  if (!d->h_selftest) HIPCHK(d, hipHostMalloc(&d->h_selftest, sizeof(unsigned long long) * 6));
+  for (hipEvent_t &e : d->ev_selftest)
+    if (!e) HIPCHK(d, hipEventCreate(&e));
+  for (std::vector<hipEvent_t> *list : {&d->ev_slab, &d->ev_sum})
+    while (list->size() < (size_t)nslab) {
+      hipEvent_t e;
+      HIPCHK(d, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+      list->push_back(e);
+    }
+  return 0;
+}
+
+// the route's record and, where something mismatched, the value found at the lowest such index: through the pinned
+// members of the context, behind sync_stream on the comm stream (the C2R_COMM_TIMEOUT_S watchdog covers a peer that
+// never arrives)
+int selftest_collect(c2r_ctx *c, const std::vector<c2r_ctx *> &dev, int route) {
+  for (c2r_ctx *d : dev) {
+    HIPCHK(c, hipSetDevice(d->device));
+    HIPCHK(c, hipMemcpyAsync(d->h_selftest + 2 * route, d->d_selftest + 2 * route, sizeof(unsigned long long) * 2, hipMemcpyDeviceToHost, d->comm_stream));
+  }
+  for (c2r_ctx *d : dev) {
+    HIPCHK(c, hipSetDevice(d->device));
+    if (sync_stream(d, d->comm_stream, "the self-test of the sum over the ranks")) { c->err = d->err; return 1; }
+  }
+  for (c2r_ctx *d : dev) {
+    if (!d->h_selftest[2 * route]) continue;
+    HIPCHK(c, hipSetDevice(d->device));
+    HIPCHK(c, hipMemcpyAsync(d->h_selftest + 4 + route, d->d_rates + d->h_selftest[2 * route + 1], sizeof(double), hipMemcpyDeviceToHost, d->comm_stream));
+    if (sync_stream(d, d->comm_stream, "the self-test of the sum over the ranks")) { c->err = d->err; return 1; }
+  }
+  return 0;
+}
+
+// c2r_get_comm_timing: the timing events of a device, made before its pass (nothing is made or recorded with timing off)
+int comm_timing_prepare(c2r_ctx *d) {
+  if (!d->timing) {
+    d->ctm = c2r_comm_timing{};
+    return 0;
+  }
+  for (hipEvent_t &e : d->ev_ct)
+    if (!e) HIPCHK(d, hipEventCreate(&e));
+  return 0;
+}
+int comm_timing_mark(c2r_ctx *c, c2r_ctx *d, int which) {
+  if (d->timing) HIPCHK(c, hipEventRecord(d->ev_ct[which], d->comm_stream));
+  return 0;
+}
+// ... read once the iteration's synchronisation is behind us
+int comm_timing_read(c2r_ctx *c, c2r_ctx *d) {
+  if (!d->timing) return 0;
+  HIPCHK(c, hipSetDevice(d->device));
+  float ms = 0;
+  d->ctm = c2r_comm_timing{};
+  d->ctm.slabs = d->pass_slabs;
+  HIPCHK(c, hipEventElapsedTime(&ms, d->ev_ct[1], d->ev_ct[4]));
+  d->ctm.allreduce_ms = ms;
+  HIPCHK(c, hipEventElapsedTime(&ms, d->ev_ct[3], d->ev_ct[4]));
+  d->ctm.tail_ms = ms;
+  if (d->ct_rates_recorded) {
+    // from the later of "rates complete" and "first sum released": a device whose rates were through before the host had
+    // queued the first sum (a rank without sources; any rank of a tiny mesh) has waited for the host until then, not for
+    // the wire -- so the exposed part lies inside [first sum released, tail complete] and never exceeds allreduce_ms
+    float to_sum = 0, to_release = 0;
+    HIPCHK(c, hipEventElapsedTime(&to_sum, d->ev_ct[0], d->ev_ct[2]));
+    HIPCHK(c, hipEventElapsedTime(&to_release, d->ev_ct[0], d->ev_ct[1]));
+    d->ctm.allreduce_exposed_ms = std::max(0.0f, to_sum - std::max(0.0f, to_release));
+  }
+  return 0;
+}
+
 } // namespace
 
 extern "C" int c2r_device_count(void) {
@@ -309,6 +436,177 @@ extern "C" int c2r_comm_unique_id(char id[128]) {
   return 0;
 }
 
+// c2r_comm_selftest (see the header): a known pattern through the context's own buffer, communicators, comm streams and
+// events, by the routines and in the stream order of the two production routes
+static int comm_selftest_body(c2r_ctx *c, int nslab, c2r_comm_selftest_report *rep) {
+  const std::vector<c2r_ctx *> dev = devices_of(c);
+  const unsigned long long n = (unsigned long long)c->comm_nranks, mult_sum = n * (n + 1) / 2;
+  const size_t plane = (size_t)c->g.n1 * c->g.n2, ncell = c->g.ncell;
+  const int ns = std::min(nslab, c->g.n3);
+  rep->ranks = c->comm_nranks;
+  rep->kind = c->comm_kind;
+  rep->devices = (int)dev.size();
+  for (c2r_ctx *d : dev) {
+    if (d->pass_open) return fail(c, "c2r_comm_selftest: a pass is open (c2r_pass_sources_begin without c2r_pass_sources_end)");
+    if (selftest_prepare(d, ns)) { c->err = d->err; return 1; }
+    // what the test leaves in the buffer is never read: the next pass finds c2r_set_rates_to_zero's state (phiheat
+    // included, which an isothermal pass would otherwise take for zero)
+    d->rates_zero_pending = true;
+    d->phiheat_dirty = true;
+  }
+  // route 0, as c2r_allreduce_rates: the whole buffer in one all-reduce
+  for (c2r_ctx *d : dev) {
+    HIPCHK(c, hipSetDevice(d->device));
+    if (d == c) HIPCHK(c, hipEventRecord(c->ev_selftest[0], c->stream));
+    hipLaunchKernelGGL(k_selftest_fill, dim3(selftest_grid(c->rates_count)), dim3(BLOCK), 0, d->stream, d->d_rates, c->rates_count,
+                       (unsigned long long)d->comm_rank + 1, d->d_selftest);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(d->ev_comm_a, d->stream));
+    HIPCHK(c, hipStreamWaitEvent(d->comm_stream, d->ev_comm_a, 0));
+  }
+  {
+    const size_t off[1] = {0}, len[1] = {c->rates_count};
+    if (sum_ranges(c, 1, off, len)) return 1;
+  }
+  for (c2r_ctx *d : dev) {
+    HIPCHK(c, hipSetDevice(d->device));
+    hipLaunchKernelGGL(k_selftest_check, dim3(selftest_grid(c->rates_count)), dim3(BLOCK), 0, d->comm_stream, d->d_rates, (size_t)0,
+                       c->rates_count, mult_sum, d->d_selftest);
+    HIPCHK(c, hipGetLastError());
+    if (d == c) HIPCHK(c, hipEventRecord(c->ev_selftest[1], c->comm_stream));
+  }
+  rep->elements[0] = (long long)c->rates_count;
+  if (selftest_collect(c, dev, 0)) return 1;
+  // route 1, as c2r_pass_allreduce_chemistry: slab by slab behind the slab events, each slab's component ranges in one
+  // grouped launch, the check of a slab behind the event of its sum (where production queues its chemistry), then the tail
+  for (c2r_ctx *d : dev) {
+    HIPCHK(c, hipSetDevice(d->device));
+    if (d == c) HIPCHK(c, hipEventRecord(c->ev_selftest[2], c->stream));
+    hipLaunchKernelGGL(k_selftest_fill, dim3(selftest_grid(c->rates_count)), dim3(BLOCK), 0, d->stream, d->d_rates, c->rates_count,
+                       (unsigned long long)d->comm_rank + 1, d->d_selftest + 2);
+    HIPCHK(c, hipGetLastError());
+    for (int sidx = 0; sidx < ns; sidx++) HIPCHK(c, hipEventRecord(d->ev_slab[sidx], d->stream));
+  }
+  int ncomp = 0;
+  for (int sidx = 0; sidx < ns; sidx++) {
+    const size_t k0 = (size_t)((long long)c->g.n3 * sidx / ns), k1 = (size_t)((long long)c->g.n3 * (sidx + 1) / ns);
+    size_t off[4], len[4];
+    const int nr = ncomp = slab_ranges(c, plane * k0, plane * (k1 - k0), off, len);
+    for (c2r_ctx *d : dev) {
+      HIPCHK(c, hipSetDevice(d->device));
+      HIPCHK(c, hipStreamWaitEvent(d->comm_stream, d->ev_slab[sidx], 0));
+    }
+    if (sum_ranges(c, nr, off, len)) return 1;
+    for (c2r_ctx *d : dev) {
+      HIPCHK(c, hipSetDevice(d->device));
+      HIPCHK(c, hipEventRecord(d->ev_sum[sidx], d->comm_stream));
+      HIPCHK(c, hipStreamWaitEvent(d->stream, d->ev_sum[sidx], 0));
+      for (int k = 0; k < nr; k++)
+        hipLaunchKernelGGL(k_selftest_check, dim3(selftest_grid(len[k])), dim3(BLOCK), 0, d->stream, d->d_rates, off[k], len[k], mult_sum,
+                           d->d_selftest + 2);
+      HIPCHK(c, hipGetLastError());
+    }
+  }
+  for (c2r_ctx *d : dev) {
+    HIPCHK(c, hipSetDevice(d->device));
+    HIPCHK(c, hipEventRecord(d->ev_comm_a, d->stream));
+    HIPCHK(c, hipStreamWaitEvent(d->comm_stream, d->ev_comm_a, 0));
+  }
+  {
+    const size_t off[1] = {4 * ncell}, len[1] = {(size_t)C2R_NFREQ + 1};
+    if (sum_ranges(c, 1, off, len)) return 1;
+  }
+  for (c2r_ctx *d : dev) {
+    HIPCHK(c, hipSetDevice(d->device));
+    hipLaunchKernelGGL(k_selftest_check, dim3(1), dim3(BLOCK), 0, d->comm_stream, d->d_rates, 4 * ncell, (size_t)C2R_NFREQ + 1, mult_sum,
+                       d->d_selftest + 2);
+    HIPCHK(c, hipGetLastError());
+    if (d == c) HIPCHK(c, hipEventRecord(c->ev_selftest[3], c->comm_stream));
+  }
+  rep->elements[1] = (long long)((size_t)ncomp * ncell + C2R_NFREQ + 1);
+  if (selftest_collect(c, dev, 1)) return 1;
+  // the verdict: local to this process
+  HIPCHK(c, hipSetDevice(c->device));
+  for (int route = 0; route < 2; route++) {
+    float ms = 0;
+    HIPCHK(c, hipEventElapsedTime(&ms, c->ev_selftest[2 * route], c->ev_selftest[2 * route + 1]));
+    rep->ms[route] = ms;
+  }
+  const c2r_ctx *bad_dev = nullptr;
+  for (int route = 0; route < 2; route++)
+    for (const c2r_ctx *d : dev) {
+      const unsigned long long bad = d->h_selftest[2 * route];
+      rep->mismatches[route] += (long long)bad;
+      if (bad && !bad_dev) {
+        bad_dev = d;
+        rep->bad_route = route;
+        rep->bad_rank = d->comm_rank;
+        rep->bad_index = (long long)d->h_selftest[2 * route + 1];
+        std::memcpy(&rep->got, d->h_selftest + 4 + route, sizeof(double));
+        rep->expected = selftest_value((unsigned long long)rep->bad_index, mult_sum);
+      }
+    }
+  if (!bad_dev) return 0;
+  char lib[1024] = "the in-process sum of replicas that share a device";
+  if (c->comm_kind == 1) (void)c2r_comm_library(lib, (int)sizeof lib);
+  unsigned long long gb, eb;
+  std::memcpy(&gb, &rep->got, 8);
+  std::memcpy(&eb, &rep->expected, 8);
+  char msg[2048];
+  snprintf(msg, sizeof msg,
+           "c2r_comm_selftest: the sum over the %d ranks came back WRONG: route %d (%s), rank %d, device %d, index %lld of the "
+           "reduction buffer: got %.17g (0x%016llx), expected %.17g (0x%016llx); mismatches on this process's %d device(s): %lld of "
+           "%lld doubles (whole buffer), %lld of %lld (slab-wise); library: %s",
+           rep->ranks, rep->bad_route, rep->bad_route == 0 ? "whole buffer, as c2r_allreduce_rates" : "slab-wise, as c2r_pass_allreduce_chemistry",
+           rep->bad_rank, bad_dev->device, rep->bad_index, rep->got, gb, rep->expected, eb, rep->devices, rep->mismatches[0],
+           rep->elements[0] * rep->devices, rep->mismatches[1], rep->elements[1] * rep->devices, lib);
+  c->err = msg;
+  return 1;
+}
+
+extern "C" int c2r_comm_selftest(c2r_ctx *c, int nslab, c2r_comm_selftest_report *rep) {
+  if (!c || !rep) return 1;
+  std::memset(rep, 0, sizeof *rep);
+  rep->bad_route = rep->bad_rank = -1;
+  rep->bad_index = -1;
+  rep->ranks = 1;
+  if (nslab < 1) return fail(c, "c2r_comm_selftest: nslab=%d", nslab);
+  if (!c->comm_kind) {
+    if (!c->replicas.empty()) return fail(c, "c2r_comm_selftest: a multi-device context needs c2r_comm_init_local or c2r_comm_init first");
+    rep->devices = 1;
+    return 0; // one rank: nothing is summed, nothing to check
+  }
+  if (c->comm_nranks > 4095)
+    return fail(c, "c2r_comm_selftest: %d ranks; the pattern's sums are exact (below 2^53) for at most 4095", c->comm_nranks);
+  return with_comm_abort(c, "c2r_comm_selftest", [&] { return comm_selftest_body(c, nslab, rep); });
+}
+
+// C2R_COMM_SELFTEST=1: the communicators of a context are tested before c2r_comm_init / c2r_comm_init_local hand them out
+static int selftest_at_init(c2r_ctx *c, const char *who) {
+  const char *on = getenv("C2R_COMM_SELFTEST");
+  if (!on || atoi(on) <= 0) return 0;
+  const char *env = getenv("C2R_ALLREDUCE_SLABS");
+  c2r_comm_selftest_report rep;
+  if (c2r_comm_selftest(c, env && atoi(env) > 0 ? atoi(env) : 4, &rep)) {
+    const std::string why = c->err;
+    (void)c2r_comm_destroy(c);
+    c->err = std::string(who) + " (C2R_COMM_SELFTEST): " + why;
+    return 1;
+  }
+  char lib[1024] = "none (in-process sum of replicas that share a device)";
+  if (rep.kind == 1) (void)c2r_comm_library(lib, (int)sizeof lib);
+  fprintf(stderr, "c2ray_hip: comm self-test ok: %d ranks, %lld + %lld doubles on each of %d device(s), %.3f + %.3f ms, library %s\n", rep.ranks,
+          rep.elements[0], rep.elements[1], rep.devices, rep.ms[0], rep.ms[1], lib);
+  return 0;
+}
+
+extern "C" int c2r_get_comm_timing(c2r_ctx *c, int idev, c2r_comm_timing *out) {
+  if (!c || !out) return 1;
+  if (idev < 0 || idev > (int)c->replicas.size()) return fail(c, "c2r_get_comm_timing: device %d of %d", idev, 1 + (int)c->replicas.size());
+  *out = idev == 0 ? c->ctm : c->replicas[(size_t)idev - 1]->ctm;
+  return 0;
+}
+
 // Rank `first_rank + i` of `nranks` for the i-th device of the context (one device: rank first_rank).
 // The source split of c2r_evolve3d / the Fortran shim (process p of P takes sources 1 + p + i * P on its device i)
 // assumes that every process drives the same number of devices, in rank order: first_rank and nranks must be
@@ -352,7 +650,7 @@ extern "C" int c2r_comm_init(c2r_ctx *c, int first_rank, int nranks, const char 
     dev[(size_t)i]->comm_rank = first_rank + i;
     dev[(size_t)i]->comm_nranks = nranks;
   }
-  return 0;
+  return selftest_at_init(c, "c2r_comm_init");
 }
 
 // One process, the devices of a context made by c2r_create_multi: ncclCommInitAll.  Replicas that share a
@@ -390,7 +688,7 @@ extern "C" int c2r_comm_init_local(c2r_ctx *c) {
     dev[i]->comm_rank = (int)i;
     dev[i]->comm_nranks = (int)dev.size();
   }
-  return 0;
+  return selftest_at_init(c, "c2r_comm_init_local");
 }
 
 extern "C" int c2r_comm_destroy(c2r_ctx *c) {
@@ -405,6 +703,7 @@ extern "C" int c2r_comm_destroy(c2r_ctx *c) {
     d->comm_nranks = 1;
     d->comm_broken = false;
     d->comm_broken_why.clear();
+    d->ctm = c2r_comm_timing{};
   }
   return 0;
 }
@@ -473,6 +772,7 @@ static int pass_slabs_one(c2r_ctx *d, bool own_sums, int first, int stride, int 
   for (int ns = first; ns <= d->nsrc; ns += stride) mine.push_back(ns);
   d->last_first = first;
   d->last_stride = stride;
+  if (comm_timing_prepare(d)) return 1;
   if (pass_list(d, mine, nslab)) return 1;
   d->slab_passes++;
   // C2R_FAULT_INJECT="rank:pass" (test hook): that rank returns from its pass-th slab-wise pass with an error, after its
@@ -496,8 +796,10 @@ static int pass_slabs_one(c2r_ctx *d, bool own_sums, int first, int stride, int 
     size_t off[4], len[4];
     const int nr = slab_ranges(d, c0, cnt, off, len);
     HIPCHK(d, hipStreamWaitEvent(d->comm_stream, d->ev_slab[sidx], 0));
+    if (sidx == 0 && comm_timing_mark(d, d, 1)) return 1;
     if (sum_ranges(d, nr, off, len)) return 1;
     HIPCHK(d, hipEventRecord(d->ev_sum[sidx], d->comm_stream));
+    if (sidx == n - 1 && comm_timing_mark(d, d, 2)) return 1;
     if (c2r_global_pass_cells(d, dt, c0, cnt, d->ev_sum[sidx])) return 1;
   }
   return 0;
@@ -526,11 +828,13 @@ static int pass_allreduce_chemistry_body(c2r_ctx *c, int first, int stride, int 
       for (c2r_ctx *d : dev) {
         HIPCHK(c, hipSetDevice(d->device));
         HIPCHK(c, hipStreamWaitEvent(d->comm_stream, d->ev_slab[sidx], 0));
+        if (sidx == 0 && comm_timing_mark(c, d, 1)) return 1;
       }
       if (sum_ranges(c, nr, off, len)) return 1;
       for (c2r_ctx *d : dev) {
         HIPCHK(c, hipSetDevice(d->device));
         HIPCHK(c, hipEventRecord(d->ev_sum[sidx], d->comm_stream));
+        if (sidx == n - 1 && comm_timing_mark(c, d, 2)) return 1;
         if (c2r_global_pass_cells(d, dt, c0, cnt, d->ev_sum[sidx])) { c->err = d->err; return 1; }
       }
     }
@@ -541,15 +845,22 @@ static int pass_allreduce_chemistry_body(c2r_ctx *c, int first, int stride, int 
     if (pass_finish(d)) { c->err = d->err; return 1; }
     HIPCHK(c, hipEventRecord(d->ev_comm_a, d->stream));
     HIPCHK(c, hipStreamWaitEvent(d->comm_stream, d->ev_comm_a, 0));
+    if (comm_timing_mark(c, d, 3)) return 1;
   }
   {
     const size_t off[1] = {4 * c->g.ncell}, len[1] = {(size_t)C2R_NFREQ + 1};
     if (sum_ranges(c, 1, off, len)) return 1;
   }
+  for (c2r_ctx *d : dev) {
+    HIPCHK(c, hipSetDevice(d->device));
+    if (comm_timing_mark(c, d, 4)) return 1;
+  }
   for (c2r_ctx *d : dev)
     if (fetch_summed_tail(d)) { c->err = d->err; return 1; }
   std::vector<int> conv((size_t)ndev, 0);
   if (on_all_devices(c, [&](c2r_ctx *d, int i) { return c2r_global_pass_finish(d, &conv[(size_t)i]); })) return 1;
+  for (c2r_ctx *d : dev)
+    if (comm_timing_read(c, d)) return 1;
   if (conv_flag) *conv_flag = conv[0];
   return 0;
 }

@@ -1427,6 +1427,16 @@ struct c2r_ctx {
   hipStream_t comm_stream = nullptr;
   hipEvent_t ev_comm_a = nullptr, ev_comm_b = nullptr;
   std::vector<hipEvent_t> ev_sum;  // slab s of the rate grids is summed over the ranks
+  // c2r_comm_selftest: per route {mismatches, lowest mismatching index} on the device, the pinned copy the host reads
+  // (4 counters, then `got` of either route as doubles), and the timing events of the two routes
+  unsigned long long *d_selftest = nullptr, *h_selftest = nullptr;
+  hipEvent_t ev_selftest[4] = {nullptr, nullptr, nullptr, nullptr};
+  // c2r_get_comm_timing: timing events recorded NEXT TO ev_slab / ev_sum while timing is on -- [0] every slab of rates
+  // complete (rates stream), [1] first slab's sum released, [2] last slab's sum complete, [3] tail's sum released,
+  // [4] tail's sum complete (comm stream)
+  hipEvent_t ev_ct[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  bool ct_rates_recorded = false;
+  c2r_comm_timing ctm{};
   hipStream_t stream = nullptr;
   Grid g{};
   std::string err;
@@ -1885,6 +1895,12 @@ extern "C" void c2r_destroy(c2r_ctx *c) {
   if (c->ev_comm_a) (void)hipEventDestroy(c->ev_comm_a);
   if (c->ev_comm_b) (void)hipEventDestroy(c->ev_comm_b);
   for (auto &ev : c->ev_sum) (void)hipEventDestroy(ev);
+  for (auto &ev : c->ev_selftest)
+    if (ev) (void)hipEventDestroy(ev);
+  for (auto &ev : c->ev_ct)
+    if (ev) (void)hipEventDestroy(ev);
+  if (c->d_selftest) (void)hipFree(c->d_selftest);
+  if (c->h_selftest) (void)hipHostFree(c->h_selftest);
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   for (auto &row : c->d_sed_tab)
     for (double *p : row)
@@ -3272,6 +3288,10 @@ static int launch_rates(const PassCtx &P, Batch &B, bool last_batch) {
   HIPCHK(c, hipGetLastError());
   c->tm.rates_launches++;
   if (c->timing) HIPCHK(c, hipEventRecord(B.ev[3], c->stream2));
+  if (c->timing && slabs && c->ev_ct[0]) { // c2r_get_comm_timing: this device's last slab of rates is complete
+    HIPCHK(c, hipEventRecord(c->ev_ct[0], c->stream2));
+    c->ct_rates_recorded = true;
+  }
   return 0;
 }
 
@@ -3353,6 +3373,7 @@ static int pass_list(c2r_ctx *c, const std::vector<int> &mine, int nslab = 0) {
   c->tm.sweep_launches = c->tm.rates_launches = 0;
   c->tm.cells_swept = 0;
   c->ev_used = 0;
+  c->ct_rates_recorded = false;
   // every pass is closed by pass_finish, which adds the batches' kept losses into photon_loss / sum_nbox and empties
   // this list; entries still here belong to a pass that ended in an error and must not be added to this one
   c->tails.clear();
@@ -3413,8 +3434,13 @@ static int pass_list(c2r_ctx *c, const std::vector<int> &mine, int nslab = 0) {
   }
   if (!P.transposed_seen) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_transposed, 0));
   // a rank without sources of its own still owes the caller its slab events
-  if (mine.empty())
+  if (mine.empty()) {
     for (int sidx = 0; sidx < P.nslab; sidx++) HIPCHK(c, hipEventRecord(c->ev_slab[sidx], c->stream2));
+    if (c->timing && P.nslab > 0 && c->ev_ct[0]) {
+      HIPCHK(c, hipEventRecord(c->ev_ct[0], c->stream2));
+      c->ct_rates_recorded = true;
+    }
+  }
   c->pass_tev = P.tev;
   c->pass_open = true;
   c->pass_slabs = P.nslab;

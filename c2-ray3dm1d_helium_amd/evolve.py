@@ -206,6 +206,27 @@ class HipEngine:
     def allreduce_rates(self):
         self._chk(self.lib.c2r_allreduce_rates(self.h))
 
+    def comm_selftest(self, nslab=4):
+        """c2r_comm_selftest: a known pattern summed over the ranks through the context's own buffer, communicators and
+        streams, over both routes a run takes (collective: every rank calls it).  Returns the report as a dict; raises
+        C2RayHipError, with the report attached as `.report`, when a sum came back wrong or the transport failed."""
+        rep = _lib.CommSelftestReport()
+        rc = self.lib.c2r_comm_selftest(self.h, int(nslab), C.byref(rep))
+        out = {k: getattr(rep, k) for k in ("ranks", "kind", "devices", "bad_route", "bad_rank", "bad_index", "got", "expected")}
+        for k in ("elements", "mismatches", "ms"):
+            out[k] = list(getattr(rep, k))
+        if rc != 0:
+            err = C2RayHipError(self.lib.c2r_last_error(self.h).decode())
+            err.report = out
+            raise err
+        return out
+
+    def comm_timing(self, idev=None):
+        """c2r_get_comm_timing of device idev (None: the first) as a dict: the sum over ranks of the last fused iteration."""
+        t = _lib.CommTiming()
+        self._chk(self.lib.c2r_get_comm_timing(self.h, 0 if idev is None else int(idev), C.byref(t)))
+        return {k: getattr(t, k) for k in ("slabs", "allreduce_ms", "allreduce_exposed_ms", "tail_ms")}
+
     def pass_allreduce_chemistry(self, dt, first=1, stride=1, nslab=4):
         """pass_all_sources + sum over ranks + global pass of one outer iteration, overlapped slab by slab;
         returns the non-converged count."""

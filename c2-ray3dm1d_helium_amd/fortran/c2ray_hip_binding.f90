@@ -28,6 +28,23 @@ module c2ray_hip
      real(c_double) :: reccoef(12)
   end type c2r_iteration_report
 
+  !> c2r_comm_selftest_report of include/c2ray_hip.h: what the self-test of the sum over ranks found
+  type, bind(C) :: c2r_comm_selftest_report
+     integer(c_int) :: ranks, kind, devices
+     integer(c_long_long) :: elements(2)
+     integer(c_long_long) :: mismatches(2)
+     integer(c_int) :: bad_route, bad_rank
+     integer(c_long_long) :: bad_index
+     real(c_double) :: got, expected
+     real(c_double) :: ms(2)
+  end type c2r_comm_selftest_report
+
+  !> c2r_comm_timing of include/c2ray_hip.h: the sum over ranks of the last fused iteration on one device
+  type, bind(C) :: c2r_comm_timing
+     integer(c_int) :: slabs
+     real(c_double) :: allreduce_ms, allreduce_exposed_ms, tail_ms
+  end type c2r_comm_timing
+
   !> c2r_sed_setup of include/c2ray_hip.h: what spec_integration starts from for one SED
   type, bind(C) :: c2r_sed_setup
      integer(c_int) :: nfreq, sed
@@ -508,6 +525,21 @@ module c2ray_hip
        type(c_ptr), value :: ctx
        type(c2r_timing), intent(out) :: tm
      end function c2r_get_timing
+
+     !> collective: every rank of the communicator calls it (see the header for what a pass proves)
+     integer(c_int) function c2r_comm_selftest(ctx, nslab, report) bind(C, name="c2r_comm_selftest")
+       import :: c_int, c_ptr, c2r_comm_selftest_report
+       type(c_ptr), value :: ctx
+       integer(c_int), value :: nslab
+       type(c2r_comm_selftest_report), intent(out) :: report
+     end function c2r_comm_selftest
+
+     integer(c_int) function c2r_get_comm_timing(ctx, idev, tm) bind(C, name="c2r_get_comm_timing")
+       import :: c_int, c_ptr, c2r_comm_timing
+       type(c_ptr), value :: ctx
+       integer(c_int), value :: idev
+       type(c2r_comm_timing), intent(out) :: tm
+     end function c2r_get_comm_timing
 
   end interface
 

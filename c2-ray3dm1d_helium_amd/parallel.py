@@ -187,6 +187,23 @@ class RcclComm:
             os._exit(3)
         return out["err"]
 
+    def selftest(self, nslab=4):
+        """c2r_comm_selftest on every rank, then one agreement over `dist` (as the constructor's agree()): every rank
+        returns its own report, or every rank raises the first failing rank's text.  The library's verdict is local to a
+        process -- a wrong transport need not be wrong everywhere, and is not asked to carry the news about itself."""
+        report, err = None, None
+        try:
+            report = self.engine.comm_selftest(nslab)
+        except Exception as ex:  # noqa: BLE001 -- travels to the other ranks
+            err = str(ex)
+        if self.dist is not None and self.size > 1:
+            errs = [None] * self.size
+            self.dist.all_gather_object(errs, err)
+            err = next((f"rank {r}: {e}" for r, e in enumerate(errs) if e is not None), None)
+        if err is not None:
+            raise RuntimeError(f"comm self-test failed: {err}")
+        return report
+
     def allreduce_rates(self, engine=None):
         self.engine.allreduce_rates()
 
@@ -210,6 +227,10 @@ class LocalComm:
     def __init__(self, engine):
         self.engine = engine
         self.size = 1        # ranks of THIS host loop: the split over the devices is the library's
+
+    def selftest(self, nslab=4):
+        """c2r_comm_selftest over the devices of the context; returns the report or raises."""
+        return self.engine.comm_selftest(nslab)
 
     def allreduce_rates(self, engine=None):
         self.engine.allreduce_rates()

@@ -303,6 +303,60 @@ int c2r_allreduce_rates(c2r_ctx *ctx);
  * its sum is complete.  conv_flag: non-converged cells (evolve.F90:488). */
 int c2r_pass_allreduce_chemistry(c2r_ctx *ctx, int first, int stride, int nslab, double dt, int *conv_flag);
 
+/* Self-test of the sum over ranks: a collective call (every rank of the communicator makes it, like
+ * c2r_allreduce_rates).  A known pattern is summed through the context's own reduction buffer (the one given to
+ * c2r_set_rates_buffer, if any), communicators, comm streams and events, by the routines the production calls use,
+ * over both routes a run takes:
+ *   route 0, as c2r_allreduce_rates: the whole buffer (c2r_rates_count doubles) in one all-reduce;
+ *   route 1, as c2r_pass_allreduce_chemistry: nslab slabs of k-planes (an even split; production boundaries depend
+ *            on the sources), each slab's 3 or 4 component ranges in one grouped launch, then the 48-double tail.
+ * The pattern, for position i of the buffer and rank r (0-based) of n:
+ *   h = splitmix64(i)   (z = i + 0x9E3779B97F4A7C15; z = (z ^ z>>30) * 0xBF58476D1CE4E5B9;
+ *                        z = (z ^ z>>27) * 0x94D049BB133111EB; h = z ^ z>>31)
+ *   a(i) = (2^29 + (h mod 2^29)) | 1      e(i) = ((h >> 32) mod 121) - 60
+ *   v(r, i) = (r + 1) a(i) 2^e(i)         expected(i) = n (n + 1) / 2 a(i) 2^e(i)
+ * Every partial sum is an integer below 2^53 times one power of two, so the sum is exact in every association for
+ * n <= 4095 (more ranks are refused) and the check is == on the value.  a(i) is odd with 30 significant bits: a
+ * transport that reduces through fp32 cannot produce it; a rank left out, added twice or left un-reduced changes
+ * the sum by a non-zero multiple of a(i); a and e vary with i, so a range that lands at a wrong offset is seen.
+ * WHAT A PASS PROVES: the sums the transport returned for this buffer, these offsets, these message sizes and this
+ * grouping were exact, on this process's devices, at the time of the call.  WHAT IT DOES NOT: performance, corruption
+ * that happens later, or anything about a transport it was not run on.  The verdict is local to the process (a wrong
+ * transport need not be wrong on every rank); agreeing about it is the launcher's business.
+ * Allowed wherever c2r_set_rates_to_zero is allowed, and on a context fresh from c2r_create + c2r_comm_init*; it has
+ * c2r_set_rates_to_zero's effect on the rate grids, photon_loss / sum_nbox of c2r_get_loss stay what they were.
+ * One-device context without communicator: returns 0 with ranks = 1 and nothing checked.  A mismatch or a transport
+ * error: non-zero return, the report is filled in all the same, the error text names route, rank, device, index, got,
+ * expected, the mismatch count and c2r_comm_library's path, and -- as after any other error inside a collective phase
+ * -- the RCCL communicators of the context are aborted.  Both routes always run to their end (unless the transport
+ * itself returns an error), so that no peer waits for a rank that gave up half-way.
+ * Environment: C2R_COMM_SELFTEST=1 makes c2r_comm_init and c2r_comm_init_local run it (nslab from
+ * C2R_ALLREDUCE_SLABS, default 4) once the communicators exist: a failure fails the init call with the self-test's
+ * text and leaves the context without communicator, a pass prints one "comm self-test ok" line on stderr. */
+typedef struct {
+  int ranks, kind, devices;      /* c2r_comm_nranks, c2r_comm_kind, devices of this context that were checked */
+  long long elements[2];         /* doubles summed and compared per device: [0] whole-buffer route, [1] slab-wise route */
+  long long mismatches[2];       /* over all devices of this context */
+  int bad_route, bad_rank;       /* the first mismatch: lowest route, then lowest rank, then lowest index; -1: none */
+  long long bad_index;           /* position in the reduction buffer */
+  double got, expected;
+  double ms[2];                  /* per route, event-timed on the first device: fill queued -> check complete */
+} c2r_comm_selftest_report;
+int c2r_comm_selftest(c2r_ctx *ctx, int nslab, c2r_comm_selftest_report *report);
+
+/* Timings of the sum over ranks of the last c2r_pass_allreduce_chemistry on device idev (0 .. c2r_num_devices-1),
+ * filled only while c2r_enable_timing(ctx, 1) is on (all zero otherwise, and for a context without communicator).
+ * allreduce_exposed_ms is what the sum costs the iteration: after a device's last slab of rates nothing of its own is
+ * left to hide the wire behind but the chemistry of earlier slabs. */
+typedef struct {
+  int slabs;                    /* slabs of the last slab-wise pass on this device; 0: none yet, or no communicator */
+  double allreduce_ms;          /* comm stream: first slab's sum released -> tail's sum complete */
+  double allreduce_exposed_ms;  /* this device's LAST slab of rates complete (or the first sum released, if that came
+                                   later: until then the device waited for the host, not the wire) -> that slab's sum complete */
+  double tail_ms;               /* the 48-double tail's sum alone */
+} c2r_comm_timing;
+int c2r_get_comm_timing(c2r_ctx *ctx, int idev, c2r_comm_timing *out);
+
 /* evolve0D(dt,rtpos,ns,niter) (files_for_3D/evolve_point.F90:79-319) for ONE cell, for hosts that drive the sweep
  * themselves, cell by cell, as the reference's do_source does through evolve2D / evolve1D_axis / evolve2D_plane /
  * evolve3D_quadrant (files_for_3D/evolve_source.F90:244-608): the incoming columns of the cell at mesh position rtpos
