@@ -61,11 +61,24 @@ struct SrcDev {
   int loss_lo;         // >= 0: the rates launch leaves, for every surface cell of the final sub-box in shells >= loss_lo,
                        // the photons that leave the box through it in the cell's N_in(HI) slot (k_loss_stored adds
                        // them up); -1: no such request (set before the rates launch)
+  int rl[3], rr[3];    // open boundaries only: the source's reach, -min(max_subbox, srcpos - 1) and min(max_subbox, mesh - srcpos)
+                       // (the else branch of evolve_source.F90:103-109); the periodic kernels never read them
 };
 // the sub-box of the round in flight: the same for every active source of a batch (all are in the same round)
 struct Box {
   int lo[3], hi[3];
 };
+// Open (non-periodic) boundaries: nothing wraps, so a source's sub-box is the round's box cut at the source's own reach,
+// and it differs from source to source within a round.  OPEN is a template parameter of every kernel that looks at a
+// box: the periodic instantiations are the code they were before the open ones existed.
+__device__ __forceinline__ Box source_box(const Box &box, const SrcDev &S) {
+  Box b;
+  for (int d = 0; d < 3; d++) {
+    b.lo[d] = box.lo[d] > S.rl[d] ? box.lo[d] : S.rl[d];
+    b.hi[d] = box.hi[d] < S.rr[d] ? box.hi[d] : S.rr[d];
+  }
+  return b;
+}
 
 struct StepScalars {
   double dr1, dr2, dr3, vol;
@@ -86,6 +99,24 @@ __device__ __forceinline__ int wrap0(int x, int n) { // 0-based periodic index o
   const unsigned a = u + m, b = u - m;
   const unsigned lo = a < b ? a : b;
   return (int)(u < lo ? u : lo);
+}
+
+// 0-based mesh index of the cell at offset x from the origin: periodic, or as it is (open boundaries: a cell of a source's
+// box lies in the mesh)
+template <bool OPEN>
+__device__ __forceinline__ int mesh0(int x, int n) { return OPEN ? x : wrap0(x, n); }
+
+// Does a surface cell of the sub-box `b` count?  Periodic boundaries, and the loss that is KEPT (photon_loss) in open
+// ones: every cell with a coordinate on a face.  The loss that DECIDES whether an open box grows once more (movable_only):
+// only cells on a face still short of the source's reach -- photons that leave through a mesh face are lost whatever the
+// box does and must not make a source next to an edge sweep the whole mesh.  This replaces the while-test of
+// evolve_source.F90:136-139, which looks at z only and is wrong without periodicity.
+template <bool OPEN>
+__device__ __forceinline__ bool on_counted_face(const Box &b, const SrcDev &S, int di, int dj, int dk, int movable_only) {
+  if (OPEN && movable_only)
+    return (di == b.lo[0] && b.lo[0] > S.rl[0]) || (dj == b.lo[1] && b.lo[1] > S.rl[1]) || (dk == b.lo[2] && b.lo[2] > S.rl[2]) ||
+           (di == b.hi[0] && b.hi[0] < S.rr[0]) || (dj == b.hi[1] && b.hi[1] < S.rr[1]) || (dk == b.hi[2] && b.hi[2] < S.rr[2]);
+  return di == b.lo[0] || dj == b.lo[1] || dk == b.lo[2] || di == b.hi[0] || dj == b.hi[1] || dk == b.hi[2];
 }
 
 __device__ __forceinline__ double block_sum(double x, double *sh) {
@@ -208,14 +239,19 @@ k_transpose_packed(Grid g, const double *__restrict__ packed, double *__restrict
 // sample = 1, and only such full sums are ever kept.
 // (Inside k_sweep_shell this work sat in a sixteenth of the waves, all of them on two of the eight XCDs: the
 // last shell of every round took twice as long as its neighbours.  Here every lane of every wave has a cell.)
+// OPEN: `box` is the round's box before it is cut at each source's reach; MOVABLE: the sum that decides (on_counted_face).
+template <bool OPEN, bool MOVABLE>
 __global__ void __launch_bounds__(BLOCK)
-k_loss(Grid g, const SrcDev *__restrict__ src, const int *__restrict__ list, int multi, int s_lo, int s_hi, Box box,
+k_loss(Grid g, const SrcDev *__restrict__ src, const int *__restrict__ list, int multi, int s_lo, int s_hi, Box box_,
        StepScalars sc, const BandData *__restrict__ bd, SedSet ss,
        const int *__restrict__ block_base, double *__restrict__ loss_partial, int pitch, int sample, int first_block) {
   // first_block: the blocks before it hold no surface cell (the host has set their partials to zero and does not
   // launch them); block numbers, and with them the order of the sum, stay what they are
   __shared__ double sh[BLOCK / 64];
   const SrcDev &S = src[list[blockIdx.y]];
+  Box cut_;
+  if constexpr (OPEN) cut_ = source_box(box_, S);
+  const Box &box = OPEN ? cut_ : box_; // (periodic: the launch's box itself)
   const int bx = first_block + (int)blockIdx.x;
   const int B = block_base[s_lo] + bx * sample;
   int lo = s_lo, hi = s_hi; // largest shell with block_base[shell] <= B
@@ -232,8 +268,7 @@ k_loss(Grid g, const SrcDev *__restrict__ src, const int *__restrict__ list, int
     shell_decode(shell, (int)t, di, dj, dk);
     const bool inside = di >= box.lo[0] && di <= box.hi[0] && dj >= box.lo[1] && dj <= box.hi[1] && dk >= box.lo[2] &&
                         dk <= box.hi[2];
-    const bool boundary = di == box.lo[0] || dj == box.lo[1] || dk == box.lo[2] || di == box.hi[0] || dj == box.hi[1] ||
-                          dk == box.hi[2];
+    const bool boundary = on_counted_face<OPEN>(box, S, di, dj, dk, MOVABLE ? 1 : 0);
     if (inside && boundary) {
       const size_t cz = S.cz;
       const size_t p = (size_t)shell_offset(shell) + (size_t)t;
@@ -274,11 +309,16 @@ k_loss(Grid g, const SrcDev *__restrict__ src, const int *__restrict__ list, int
 // So k_rates stores them (SrcDev::loss_lo) in the cell's N_in(HI) slot of the column block, which nobody reads
 // after it, and this kernel adds them up with k_loss's thread <-> cell map, block partials and block order: the
 // same bits as k_loss gives, without evaluating a single band a second time.
+// (OPEN: the kept loss of an open box runs over its whole surface, mesh faces included, and over all its shells.)
+template <bool OPEN>
 __global__ void __launch_bounds__(BLOCK)
-k_loss_stored(Grid g, const SrcDev *__restrict__ src, const int *__restrict__ list, int s_lo, int s_hi, Box box,
+k_loss_stored(Grid g, const SrcDev *__restrict__ src, const int *__restrict__ list, int s_lo, int s_hi, Box box_,
               const int *__restrict__ block_base, double *__restrict__ loss_partial, int pitch, int first_block) {
   __shared__ double sh[BLOCK / 64];
   const SrcDev &S = src[list[blockIdx.y]];
+  Box cut_;
+  if constexpr (OPEN) cut_ = source_box(box_, S);
+  const Box &box = OPEN ? cut_ : box_; // (periodic: the launch's box itself)
   const int bx = first_block + (int)blockIdx.x;
   const int B = block_base[s_lo] + bx;
   int lo = s_lo, hi = s_hi; // largest shell with block_base[shell] <= B
@@ -295,8 +335,7 @@ k_loss_stored(Grid g, const SrcDev *__restrict__ src, const int *__restrict__ li
     shell_decode(shell, (int)t, di, dj, dk);
     const bool inside = di >= box.lo[0] && di <= box.hi[0] && dj >= box.lo[1] && dj <= box.hi[1] && dk >= box.lo[2] &&
                         dk <= box.hi[2];
-    const bool boundary = di == box.lo[0] || dj == box.lo[1] || dk == box.lo[2] || di == box.hi[0] || dj == box.hi[1] ||
-                          dk == box.hi[2];
+    const bool boundary = on_counted_face<OPEN>(box, S, di, dj, dk, 0);
     if (inside && boundary) {
       const size_t p = (size_t)shell_offset(shell) + (size_t)t;
       loss = ((const global_double *)S.cols)[col_in(p, 0, S.cz)];
@@ -356,18 +395,25 @@ __device__ __forceinline__ void sweep_cell_state(const SweepArgs &A, int i, int 
 
 // evolve0D's column part (files_for_3D/evolve_point.F90:114-168, :237-244) for cell t of shell `shell` around source
 // S, any shell: cinterp through the general short_characteristic / shell_position
+// OPEN: the round's box cut at the source's reach, no modulo: a shell cell outside the reach does not exist, and the
+// upstream cells of a cell in the mesh lie in the mesh (corners of weight exactly 0 may be read from a slot that was
+// never written: finite, as everything in the arena).
+template <bool OPEN>
 __device__ __forceinline__ void sweep_cell(const SweepArgs &A, const SrcDev &S, int shell, int t) {
   const Grid &g = A.g;
   const StepScalars &sc = A.sc;
   int di, dj, dk;
   shell_decode(shell, t, di, dj, dk);
-  const bool inside = di >= A.box.lo[0] && di <= A.box.hi[0] && dj >= A.box.lo[1] && dj <= A.box.hi[1] && dk >= A.box.lo[2] &&
-                      dk <= A.box.hi[2];
+  Box cut_;
+  if constexpr (OPEN) cut_ = source_box(A.box, S);
+  const Box &box = OPEN ? cut_ : A.box; // (periodic: the launch's box itself)
+  const bool inside = di >= box.lo[0] && di <= box.hi[0] && dj >= box.lo[1] && dj <= box.hi[1] && dk >= box.lo[2] &&
+                      dk <= box.hi[2];
   if (!inside) return;
   const size_t cz = S.cz;
   const size_t p = (size_t)shell_offset(shell) + (size_t)t;
   global_double *cs = (global_double *)S.cols;
-  const int i = wrap0(S.i0 - 1 + di, g.n1), j = wrap0(S.j0 - 1 + dj, g.n2), k = wrap0(S.k0 - 1 + dk, g.n3);
+  const int i = mesh0<OPEN>(S.i0 - 1 + di, g.n1), j = mesh0<OPEN>(S.j0 - 1 + dj, g.n2), k = mesh0<OPEN>(S.k0 - 1 + dk, g.n3);
   const int w_ = 2 * shell + 1;
   double u_HI, u_HeI, u_HeII;
   sweep_cell_state(A, i, j, k, shell > 0 && t >= 2 * w_ * w_ + 2 * (w_ - 2) * w_, u_HI, u_HeI, u_HeII);
@@ -410,18 +456,22 @@ __device__ __forceinline__ void sweep_cell(const SweepArgs &A, const SrcDev &S, 
 // (corners of weight exactly 0 on the edges of a face are read from the nearest cell of shell s-1).  Bit for bit
 // the columns of sweep_cell (tests/test_gpu_parity.py::test_fast_sweep_equals_the_general_sweep runs that one for every
 // shell, C2R_SWEEP_GENERIC=1, in a process of its own and compares the columns).
+template <bool OPEN>
 __device__ __forceinline__ void sweep_cell_fast(const SweepArgs &A, const SrcDev &S, const ShellGeom &G, int t) {
   const Grid &g = A.g;
   const StepScalars &sc = A.sc;
   int di, dj, dk;
   const int face = shell_decode_fast(G, t, di, dj, dk);
-  const bool inside = di >= A.box.lo[0] && di <= A.box.hi[0] && dj >= A.box.lo[1] && dj <= A.box.hi[1] && dk >= A.box.lo[2] &&
-                      dk <= A.box.hi[2];
+  Box cut_;
+  if constexpr (OPEN) cut_ = source_box(A.box, S);
+  const Box &box = OPEN ? cut_ : A.box; // (periodic: the launch's box itself)
+  const bool inside = di >= box.lo[0] && di <= box.hi[0] && dj >= box.lo[1] && dj <= box.hi[1] && dk >= box.lo[2] &&
+                      dk <= box.hi[2];
   if (!inside) return;
   const size_t cz = S.cz;
   const size_t p = (size_t)G.off + (size_t)t;
   global_double *cs = (global_double *)S.cols;
-  const int i = wrap0(S.i0 - 1 + di, g.n1), j = wrap0(S.j0 - 1 + dj, g.n2), k = wrap0(S.k0 - 1 + dk, g.n3);
+  const int i = mesh0<OPEN>(S.i0 - 1 + di, g.n1), j = mesh0<OPEN>(S.j0 - 1 + dj, g.n2), k = mesh0<OPEN>(S.k0 - 1 + dk, g.n3);
   double u_HI, u_HeI, u_HeII;
   sweep_cell_state(A, i, j, k, face == 2, u_HI, u_HeI, u_HeII);
   ShellCorners c4;
@@ -463,16 +513,20 @@ __device__ __forceinline__ int sweep_block_cell(int cnt) {
   return t < cnt ? t : -1;
 }
 
+// (OPEN: up to 7/8 of the threads of a corner source's shell lie outside its reach; they leave after the decode and the
+// box test, before any memory access.)
+template <bool OPEN>
 __global__ void __launch_bounds__(BLOCK, C2R_SWEEP_WAVES)
 k_sweep_shell(SweepArgs A, const SrcDev *__restrict__ src, const int *__restrict__ active, int shell) {
   const int t = sweep_block_cell((int)shell_count(shell));
-  if (t >= 0) sweep_cell(A, src[active[blockIdx.y]], shell, t);
+  if (t >= 0) sweep_cell<OPEN>(A, src[active[blockIdx.y]], shell, t);
 }
 
+template <bool OPEN>
 __global__ void __launch_bounds__(BLOCK, C2R_SWEEP_WAVES)
 k_sweep_shell_fast(SweepArgs A, const SrcDev *__restrict__ src, const int *__restrict__ active, ShellGeom G) {
   const int t = sweep_block_cell(24 * G.s * G.s + 2);
-  if (t >= 0) sweep_cell_fast(A, src[active[blockIdx.y]], G, t);
+  if (t >= 0) sweep_cell_fast<OPEN>(A, src[active[blockIdx.y]], G, t);
 }
 
 // photon_loss_src_thread(tn) += ... (evolve_point.F90:312): sum the block partials of all shells of
@@ -506,6 +560,8 @@ struct ProbeRound {
   int partial_off;  // first partial sum of the round (nblk per source)
   int acc_off;      // first result of the round (one per source)
 };
+// (OPEN: a bound of the sum that decides -- the box of each source, the faces that can still move.)
+template <bool OPEN>
 __global__ void __launch_bounds__(BLOCK)
 k_loss_probe_rounds(Grid g, const SrcDev *__restrict__ src, const int *__restrict__ lists, const ProbeRound *__restrict__ rounds,
                     int multi, StepScalars sc, const BandData *__restrict__ bd, SedSet ss, const int *__restrict__ block_base,
@@ -514,6 +570,9 @@ k_loss_probe_rounds(Grid g, const SrcDev *__restrict__ src, const int *__restric
   const ProbeRound &R = rounds[blockIdx.z];
   if ((int)blockIdx.x >= R.nblk || (int)blockIdx.y >= R.nact) return; // uniform per block
   const SrcDev &S = src[lists[R.list_off + blockIdx.y]];
+  Box cut_;
+  if constexpr (OPEN) cut_ = source_box(R.box, S);
+  const Box &box = OPEN ? cut_ : R.box; // (periodic: the launch's box itself)
   const int s_lo = R.s_lo, s_hi = R.s_hi;
   // every sample-th block counted from the END of the round (the surface of a box is mostly its outermost shell)
   const int B = block_base[s_hi + 1] - 1 - (int)blockIdx.x * sample;
@@ -530,10 +589,9 @@ k_loss_probe_rounds(Grid g, const SrcDev *__restrict__ src, const int *__restric
   if (t < cnt) {
     int di, dj, dk;
     shell_decode(shell, (int)t, di, dj, dk);
-    const bool inside = di >= R.box.lo[0] && di <= R.box.hi[0] && dj >= R.box.lo[1] && dj <= R.box.hi[1] && dk >= R.box.lo[2] &&
-                        dk <= R.box.hi[2];
-    const bool boundary = di == R.box.lo[0] || dj == R.box.lo[1] || dk == R.box.lo[2] || di == R.box.hi[0] || dj == R.box.hi[1] ||
-                          dk == R.box.hi[2];
+    const bool inside = di >= box.lo[0] && di <= box.hi[0] && dj >= box.lo[1] && dj <= box.hi[1] && dk >= box.lo[2] &&
+                        dk <= box.hi[2];
+    const bool boundary = on_counted_face<OPEN>(box, S, di, dj, dk, 1);
     if (inside && boundary) {
       const size_t cz = S.cz;
       const size_t p = (size_t)shell_offset(shell) + (size_t)t;
@@ -578,13 +636,18 @@ k_loss_finish_rounds(const ProbeRound *__restrict__ rounds, const double *__rest
 }
 
 // columns of one slot from shell order back to mesh order (diagnostic download only)
+template <bool OPEN>
 __global__ void __launch_bounds__(BLOCK)
 k_col_to_grid(Grid g, SrcDev S, const double *__restrict__ cs, double *__restrict__ out) {
   const size_t q = (size_t)blockIdx.x * BLOCK + threadIdx.x;
   if (q >= g.ncell) return;
   const int i = (int)(q % g.n1), j = (int)((q / g.n1) % g.n2), k = (int)(q / ((size_t)g.n1 * g.n2));
-  const int di = wrap0(i + 1 - S.i0 + g.l1, g.n1) - g.l1, dj = wrap0(j + 1 - S.j0 + g.l2, g.n2) - g.l2,
-            dk = wrap0(k + 1 - S.k0 + g.l3, g.n3) - g.l3;
+  int di = i + 1 - S.i0, dj = j + 1 - S.j0, dk = k + 1 - S.k0;
+  if constexpr (!OPEN) {
+    di = wrap0(di + g.l1, g.n1) - g.l1;
+    dj = wrap0(dj + g.l2, g.n2) - g.l2;
+    dk = wrap0(dk + g.l3, g.n3) - g.l3;
+  }
   const bool inside = di >= S.lo[0] && di <= S.hi[0] && dj >= S.lo[1] && dj <= S.hi[1] && dk >= S.lo[2] && dk <= S.hi[2];
   const size_t p = shell_position(di, dj, dk);
   for (int c = 0; c < 3; c++) out[q + c * g.ncell] = inside ? cs[col_out(p, c, S.cz)] : 0.0;
@@ -609,7 +672,10 @@ k_col_to_grid(Grid g, SrcDev S, const double *__restrict__ cs, double *__restric
 #ifndef C2R_RATES_WAVES_HEAT_MULTI
 #define C2R_RATES_WAVES_HEAT_MULTI 4
 #endif
-template <bool HEAT, bool MULTI>
+// OPEN (open boundaries): the offset of a cell from a source is what it is, no modulo; the final sub-box and the surface
+// test come from S.lo / S.hi as they always did.  Instantiations of their own: the periodic kernels have no issue slot
+// to spare and stay the code they were.
+template <bool HEAT, bool MULTI, bool OPEN = false>
 __global__ void __launch_bounds__(BLOCK, MULTI ? (HEAT ? C2R_RATES_WAVES_HEAT_MULTI : 4) : (HEAT ? C2R_RATES_WAVES_HEAT : C2R_RATES_WAVES_ISO))
 k_rates(Grid g, const SrcDev *__restrict__ src, int nsrc, StepScalars sc, const double *__restrict__ ndens,
         const double *__restrict__ xh_av, const double *__restrict__ xhe_av,
@@ -714,9 +780,11 @@ k_rates(Grid g, const SrcDev *__restrict__ src, int nsrc, StepScalars sc, const 
     const SrcDev &S = src[tile_ptr ? tile_src[e] : e];
     // unwrapped offset rtpos - srcpos in [-mesh/2, mesh - mesh/2 - 1]
     int di = i + 1 - S.i0, dj = j + 1 - S.j0, dk = k + 1 - S.k0;
-    di = wrap0(di + g.l1, g.n1) - g.l1;
-    dj = wrap0(dj + g.l2, g.n2) - g.l2;
-    dk = wrap0(dk + g.l3, g.n3) - g.l3;
+    if constexpr (!OPEN) {
+      di = wrap0(di + g.l1, g.n1) - g.l1;
+      dj = wrap0(dj + g.l2, g.n2) - g.l2;
+      dk = wrap0(dk + g.l3, g.n3) - g.l3;
+    }
     // Cells outside the source's last sub-box were never traced (evolve_source.F90:136-144): no
     // contribution.  (The reference's own marker is coldensh_out == 0, evolve_point.F90:120; every cell
     // of the box is traced exactly once, so "inside the box" is the same set and needs no zeroing.)
@@ -1265,7 +1333,7 @@ k_stat_finish(const double *__restrict__ partial, int nblocks, double *__restric
 
 // evolve0D for one cell and one source (c2r_evolve0d): the column part (sweep_cell) and the rates part (as k_rates
 // for one source) in one thread, the loss through the cell if the caller says it lies on its sub-box's surface.
-template <bool HEAT, bool MULTI>
+template <bool HEAT, bool MULTI, bool OPEN = false>
 __global__ void __launch_bounds__(64)
 k_evolve0d(SweepArgs A, SrcDev S, int di, int dj, int dk, const BandData *__restrict__ bd, SedSet ss, double *__restrict__ rates,
            double *__restrict__ loss_out) {
@@ -1275,13 +1343,13 @@ k_evolve0d(SweepArgs A, SrcDev S, int di, int dj, int dk, const BandData *__rest
   const int ia = di < 0 ? -di : di, ja = dj < 0 ? -dj : dj, ka = dk < 0 ? -dk : dk;
   const int shell = ia > ja ? (ia > ka ? ia : ka) : (ja > ka ? ja : ka);
   const size_t p = shell_position(di, dj, dk);
-  sweep_cell(A, S, shell, (int)(p - (size_t)shell_offset(shell)));
+  sweep_cell<OPEN>(A, S, shell, (int)(p - (size_t)shell_offset(shell)));
   __threadfence_block();
   const global_double *cs = (const global_double *)S.cols;
   const size_t cz = S.cz;
   const double cin_HI = cs[col_in(p, 0, cz)], cin_HeI = cs[col_in(p, 1, cz)], cin_HeII = cs[col_in(p, 2, cz)];
   const double cout_HI = cs[col_out(p, 0, cz)], cout_HeI = cs[col_out(p, 1, cz)], cout_HeII = cs[col_out(p, 2, cz)];
-  const int i = wrap0(S.i0 - 1 + di, g.n1), j = wrap0(S.j0 - 1 + dj, g.n2), k = wrap0(S.k0 - 1 + dk, g.n3);
+  const int i = mesh0<OPEN>(S.i0 - 1 + di, g.n1), j = mesh0<OPEN>(S.j0 - 1 + dj, g.n2), k = mesh0<OPEN>(S.k0 - 1 + dk, g.n3);
   const size_t q = (size_t)i + (size_t)g.n1 * ((size_t)j + (size_t)g.n2 * (size_t)k);
   const double nd = A.ndens[q];
   const double h0 = dmax(A.xh_av[q], epsilon), h1 = dmax(A.xh_av[q + nc], epsilon);
@@ -1484,6 +1552,7 @@ struct c2r_ctx {
   size_t rates_count = 0;
 
   int batch = 256;                 // most sources per batch (c2r_set_batch); the scratch arena may allow fewer
+  bool periodic = true;            // mesh boundaries (c2r_set_boundaries): periodic as the reference, or open (nothing wraps)
   // Column scratch: per ping-pong set a list of segments; a source's block is cut from the current segment of
   // its set (shell-ordered arrays are prefixes of one another, so a block that turns out too small moves to a
   // deeper one by six copies).  A set that runs out of room gets another segment -- nothing that exists moves, no
@@ -1775,6 +1844,24 @@ static int ensure_pair(c2r_ctx *c, T **d, T **h, size_t *cap, size_t need) {
   return 0;
 }
 
+// What follows from the largest shell a source of this mesh can reach: mesh/2 with periodic boundaries
+// (evolve_source.F90:105), mesh - 1 with open ones (a source in a corner, :107-108).  Host side only; the device copies
+// are made by the caller.
+static void shell_bookkeeping(c2r_ctx *c) {
+  Grid &g = c->g;
+  g.smax = c->periodic ? std::max(g.l1, std::max(g.l2, g.l3)) : std::min(MAX_SUBBOX, std::max(g.n1, std::max(g.n2, g.n3)) - 1);
+  g.colsize = (size_t)(2 * g.smax + 1) * (2 * g.smax + 1) * (2 * g.smax + 1);
+  // block bookkeeping of the shells 0..smax
+  c->block_base.assign(g.smax + 2, 0);
+  for (int s = 0; s <= g.smax; s++)
+    c->block_base[s + 1] = c->block_base[s] + (int)((shell_count(s) + BLOCK - 1) / BLOCK);
+  c->blocks_total = c->block_base[g.smax + 1];
+  c->shell_geom.clear();
+  for (int s = 0; s <= g.smax; s++) c->shell_geom.push_back(shell_geometry(s));
+  // active lists of all rounds of a batch, one after another (two per round at most, plus the final losses)
+  c->list_cap = (size_t)(2 * (g.smax / SUBBOXSIZE + 2) + 4) * BATCH_MAX;
+}
+
 extern "C" int c2r_create(c2r_ctx **out, int device, const int mesh[3]) {
   if (!out || !mesh) return fail(nullptr, "c2r_create: null argument");
   if (mesh[0] < 2 || mesh[1] < 2 || mesh[2] < 2 || mesh[0] > 4096 || mesh[1] > 4096 || mesh[2] > 4096)
@@ -1793,8 +1880,7 @@ extern "C" int c2r_create(c2r_ctx **out, int device, const int mesh[3]) {
   c->g.n1 = mesh[0]; c->g.n2 = mesh[1]; c->g.n3 = mesh[2];
   c->g.l1 = mesh[0] / 2; c->g.l2 = mesh[1] / 2; c->g.l3 = mesh[2] / 2;
   c->g.ncell = (size_t)mesh[0] * mesh[1] * mesh[2];
-  c->g.smax = std::max(c->g.l1, std::max(c->g.l2, c->g.l3));
-  c->g.colsize = (size_t)(2 * c->g.smax + 1) * (2 * c->g.smax + 1) * (2 * c->g.smax + 1);
+  shell_bookkeeping(c);
   const size_t nc = c->g.ncell;
 #define CR(call)                                                                                    \
   do {                                                                                              \
@@ -1846,12 +1932,6 @@ extern "C" int c2r_create(c2r_ctx **out, int device, const int mesh[3]) {
   CR(hipMalloc(&c->d_chemspread, sizeof(int) * (size_t)CHEM_CTL_COPIES * CHEM_CTL_STRIDE));
   CR(hipMemset(c->d_chemspread, 0, sizeof(int) * (size_t)CHEM_CTL_COPIES * CHEM_CTL_STRIDE)); // k_chem_ctl_reduce leaves it zeroed
   CR(hipDeviceSynchronize()); // phih_grid = 0 for initial output (evolve_data.F90:77,80)
-  // block bookkeeping of the shells 0..smax
-  c->block_base.assign(c->g.smax + 2, 0);
-  for (int s = 0; s <= c->g.smax; s++)
-    c->block_base[s + 1] = c->block_base[s] + (int)((shell_count(s) + BLOCK - 1) / BLOCK);
-  c->blocks_total = c->block_base[c->g.smax + 1];
-  for (int s = 0; s <= c->g.smax; s++) c->shell_geom.push_back(shell_geometry(s));
   CR(hipMalloc(&c->d_block_base, sizeof(int) * c->block_base.size()));
   CR(hipMemcpy(c->d_block_base, c->block_base.data(), sizeof(int) * c->block_base.size(), hipMemcpyHostToDevice));
   c->ntiles = (size_t)((mesh[0] + 7) / 8) * ((mesh[1] + 7) / 8) * ((mesh[2] + 3) / 4);
@@ -1862,8 +1942,6 @@ extern "C" int c2r_create(c2r_ctx **out, int device, const int mesh[3]) {
     CR(hipHostMalloc(&c->h_tptr[k], sizeof(int) * (c->ntiles + 1)));
     CR(hipMalloc(&c->d_src[k], sizeof(SrcDev) * BATCH_MAX));
     CR(hipHostMalloc(&c->h_src[k], sizeof(SrcDev) * BATCH_MAX));
-    // active lists of all rounds of a batch, one after another (two per round at most, plus the final losses)
-    c->list_cap = (size_t)(2 * (c->g.smax / SUBBOXSIZE + 2) + 4) * BATCH_MAX;
     CR(hipMalloc(&c->d_list[k], sizeof(int) * c->list_cap));
     CR(hipHostMalloc(&c->h_list[k], sizeof(int) * c->list_cap));
   }
@@ -2445,12 +2523,50 @@ static StepScalars scalars(c2r_ctx *c) {
 // time step break out, boxes jump several rounds per iteration: a block sized for one more round then moved to one twice
 // as deep in the middle of the sweep, its old place lay idle until the batch was over, and a batch that ran out of room
 // that way started over); four rounds when nothing is known; never more than the mesh.
+// extent of the mesh as seen from a source
+struct Reach {
+  int l[3], r[3];
+};
+// periodic_bc = .true. (evolve_source.F90:103-105): the same for every source
+static Reach mesh_reach(const Grid &g) {
+  const int mesh[3] = {g.n1, g.n2, g.n3};
+  Reach R;
+  for (int d = 0; d < 3; d++) {
+    R.r[d] = std::min(MAX_SUBBOX, mesh[d] / 2 - 1 + mesh[d] % 2);
+    R.l[d] = -std::min(MAX_SUBBOX, mesh[d] / 2);
+  }
+  return R;
+}
+// open boundaries, the else branch of evolve_source.F90:107-108 (dead code there: lastpos_r = min(srcpos + max_subbox,
+// mesh), lastpos_l = max(srcpos - max_subbox, 1)): up to the mesh faces, per source
+static Reach open_reach(const Grid &g, const int *srcpos) {
+  const int mesh[3] = {g.n1, g.n2, g.n3};
+  Reach R;
+  for (int d = 0; d < 3; d++) {
+    R.r[d] = std::min(MAX_SUBBOX, mesh[d] - srcpos[d]);
+    R.l[d] = -std::min(MAX_SUBBOX, srcpos[d] - 1);
+  }
+  return R;
+}
+static Reach source_reach(const c2r_ctx *c, int ns) {
+  return c->periodic ? mesh_reach(c->g) : open_reach(c->g, &c->srcpos[3 * (size_t)(ns - 1)]);
+}
+// the largest shell a source's column block ever has to hold
+static int source_smax(const c2r_ctx *c, int ns) {
+  if (c->periodic) return c->g.smax;
+  const Reach R = source_reach(c, ns);
+  int m = 0;
+  for (int d = 0; d < 3; d++) m = std::max(m, std::max(R.r[d], -R.l[d]));
+  return m;
+}
+
 static int predicted_shells(const c2r_ctx *c, int ns) {
   const int prev = c->prev_nbox[(size_t)ns - 1];
   const int grow = c->prev_grow.size() == c->prev_nbox.size() ? c->prev_grow[(size_t)ns - 1] : 0;
-  const int cap = std::min(c->g.smax, SUBBOXSIZE * (prev > 0 ? prev + std::max(1, 2 * grow) : 4));
+  const int smax = source_smax(c, ns);
+  const int cap = std::min(smax, SUBBOXSIZE * (prev > 0 ? prev + std::max(1, 2 * grow) : 4));
   // within a fifth of the mesh limit: the limit (a block less than twice as large, and never a move)
-  return 5 * cap >= 4 * c->g.smax ? c->g.smax : cap;
+  return 5 * cap >= 4 * smax ? smax : cap;
 }
 
 static int arena_prepare(c2r_ctx *c) {
@@ -2489,7 +2605,8 @@ static int arena_prepare(c2r_ctx *c) {
       const int cap = predicted_shells(c, mine[b]); // pass_list's predicted_cap
       sum += block_doubles(cap);
       // ... and room for ONE source of the batch to outgrow that (its block then moves to one twice as deep)
-      if (cap < c->g.smax) spare = std::max(spare, block_doubles(std::min(c->g.smax, 2 * cap)));
+      const int smax = source_smax(c, mine[b]);
+      if (cap < smax) spare = std::max(spare, block_doubles(std::min(smax, 2 * cap)));
     }
     need[bi & 1] = std::max(need[bi & 1], sum + spare);
   }
@@ -2577,21 +2694,10 @@ struct SrcRun {
   bool final_loss_due = false; // the last round ended for geometric reasons: its full loss is evaluated after the sweep
   int cap = 0;            // shells the column block can hold
   int smax_prev = -1;     // largest shell already swept
+  Reach reach{};          // how far its box can go: the mesh's with periodic boundaries, its own with open ones
+  int smax = 0;           // the largest shell within that reach
 };
 
-// extent of the mesh as seen from a source, periodic_bc = .true. (evolve_source.F90:103-105)
-struct Reach {
-  int l[3], r[3];
-};
-static Reach mesh_reach(const Grid &g) {
-  const int mesh[3] = {g.n1, g.n2, g.n3};
-  Reach R;
-  for (int d = 0; d < 3; d++) {
-    R.r[d] = std::min(MAX_SUBBOX, mesh[d] / 2 - 1 + mesh[d] % 2);
-    R.l[d] = -std::min(MAX_SUBBOX, mesh[d] / 2);
-  }
-  return R;
-}
 // the sub-box after `nbox` rounds (evolve_source.F90:141-144)
 static Box round_box(const Reach &R, int nbox) {
   Box b;
@@ -2613,6 +2719,14 @@ static long long box_cells(const Box &b) {
 }
 // the while-test of evolve_source.F90:136-139 can still pass after this box (z extent short of the mesh)
 static bool box_can_grow(const Reach &R, const Box &b) { return b.hi[2] < R.r[2] && b.lo[2] > R.l[2]; }
+// Open boundaries: that test looks at z only and at both sides at once, so a source on the plane k = 1 would never start
+// its first round.  Instead: at least one of the six faces of the box is still short of the source's reach.
+static bool box_can_grow_open(const Reach &R, const Box &b) {
+  for (int d = 0; d < 3; d++)
+    if (b.hi[d] < R.r[d] || b.lo[d] > R.l[d]) return true;
+  return false;
+}
+static bool can_grow(const c2r_ctx *c, const Reach &R, const Box &b) { return c->periodic ? box_can_grow(R, b) : box_can_grow_open(R, b); }
 
 static int pool_event(c2r_ctx *c, hipEvent_t *out) {
   if (c->ev_used == c->ev_pool.size()) {
@@ -2636,19 +2750,27 @@ static int blocks_before_surface(const c2r_ctx *c, const Box &box, int s_lo, int
 
 // Photon loss of the round's box for the sources h_list[set][list_off .. +n) (positions in the batch) into
 // c->h_loss[0..n).  Synchronises the sweep stream.
+// Open boundaries: `box` is the round's box before it is cut at each source's reach; deciding: the sum over the faces that
+// can still move (the while-test), else the sum over the whole surface (the loss that is kept).
 static int boundary_loss(c2r_ctx *c, int set, size_t list_off, int n, int s_lo, int s_hi, const Box &box,
-                         const StepScalars &sc, const SedSet &ss, bool multi) {
+                         const StepScalars &sc, const SedSet &ss, bool multi, bool deciding) {
   const int nblk = c->block_base[s_hi + 1] - c->block_base[s_lo];
   const size_t need = (size_t)nblk * n;
   if (c->loss_partial_cap < need) {
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (ensure_pair<double>(c, &c->d_loss_partial, (double **)nullptr, &c->loss_partial_cap, need)) return 1;
   }
-  const int first_block = blocks_before_surface(c, box, s_lo, s_hi);
+  // (open boundaries: a box cut at a mesh face has surface cells in every shell)
+  const int first_block = c->periodic ? blocks_before_surface(c, box, s_lo, s_hi) : 0;
   if (first_block > 0) HIPCHK(c, zero_device(c->d_loss_partial, sizeof(double) * need, c->stream));
-  hipLaunchKernelGGL(k_loss, dim3(nblk - first_block, n), dim3(BLOCK), 0, c->stream, c->g, c->d_src[set], c->d_list[set] + list_off,
-                     multi ? 1 : 0, s_lo, s_hi, box, sc, c->d_bands, ss, c->d_block_base, c->d_loss_partial, nblk,
-                     1, first_block);
+  auto go = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, dim3(nblk - first_block, n), dim3(BLOCK), 0, c->stream, c->g, c->d_src[set], c->d_list[set] + list_off,
+                       multi ? 1 : 0, s_lo, s_hi, box, sc, c->d_bands, ss, c->d_block_base, c->d_loss_partial, nblk,
+                       1, first_block);
+  };
+  if (c->periodic) go(k_loss<false, false>);
+  else if (deciding) go(k_loss<true, true>);
+  else go(k_loss<true, false>);
   hipLaunchKernelGGL(k_loss_finish, dim3(n), dim3(BLOCK), 0, c->stream, c->d_loss_partial, nblk, nblk, c->d_loss_acc);
   c->tm.sweep_launches += 2;
   HIPCHK(c, hipGetLastError());
@@ -2755,9 +2877,12 @@ static int launch_probes(const PassCtx &P, Batch &B) {
     max_nact = std::max(max_nact, P.nact);
   }
   HIPCHK(c, hipMemcpyAsync(c->d_probe_rounds, hr, sizeof(ProbeRound) * nr, hipMemcpyHostToDevice, st));
-  hipLaunchKernelGGL(k_loss_probe_rounds, dim3(max_nblk, max_nact, (unsigned)nr), dim3(BLOCK), 0, st, c->g, c->d_src[B.set], c->d_list[B.set],
-                     static_cast<const ProbeRound *>(c->d_probe_rounds), P.multi ? 1 : 0, P.sc, c->d_bands, P.ss, c->d_block_base,
-                     c->d_probe_partial, PROBE_SAMPLE);
+  auto go = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, dim3(max_nblk, max_nact, (unsigned)nr), dim3(BLOCK), 0, st, c->g, c->d_src[B.set], c->d_list[B.set],
+                       static_cast<const ProbeRound *>(c->d_probe_rounds), P.multi ? 1 : 0, P.sc, c->d_bands, P.ss, c->d_block_base,
+                       c->d_probe_partial, PROBE_SAMPLE);
+  };
+  if (c->periodic) go(k_loss_probe_rounds<false>); else go(k_loss_probe_rounds<true>);
   hipLaunchKernelGGL(k_loss_finish_rounds, dim3(max_nact, (unsigned)nr), dim3(BLOCK), 0, st,
                      static_cast<const ProbeRound *>(c->d_probe_rounds), c->d_probe_partial, c->d_probe_acc);
   c->tm.sweep_launches += 2;
@@ -2854,7 +2979,8 @@ static int place_batch(const PassCtx &P, const std::vector<int> &mine, Batch &B)
       size_t used = 0, reserve = 0;
       for (int b = 0; b < keep; b++) {
         used += 6 * hs[b].cz;
-        if (B.run[b].cap < c->g.smax) reserve += block_doubles(std::min(c->g.smax, 2 * B.run[b].cap));
+        const int smax = source_smax(c, B.run[b].ns);
+        if (B.run[b].cap < smax) reserve += block_doubles(std::min(smax, 2 * B.run[b].cap));
       }
       if (keep <= 1 || used + reserve / 3 <= placed_doubles) break;
       keep--;
@@ -2874,6 +3000,9 @@ static int place_batch(const PassCtx &P, const std::vector<int> &mine, Batch &B)
     const int *p = &c->srcpos[3 * (size_t)(r.ns - 1)];
     S.i0 = p[0]; S.j0 = p[1]; S.k0 = p[2];
     for (int d = 0; d < 3; d++) { S.lo[d] = 0; S.hi[d] = 0; }
+    r.reach = source_reach(c, r.ns);
+    r.smax = source_smax(c, r.ns);
+    for (int d = 0; d < 3; d++) { S.rl[d] = r.reach.l[d]; S.rr[d] = r.reach.r[d]; }
     S.nflux = c->normflux[r.ns - 1];
     for (int k = 0; k < 2; k++) S.nflux_sed[k] = c->normflux_sed[k].empty() ? 0.0 : c->normflux_sed[k][r.ns - 1];
   }
@@ -2908,7 +3037,7 @@ static int settle_rounds(const PassCtx &P, Batch &B) {
       int *ul = hl + B.list_used;
       std::copy(undecided.begin(), undecided.end(), ul);
       HIPCHK(c, hipMemcpyAsync(c->d_list[B.set] + B.list_used, ul, sizeof(int) * undecided.size(), hipMemcpyHostToDevice, c->stream));
-      if (boundary_loss(c, B.set, B.list_used, (int)undecided.size(), R.s_lo, R.s_hi, R.box, P.sc, P.ss, P.multi)) return 1;
+      if (boundary_loss(c, B.set, B.list_used, (int)undecided.size(), R.s_lo, R.s_hi, R.box, P.sc, P.ss, P.multi, true)) return 1;
       B.list_used += undecided.size();
       for (size_t j = 0; j < undecided.size(); j++) B.run[undecided[j]].loss = c->h_loss[j];
     }
@@ -2999,11 +3128,17 @@ static int launch_shells(PassCtx &P, Batch &B, const Box &box, int s_lo, int s_h
     const int nblk = c->block_base[s + 1] - c->block_base[s];
     // from 64 blocks on: a multiple of 8 blocks, one contiguous eighth of the shell per XCD (see the kernel)
     const int nlaunch = nblk >= 64 ? ((nblk + 7) & ~7) : nblk;
-    if (s >= 2 && s <= SHELL_FAST_MAX && !P.generic_sweep)
-      hipLaunchKernelGGL(k_sweep_shell_fast, dim3(nlaunch, nact), dim3(BLOCK), 0, c->stream, SA, c->d_src[B.set],
+    const bool fast = s >= 2 && s <= SHELL_FAST_MAX && !P.generic_sweep;
+    if (fast && c->periodic)
+      hipLaunchKernelGGL(k_sweep_shell_fast<false>, dim3(nlaunch, nact), dim3(BLOCK), 0, c->stream, SA, c->d_src[B.set],
                          c->d_list[B.set] + act_off, c->shell_geom[(size_t)s]);
+    else if (fast)
+      hipLaunchKernelGGL(k_sweep_shell_fast<true>, dim3(nlaunch, nact), dim3(BLOCK), 0, c->stream, SA, c->d_src[B.set],
+                         c->d_list[B.set] + act_off, c->shell_geom[(size_t)s]);
+    else if (c->periodic)
+      hipLaunchKernelGGL(k_sweep_shell<false>, dim3(nlaunch, nact), dim3(BLOCK), 0, c->stream, SA, c->d_src[B.set], c->d_list[B.set] + act_off, s);
     else
-      hipLaunchKernelGGL(k_sweep_shell, dim3(nlaunch, nact), dim3(BLOCK), 0, c->stream, SA, c->d_src[B.set], c->d_list[B.set] + act_off, s);
+      hipLaunchKernelGGL(k_sweep_shell<true>, dim3(nlaunch, nact), dim3(BLOCK), 0, c->stream, SA, c->d_src[B.set], c->d_list[B.set] + act_off, s);
     c->tm.sweep_launches++;
   }
   HIPCHK(c, hipGetLastError());
@@ -3036,8 +3171,9 @@ static int sweep_batch(PassCtx &P, Batch &B) {
   int cur_nact = 0;
   size_t acc_used = 0;
   for (int round = 1;; round++) {
+    // the round's box: with open boundaries before it is cut at each source's reach (the kernels do that, source_box)
     const Box box = round_box(reach, round);
-    const int s_hi = box_smax(box);
+    int s_hi = 0; // the largest shell any source sweeps in this round
     // may this round start before the losses of the rounds before it are known?
     const bool ahead = round > 1 && cur_nact > 0 && all_reached(c, B, round);
     if (!ahead && settle_rounds(P, B)) return 1;
@@ -3048,21 +3184,24 @@ static int sweep_batch(PassCtx &P, Batch &B) {
     for (int b = 0; b < B.nb; b++) {
       SrcRun &r = B.run[b];
       if (!r.active) continue;
-      if (!box_can_grow(reach, round_box(reach, r.nbox)) || !(ahead || r.loss > C2R_F(1e-10) * r.total_flux)) {
+      if (!can_grow(c, r.reach, round_box(r.reach, r.nbox)) || !(ahead || r.loss > C2R_F(1e-10) * r.total_flux)) {
         r.active = false;
         continue;
       }
       r.nbox = round;
       act[nact++] = b;
       s_lo = std::min(s_lo, r.smax_prev + 1);
+      s_hi = std::max(s_hi, box_smax(round_box(r.reach, round)));
     }
     if (nact == 0) return settle_rounds(P, B);
     if (s_hi > c->g.smax) return fail(c, "internal: shell %d beyond smax %d", s_hi, c->g.smax);
     // blocks too small for this round move to larger ones
     for (int a = 0; a < nact; a++) {
       const int cap = B.run[act[a]].cap;
-      if (cap >= s_hi) continue;
-      const int ncap = std::min(c->g.smax, std::max(s_hi, 2 * cap));
+      // (open boundaries: shells beyond a source's own reach hold no cell of it)
+      const int need = std::min(s_hi, B.run[act[a]].smax);
+      if (cap >= need) continue;
+      const int ncap = std::min(B.run[act[a]].smax, std::max(need, 2 * cap));
       double *ncols = arena_alloc(c, B.set, block_doubles(ncap));
       if (!ncols) return start_over(P, B, round);
       if (move_block(P, B, act[a], ncap, ncols)) return 1;
@@ -3078,8 +3217,14 @@ static int sweep_batch(PassCtx &P, Batch &B) {
     cur_off = act_off;
     cur_nact = nact;
     if (launch_shells(P, B, box, s_lo, s_hi, act_off, nact)) return 1;
-    for (int a = 0; a < nact; a++) B.run[hl[act_off + a]].smax_prev = s_hi;
-    if (!box_can_grow(reach, box)) {
+    bool any_can_grow = false, any_can_grow_twice = false; // ... after this round, after the next one
+    for (int a = 0; a < nact; a++) {
+      SrcRun &r = B.run[hl[act_off + a]];
+      r.smax_prev = std::min(s_hi, r.smax);
+      any_can_grow = any_can_grow || can_grow(c, r.reach, round_box(r.reach, round));
+      any_can_grow_twice = any_can_grow_twice || can_grow(c, r.reach, round_box(r.reach, round + 1));
+    }
+    if (!any_can_grow) {
       // The while-test after this round fails whatever the loss: the round is every active source's last, and
       // its loss (the one that is kept, evolve_source.F90:233) is queued behind the rates launch (queue_kept_losses).
       // The rounds before it are decided now; their probes were queued before this round's shells.
@@ -3100,7 +3245,7 @@ static int sweep_batch(PassCtx &P, Batch &B) {
     // Its probe goes out now if the next round needs the answer before it can start (somebody may stop here) or if
     // the next round is the last for geometric reasons (the probes then run beside its shells, and the answers
     // are there when the rates launch has to be put together); otherwise it waits for company.
-    const bool next_is_last = !box_can_grow(reach, round_box(reach, round + 1));
+    const bool next_is_last = !any_can_grow_twice;
     if ((!all_reached(c, B, round + 1) || next_is_last) && launch_probes(P, B)) return 1;
   }
 }
@@ -3110,17 +3255,22 @@ static int sweep_batch(PassCtx &P, Batch &B) {
 static int close_boxes(PassCtx &P, Batch &B) {
   c2r_ctx *c = P.c;
   for (int b = 0; b < B.nb; b++) {
-    const SrcRun &r = B.run[b];
+    SrcRun &r = B.run[b];
     SrcDev &S = c->h_src[B.set][b];
-    const Box fb = round_box(P.reach, r.nbox);
+    const Box fb = round_box(r.reach, r.nbox);
     for (int d = 0; d < 3; d++) { S.lo[d] = fb.lo[d]; S.hi[d] = fb.hi[d]; }
+    // Open boundaries: the loss that decided -- through the faces that could still move -- is not the one that is kept:
+    // photon_loss takes what leaves through the WHOLE surface of the final box, mesh faces included, whichever way the
+    // loop ended.  Every source that traced anything owes that sum.
+    if (!c->periodic) r.final_loss_due = r.nbox > 0;
     // a source whose while-test failed before the first sub-box (a mesh only two cells deep) traced nothing:
     // an empty box, so that no cell passes the in-box test
     if (r.nbox == 0) { S.lo[0] = 1; S.hi[0] = 0; }
     // the terms of the kept loss of a round that was the last for geometric reasons come out of the rates launch: the
     // surface cells in the shells of that round (heating kernels do not keep photo_out, see k_rates)
     S.loss_lo = -1;
-    if (r.final_loss_due && c->isothermal) S.loss_lo = r.nbox > 1 ? box_smax(round_box(P.reach, r.nbox - 1)) + 1 : 0;
+    if (r.final_loss_due && c->isothermal)
+      S.loss_lo = c->periodic && r.nbox > 1 ? box_smax(round_box(P.reach, r.nbox - 1)) + 1 : 0; // (open: every shell of the box)
     // (known0: what was known before this batch -- a batch that started over has raised prev_nbox meanwhile)
     const int known = B.known0[(size_t)b];
     c->prev_grow[(size_t)r.ns - 1] = known > 0 ? std::max(0, r.nbox - known) : 0;
@@ -3155,7 +3305,7 @@ static int build_tile_lists(const PassCtx &P, Batch &B) {
   B.ntiles = 0;
   bool full = false;
   for (int b = 0; b < B.nb && !full; b++) {
-    const Box fb = round_box(P.reach, B.run[b].nbox);
+    const Box fb = round_box(B.run[b].reach, B.run[b].nbox);
     full = B.run[b].nbox > 0;
     for (int d = 0; d < 3; d++) full = full && (fb.hi[d] - fb.lo[d] + 1 >= mesh[d]);
   }
@@ -3166,7 +3316,7 @@ static int build_tile_lists(const PassCtx &P, Batch &B) {
   std::vector<int> cov[3];
   const int tsz[3] = {8, 8, 4}, ntd[3] = {nt1, nt2, nt3};
   auto covered = [&](int b) {
-    const Box fb = round_box(P.reach, B.run[b].nbox);
+    const Box fb = round_box(B.run[b].reach, B.run[b].nbox); // (open boundaries: inside the mesh, the modulo below does nothing)
     const int *p = &c->srcpos[3 * (size_t)(B.run[b].ns - 1)];
     for (int d = 0; d < 3; d++) {
       cov[d].clear();
@@ -3277,8 +3427,13 @@ static int launch_rates(const PassCtx &P, Batch &B, bool last_batch) {
                          c->d_bands, P.ss, c->d_rates, lists ? c->d_tiles[B.set] : nullptr, lists ? c->d_tptr[B.set] : nullptr,
                          lists ? c->d_tsrc[B.set] : nullptr, base, fresh);
     };
-    if (cnt > 0 && c->isothermal) P.multi ? go(k_rates<false, true>) : go(k_rates<false, false>);
-    if (cnt > 0 && !c->isothermal) P.multi ? go(k_rates<true, true>) : go(k_rates<true, false>);
+    if (cnt > 0 && c->periodic) {
+      if (c->isothermal) P.multi ? go(k_rates<false, true>) : go(k_rates<false, false>);
+      else P.multi ? go(k_rates<true, true>) : go(k_rates<true, false>);
+    } else if (cnt > 0) {
+      if (c->isothermal) P.multi ? go(k_rates<false, true, true>) : go(k_rates<false, false, true>);
+      else P.multi ? go(k_rates<true, true, true>) : go(k_rates<true, false, true>);
+    }
     if (slabs) HIPCHK(c, hipEventRecord(c->ev_slab[piece], st));
   }
   if (pieces > 1) {
@@ -3322,8 +3477,13 @@ static int queue_kept_losses(const PassCtx &P, Batch &B) {
         fl[nf++] = b;
         B.run[b].final_loss_due = false;
       }
+    // (open boundaries: fb is cut at each source's reach by the kernels; the whole surface of the final box, all its shells)
     const Box fb = round_box(P.reach, fr);
-    const int f_lo = fr > 1 ? box_smax(round_box(P.reach, fr - 1)) + 1 : 0, f_hi = box_smax(fb);
+    int f_lo = fr > 1 ? box_smax(round_box(P.reach, fr - 1)) + 1 : 0, f_hi = box_smax(fb);
+    if (!c->periodic) {
+      f_lo = f_hi = 0;
+      for (int j = 0; j < nf; j++) f_hi = std::max(f_hi, box_smax(round_box(B.run[fl[j]].reach, fr)));
+    }
     if (c->isothermal) {
       HIPCHK(c, hipMemcpyAsync(c->d_list[set] + B.list_used, fl, sizeof(int) * nf, hipMemcpyHostToDevice, c->stream2));
       const int nblk = c->block_base[f_hi + 1] - c->block_base[f_lo];
@@ -3332,10 +3492,14 @@ static int queue_kept_losses(const PassCtx &P, Batch &B) {
         HIPCHK(c, hipStreamSynchronize(c->stream2));
         if (ensure_pair<double>(c, &c->d_final_partial[set], (double **)nullptr, &c->final_partial_cap[set], need)) return 1;
       }
-      const int first_block = blocks_before_surface(c, fb, f_lo, f_hi);
+      const int first_block = c->periodic ? blocks_before_surface(c, fb, f_lo, f_hi) : 0;
       if (first_block > 0) HIPCHK(c, zero_device(c->d_final_partial[set], sizeof(double) * need, c->stream2));
-      hipLaunchKernelGGL(k_loss_stored, dim3(nblk - first_block, nf), dim3(BLOCK), 0, c->stream2, c->g, c->d_src[set],
-                         c->d_list[set] + B.list_used, f_lo, f_hi, fb, c->d_block_base, c->d_final_partial[set], nblk, first_block);
+      if (c->periodic)
+        hipLaunchKernelGGL(k_loss_stored<false>, dim3(nblk - first_block, nf), dim3(BLOCK), 0, c->stream2, c->g, c->d_src[set],
+                           c->d_list[set] + B.list_used, f_lo, f_hi, fb, c->d_block_base, c->d_final_partial[set], nblk, first_block);
+      else
+        hipLaunchKernelGGL(k_loss_stored<true>, dim3(nblk - first_block, nf), dim3(BLOCK), 0, c->stream2, c->g, c->d_src[set],
+                           c->d_list[set] + B.list_used, f_lo, f_hi, fb, c->d_block_base, c->d_final_partial[set], nblk, first_block);
       hipLaunchKernelGGL(k_loss_finish, dim3(nf), dim3(BLOCK), 0, c->stream2, c->d_final_partial[set], nblk, nblk,
                          c->d_final_acc[set] + nslot);
       HIPCHK(c, hipGetLastError());
@@ -3343,7 +3507,7 @@ static int queue_kept_losses(const PassCtx &P, Batch &B) {
       nslot += nf;
     } else {
       HIPCHK(c, hipMemcpyAsync(c->d_list[set] + B.list_used, fl, sizeof(int) * nf, hipMemcpyHostToDevice, c->stream));
-      if (boundary_loss(c, set, B.list_used, nf, f_lo, f_hi, fb, P.sc, P.ss, P.multi)) return 1;
+      if (boundary_loss(c, set, B.list_used, nf, f_lo, f_hi, fb, P.sc, P.ss, P.multi, false)) return 1;
       for (int j = 0; j < nf; j++) bt.loss[(size_t)fl[j]] = c->h_loss[j];
     }
     B.list_used += (size_t)nf;
@@ -3367,7 +3531,13 @@ static int pass_list(c2r_ctx *c, const std::vector<int> &mine, int nslab = 0) {
   } in_pass_guard(c);
   static const bool generic_sweep = getenv("C2R_SWEEP_GENERIC") && atoi(getenv("C2R_SWEEP_GENERIC")) > 0;
   static const bool arena_log = getenv("C2R_ARENA_LOG") != nullptr;
-  PassCtx P{c, scalars(c), SedSet(), false, mesh_reach(c->g), generic_sweep, arena_log};
+  // (open boundaries: the reach of a source in the far corner on either side -- what no source's box exceeds)
+  Reach widest = mesh_reach(c->g);
+  if (!c->periodic) {
+    const int mesh[3] = {c->g.n1, c->g.n2, c->g.n3};
+    for (int d = 0; d < 3; d++) { widest.r[d] = std::min(MAX_SUBBOX, mesh[d] - 1); widest.l[d] = -widest.r[d]; }
+  }
+  PassCtx P{c, scalars(c), SedSet(), false, widest, generic_sweep, arena_log};
   P.ss = sedset(c, &P.multi);
   c->tm.sweep_ms = c->tm.rates_ms = 0.0;
   c->tm.sweep_launches = c->tm.rates_launches = 0;
@@ -3424,7 +3594,7 @@ static int pass_list(c2r_ctx *c, const std::vector<int> &mine, int nslab = 0) {
     if (c->timing) P.tev.insert(P.tev.end(), B.ev, B.ev + 4);
     HIPCHK(c, hipEventRecord(c->ev_rates_done[B.set], c->stream2));
     c->set_busy[B.set] = true;
-    for (const SrcRun &r : B.run) c->tm.cells_swept += r.nbox > 0 ? box_cells(round_box(P.reach, r.nbox)) : 0;
+    for (const SrcRun &r : B.run) c->tm.cells_swept += r.nbox > 0 ? box_cells(round_box(r.reach, r.nbox)) : 0;
     const SrcDev &S = c->h_src[B.set][B.nb - 1];
     c->last_src = B.run[B.nb - 1].ns;
     c->last_cols = S.cols;
@@ -3645,7 +3815,7 @@ extern "C" int c2r_evolve0d(c2r_ctx *c, const int rtpos[3], int ns, int niter, i
   const Grid g = c->g;
   const int *sp = &c->srcpos[3 * (size_t)(ns - 1)];
   const int di = rtpos[0] - sp[0], dj = rtpos[1] - sp[1], dk = rtpos[2] - sp[2];
-  const Reach R = mesh_reach(g);
+  const Reach R = source_reach(c, ns);
   if (di < R.l[0] || di > R.r[0] || dj < R.l[1] || dj > R.r[1] || dk < R.l[2] || dk > R.r[2])
     return fail(c, "c2r_evolve0d: cell (%d,%d,%d) is beyond the reach of source %d at (%d,%d,%d)", rtpos[0], rtpos[1], rtpos[2], ns,
                 sp[0], sp[1], sp[2]);
@@ -3676,16 +3846,28 @@ extern "C" int c2r_evolve0d(c2r_ctx *c, const int rtpos[3], int ns, int niter, i
   S.cols = c->d_point_cols;
   S.cz = cz;
   S.loss_lo = -1;
+  for (int d = 0; d < 3; d++) { S.rl[d] = R.l[d]; S.rr[d] = R.r[d]; }
   double *dl = on_surface ? c->d_point_loss : nullptr;
   if (!c->isothermal) c->phiheat_dirty = true;
 #define C2R_LAUNCH_POINT(H, M) \
   hipLaunchKernelGGL((k_evolve0d<H, M>), dim3(1), dim3(64), 0, c->stream, SA, S, di, dj, dk, c->d_bands, ss, c->d_rates, dl)
-  if (c->isothermal) {
-    if (multi) C2R_LAUNCH_POINT(false, true); else C2R_LAUNCH_POINT(false, false);
+#define C2R_LAUNCH_POINT_OPEN(H, M) \
+  hipLaunchKernelGGL((k_evolve0d<H, M, true>), dim3(1), dim3(64), 0, c->stream, SA, S, di, dj, dk, c->d_bands, ss, c->d_rates, dl)
+  if (c->periodic) {
+    if (c->isothermal) {
+      if (multi) C2R_LAUNCH_POINT(false, true); else C2R_LAUNCH_POINT(false, false);
+    } else {
+      if (multi) C2R_LAUNCH_POINT(true, true); else C2R_LAUNCH_POINT(true, false);
+    }
   } else {
-    if (multi) C2R_LAUNCH_POINT(true, true); else C2R_LAUNCH_POINT(true, false);
+    if (c->isothermal) {
+      if (multi) C2R_LAUNCH_POINT_OPEN(false, true); else C2R_LAUNCH_POINT_OPEN(false, false);
+    } else {
+      if (multi) C2R_LAUNCH_POINT_OPEN(true, true); else C2R_LAUNCH_POINT_OPEN(true, false);
+    }
   }
 #undef C2R_LAUNCH_POINT
+#undef C2R_LAUNCH_POINT_OPEN
   HIPCHK(c, hipGetLastError());
   if (on_surface) {
     HIPCHK(c, hipMemcpyAsync(c->h_point_loss, c->d_point_loss, sizeof(double), hipMemcpyDeviceToHost, c->stream));
@@ -3916,7 +4098,8 @@ extern "C" int c2r_download_columns(c2r_ctx *c, double *coldensh_out, double *co
   S.i0 = p[0]; S.j0 = p[1]; S.k0 = p[2];
   for (int d = 0; d < 3; d++) { S.lo[d] = c->last_lo[d]; S.hi[d] = c->last_hi[d]; }
   S.cz = c->last_cz;
-  hipLaunchKernelGGL(k_col_to_grid, dim3(nblk), dim3(BLOCK), 0, c->stream, c->g, S, c->last_cols, c->d_colgrid);
+  if (c->periodic) hipLaunchKernelGGL(k_col_to_grid<false>, dim3(nblk), dim3(BLOCK), 0, c->stream, c->g, S, c->last_cols, c->d_colgrid);
+  else hipLaunchKernelGGL(k_col_to_grid<true>, dim3(nblk), dim3(BLOCK), 0, c->stream, c->g, S, c->last_cols, c->d_colgrid);
   HIPCHK(c, hipGetLastError());
   if (coldensh_out) HIPCHK(c, hipMemcpyAsync(coldensh_out, c->d_colgrid, sizeof(double) * nc, hipMemcpyDeviceToHost, c->stream));
   if (coldenshe_out)
@@ -4146,6 +4329,54 @@ extern "C" int c2r_set_batch(c2r_ctx *c, int nbatch) {
   if (int e_ = set_batch_one(c, nbatch)) return e_;
   return for_replicas(c, [&](c2r_ctx *r) { return set_batch_one(r, nbatch); });
 }
+
+// Switching forgets what earlier passes learnt about the sources (sub-box counts, hence predicted block sizes and the
+// rounds swept on trust): none of it holds for the other geometry.  The column scratch stays; it only ever holds finite
+// numbers, whoever wrote them.
+static int set_boundaries_one(c2r_ctx *c, int periodic) {
+  if (!c) return 1;
+  if (c->pass_open) return fail(c, "c2r_set_boundaries: a pass opened by c2r_pass_sources_begin is still open (close it with c2r_pass_sources_end first)");
+  const bool want = periodic != 0;
+  if (want == c->periodic) return 0;
+  HIPCHK(c, hipSetDevice(c->device));
+  // nothing queued may still read the shell bookkeeping or the lists that are about to be replaced
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream2));
+  HIPCHK(c, hipStreamSynchronize(c->stream3));
+  HIPCHK(c, hipStreamSynchronize(c->stream_probe));
+  c->periodic = want;
+  shell_bookkeeping(c);
+  HIPCHK(c, hipFree(c->d_block_base));
+  c->d_block_base = nullptr;
+  HIPCHK(c, hipMalloc(&c->d_block_base, sizeof(int) * c->block_base.size()));
+  HIPCHK(c, hipMemcpy(c->d_block_base, c->block_base.data(), sizeof(int) * c->block_base.size(), hipMemcpyHostToDevice));
+  for (int k = 0; k < 2; k++) {
+    HIPCHK(c, hipFree(c->d_list[k]));
+    HIPCHK(c, hipHostFree(c->h_list[k]));
+    c->d_list[k] = c->h_list[k] = nullptr;
+    HIPCHK(c, hipMalloc(&c->d_list[k], sizeof(int) * c->list_cap));
+    HIPCHK(c, hipHostMalloc(&c->h_list[k], sizeof(int) * c->list_cap));
+  }
+  if (c->d_point_cols) { // c2r_evolve0d's block holds the whole reach of a source: made anew at the next call
+    HIPCHK(c, hipFree(c->d_point_cols));
+    c->d_point_cols = nullptr;
+    if (c->d_point_loss) HIPCHK(c, hipFree(c->d_point_loss));
+    if (c->h_point_loss) HIPCHK(c, hipHostFree(c->h_point_loss));
+    c->d_point_loss = c->h_point_loss = nullptr;
+  }
+  c->prev_nbox.assign((size_t)c->nsrc, 0);
+  c->prev_grow.assign((size_t)c->nsrc, 0);
+  c->last_src = 0;
+  c->last_cols = nullptr;
+  return 0;
+}
+
+extern "C" int c2r_set_boundaries(c2r_ctx *c, int periodic) {
+  if (int e_ = set_boundaries_one(c, periodic)) return e_;
+  return for_replicas(c, [&](c2r_ctx *r) { return set_boundaries_one(r, periodic); });
+}
+
+extern "C" int c2r_get_boundaries(const c2r_ctx *c) { return !c || c->periodic ? 1 : 0; }
 
 extern "C" int c2r_upload_rates(c2r_ctx *c, const double *phih, const double *phihe, const double *phiheat) {
   if (int e_ = upload_rates_one(c, phih, phihe, phiheat)) return e_;

@@ -437,6 +437,15 @@ class HipEngine:
     def set_batch(self, n):
         self._chk(self.lib.c2r_set_batch(self.h, int(n)))
 
+    def set_boundaries(self, periodic=True):
+        """Mesh boundaries of the ray trace: periodic (the default, the reference's) or open -- nothing wraps, photons
+        that reach a mesh face are lost (c2r_set_boundaries; include/c2ray_hip.h has the semantics)."""
+        self._chk(self.lib.c2r_set_boundaries(self.h, int(bool(periodic))))
+
+    @property
+    def periodic(self):
+        return bool(self.lib.c2r_get_boundaries(self.h))
+
     def enable_timing(self, on=True):
         self._chk(self.lib.c2r_enable_timing(self.h, int(on)))
 
@@ -533,9 +542,11 @@ class Evolve:
     chemistry pass is replicated on every rank (evolve.F90:477-484).
     """
 
-    def __init__(self, mesh, tables: RadiationTables | None = None, device=0, engine=None, comm=None):
+    def __init__(self, mesh, tables: RadiationTables | None = None, device=0, engine=None, comm=None, periodic=True):
         self.mesh = tuple(int(m) for m in mesh)
         self.engine = engine if engine is not None else HipEngine(self.mesh, device)
+        if not periodic:    # open mesh boundaries (HipEngine.set_boundaries); the default leaves the engine as it is
+            self.engine.set_boundaries(False)
         self.tables = tables if tables is not None else RadiationTables.load()
         self.engine.set_tables(self.tables)
         self.comm = comm

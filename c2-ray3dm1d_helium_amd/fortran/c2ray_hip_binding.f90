@@ -507,6 +507,18 @@ module c2ray_hip
        integer(c_int), value :: nbatch
      end function c2r_set_batch
 
+     !> mesh boundaries of the ray trace: periodic /= 0 (default) or 0, open (include/c2ray_hip.h)
+     integer(c_int) function c2r_set_boundaries(ctx, periodic) bind(C, name="c2r_set_boundaries")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: ctx
+       integer(c_int), value :: periodic
+     end function c2r_set_boundaries
+
+     integer(c_int) function c2r_get_boundaries(ctx) bind(C, name="c2r_get_boundaries")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: ctx
+     end function c2r_get_boundaries
+
      integer(c_int) function c2r_enable_timing(ctx, on) bind(C, name="c2r_enable_timing")
        import :: c_int, c_ptr
        type(c_ptr), value :: ctx

@@ -9,6 +9,7 @@ module evolve_data
   use, intrinsic :: iso_c_binding, only: c_ptr, c_null_ptr, c_int, c_char, c_double, c_null_char
   use c2ray_hip, only: c2r_create, c2r_create_multi, c2r_error_text, c2r_device_count, c2r_get_constants
   use c2ray_hip, only: c2r_comm_unique_id, c2r_comm_init, c2r_comm_init_local, c2r_comm_kind, c2r_comm_library
+  use c2ray_hip, only: c2r_set_boundaries
   use file_admin, only: logf
   use my_mpi                                  ! rank, npr, MPI_COMM_NEW
   use precision, only: dp
@@ -22,8 +23,11 @@ module evolve_data
   implicit none
   save
 
-  !> the sweep wraps around the mesh edges (the only mode the reference supports here)
+  !> the sweep wraps around the mesh edges (the only mode the reference supports here; the reference's own
+  !! evolve_source.F90, linked on top of this module for the cell-by-cell interface, reads this parameter)
   logical, parameter :: periodic_bc = .true.
+  !> C2RAY_HIP_OPEN_BOUNDARIES=1: the device traces a box that does not wrap (c2r_set_boundaries)
+  logical :: hip_open_boundaries = .false.
 
   ! host mirrors of device arrays, public under the reference's names
   !> photo-ionisation rates summed over all sources: H, and He (components 0:1)
@@ -65,7 +69,7 @@ contains
     integer(c_int), allocatable :: devices(:)
     character(len=32) :: value
     integer :: length, status
-    integer :: n1, n2, n3, ndev_node, local_rank, offset, i
+    integer :: n1, n2, n3, ndev_node, local_rank, offset, i, open_bc
 
     n1 = mesh(1)
     n2 = mesh(2)
@@ -123,6 +127,18 @@ contains
     if (ierr /= 0) call stop_with (c2r_error_text(c_null_ptr))
     if (rank == 0) write(logf,"(A,I3,A,I3)") "evolve_ini: evolve3D runs on HIP device ", hip_device, &
          ", devices per rank: ", hip_ndevices
+
+    ! C2RAY_HIP_OPEN_BOUNDARIES=1: open (non-periodic) mesh boundaries, the dead else branch of the reference's
+    ! evolve_source.F90:103-109 built out (include/c2ray_hip.h: c2r_set_boundaries).  The reference's own build cannot
+    ! run this mode, so there are no files of its to compare with.
+    open_bc = 0
+    call env_integer ("C2RAY_HIP_OPEN_BOUNDARIES", open_bc)
+    hip_open_boundaries = open_bc /= 0
+    if (hip_open_boundaries) then
+       ierr = c2r_set_boundaries (hip_ctx, 0_c_int)
+       if (ierr /= 0) call stop_with (c2r_error_text(hip_ctx))
+       if (rank == 0) write(logf,"(A)") " evolve_ini: open (non-periodic) mesh boundaries (C2RAY_HIP_OPEN_BOUNDARIES)"
+    endif
 
     call setup_communicator ()
 

@@ -250,6 +250,34 @@ int c2r_get_constants(double *out, int capacity);
  * pass); a batch is cut short when the arena cannot hold it. */
 int c2r_set_batch(c2r_ctx *ctx, int nbatch);
 
+/* Mesh boundaries of the ray trace: periodic != 0 (the default; what the reference runs, evolve_data.F90:27-28
+ * "has to be true for this version") or periodic == 0, OPEN: nothing wraps, photons that reach a mesh face leave the
+ * box and are counted as lost.  Open boundaries follow the reference's own, dead, else branch of
+ * evolve_source.F90:103-109: the reach of a source is per source and per axis, lastpos_l = max(srcpos - max_subbox, 1),
+ * lastpos_r = min(srcpos + max_subbox, mesh); the box of round nbox (:143-144) is cut at that reach, so it differs from
+ * source to source; a cell of a box lies at srcpos + offset, no modulo.  Everything per cell (cinterp, coldens,
+ * photoion_rates, vol_ph, the LLS fog) is unchanged.
+ * ONE DEPARTURE from that source text: the while-test of :136-139 looks at z only, and at both sides at once -- without
+ * periodicity a source on the plane k = 1 would never start its first round, and a source three cells from a face
+ * would be driven across the whole mesh by photons that leave through that face whatever its box does.  In open mode
+ * there are therefore two sums over the surface cells of a box (evolve_point.F90:310-315) where the periodic code has
+ * one:
+ *   the loss that DECIDES: photo_out*vol/vol_ph over the surface cells on a face still short of the source's reach;
+ *     the loop goes on while it exceeds 1e-10 * total_source_flux and at least one of the six faces can still move;
+ *   the loss that is KEPT (photon_loss(1)): the same terms over the whole surface of the final box, mesh faces included.
+ * With periodic boundaries every face can move until the limit, the two coincide, and nothing changes.
+ * sum_nbox counts rounds as before.
+ * Acts on every device of a multi-device context.  A switch forgets what earlier passes learnt about the sources
+ * (sub-box counts, predicted column blocks, rounds swept without waiting for their loss).  Refused, with an error,
+ * between c2r_pass_sources_begin and c2r_pass_sources_end.  c2r_pass_sources, c2r_pass_sources_begin, c2r_do_source,
+ * c2r_evolve0d (whose cell must lie within the source's reach: inside the mesh), c2r_iteration, c2r_evolve3d,
+ * c2r_pass_allreduce_chemistry and c2r_download_columns honour the mode.
+ * Memory: the column block of a source in a corner holds (2(N-1)+1)^3 cells of 48 bytes -- 6.4 GB at N = 256 against
+ * 0.8 GB with periodic boundaries; blocks are sized per source, from its own reach. */
+int c2r_set_boundaries(c2r_ctx *ctx, int periodic);
+/* 1: periodic, 0: open */
+int c2r_get_boundaries(const c2r_ctx *ctx);
+
 /* ---- several GPUs: sources over ranks and the sum over ranks ----------------------------------------
  * The reference's MPI strategy (master_slave.F90:74-96 do_grid_static, evolve.F90:505-548
  * mpi_accumulate_grid_quantities): every rank holds the full grid, rank r sweeps sources r+1, r+1+npr, ...,
