@@ -27,6 +27,13 @@ class Timing(C.Structure):
                 ("cells_swept", C.c_longlong)]
 
 
+class SourceTrace(C.Structure):
+    """c2r_source_trace (include/c2ray_hip.h)."""
+    _fields_ = [("reach_l", C.c_int * 3), ("reach_r", C.c_int * 3), ("nbox", C.c_int), ("box_lo", C.c_int * 3),
+                ("box_hi", C.c_int * 3), ("block_shells", C.c_int), ("block_cells", C.c_longlong),
+                ("swept_cells", C.c_longlong), ("sweep_threads", C.c_longlong)]
+
+
 class IterationReport(C.Structure):
     """c2r_iteration_report (include/c2ray_hip.h)."""
     _fields_ = [("conv_flag", C.c_int), ("sum_nbox", C.c_int), ("photon_loss", C.c_double * NFREQ),
@@ -66,6 +73,7 @@ SYMBOLS = {
     "c2r_set_step": (C.c_int, [C.c_void_p, _dp, _dp, C.c_double, C.c_float, C.c_double, C.c_double, C.c_double,
                                C.c_int, C.c_double, _dp]),
     "c2r_arena_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong)]),
+    "c2r_get_source_trace": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(SourceTrace)]),
     "c2r_set_step_scalars": (C.c_int, [C.c_void_p, _dp, C.c_double, C.c_float, C.c_double, C.c_double, C.c_double,
                                        C.c_int, C.c_double, _dp]),
     "c2r_scale_ndens": (C.c_int, [C.c_void_p, C.c_double]),

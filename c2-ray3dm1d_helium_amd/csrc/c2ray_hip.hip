@@ -19,6 +19,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <cmath>
 #include <cstdarg>
@@ -57,7 +58,8 @@ struct SrcDev {
   double nflux;        // NormFlux(ns)
   double nflux_sed[2]; // NormFluxPL(ns), NormFluxQPL(ns) (-DPL / -DQUASARS builds), else 0
   double *cols;        // this source's column block in the scratch arena
-  size_t cz;           // entries per column array of that block: (2*cap+1)^3, cap = shells the block can hold
+  size_t cz;           // entries per column array of that block, cap = shells it can hold: (2*cap+1)^3, or with open
+                       // boundaries the cells of those shells within the source's reach (reach_cells, c2ray_shell.hpp)
   int loss_lo;         // >= 0: the rates launch leaves, for every surface cell of the final sub-box in shells >= loss_lo,
                        // the photons that leave the box through it in the cell's N_in(HI) slot (k_loss_stored adds
                        // them up); -1: no such request (set before the rates launch)
@@ -260,18 +262,21 @@ k_loss(Grid g, const SrcDev *__restrict__ src, const int *__restrict__ list, int
     if (block_base[mid] <= B) lo = mid; else hi = mid - 1;
   }
   const int shell = lo;
-  const long long cnt = shell_count(shell);
+  ReachShell RS{}; // (open boundaries: the shell cut at the source's reach; its blocks are the first of the uncut shell's)
+  if constexpr (OPEN) RS = reach_shell(S.rl, S.rr, shell);
+  const long long cnt = OPEN ? (long long)RS.cnt : shell_count(shell);
   const long long t = (long long)(B - block_base[shell]) * BLOCK + threadIdx.x;
   double loss = 0.0;
   if (t < cnt) {
     int di, dj, dk;
-    shell_decode(shell, (int)t, di, dj, dk);
+    if constexpr (OPEN) reach_decode(RS, (int)t, di, dj, dk);
+    else shell_decode(shell, (int)t, di, dj, dk);
     const bool inside = di >= box.lo[0] && di <= box.hi[0] && dj >= box.lo[1] && dj <= box.hi[1] && dk >= box.lo[2] &&
                         dk <= box.hi[2];
     const bool boundary = on_counted_face<OPEN>(box, S, di, dj, dk, MOVABLE ? 1 : 0);
     if (inside && boundary) {
       const size_t cz = S.cz;
-      const size_t p = (size_t)shell_offset(shell) + (size_t)t;
+      const size_t p = (OPEN ? (size_t)RS.off : (size_t)shell_offset(shell)) + (size_t)t;
       const global_double *cs = (const global_double *)S.cols;
       const double cin_HI = cs[col_in(p, 0, cz)], cin_HeI = cs[col_in(p, 1, cz)], cin_HeII = cs[col_in(p, 2, cz)];
       const double cout_HI = cs[col_out(p, 0, cz)], cout_HeI = cs[col_out(p, 1, cz)], cout_HeII = cs[col_out(p, 2, cz)];
@@ -327,17 +332,20 @@ k_loss_stored(Grid g, const SrcDev *__restrict__ src, const int *__restrict__ li
     if (block_base[mid] <= B) lo = mid; else hi = mid - 1;
   }
   const int shell = lo;
-  const long long cnt = shell_count(shell);
+  ReachShell RS{}; // (open boundaries: the shell cut at the source's reach; its blocks are the first of the uncut shell's)
+  if constexpr (OPEN) RS = reach_shell(S.rl, S.rr, shell);
+  const long long cnt = OPEN ? (long long)RS.cnt : shell_count(shell);
   const long long t = (long long)(B - block_base[shell]) * BLOCK + threadIdx.x;
   double loss = 0.0;
   if (t < cnt) {
     int di, dj, dk;
-    shell_decode(shell, (int)t, di, dj, dk);
+    if constexpr (OPEN) reach_decode(RS, (int)t, di, dj, dk);
+    else shell_decode(shell, (int)t, di, dj, dk);
     const bool inside = di >= box.lo[0] && di <= box.hi[0] && dj >= box.lo[1] && dj <= box.hi[1] && dk >= box.lo[2] &&
                         dk <= box.hi[2];
     const bool boundary = on_counted_face<OPEN>(box, S, di, dj, dk, 0);
     if (inside && boundary) {
-      const size_t p = (size_t)shell_offset(shell) + (size_t)t;
+      const size_t p = (OPEN ? (size_t)RS.off : (size_t)shell_offset(shell)) + (size_t)t;
       loss = ((const global_double *)S.cols)[col_in(p, 0, S.cz)];
     }
   }
@@ -403,7 +411,13 @@ __device__ __forceinline__ void sweep_cell(const SweepArgs &A, const SrcDev &S, 
   const Grid &g = A.g;
   const StepScalars &sc = A.sc;
   int di, dj, dk;
-  shell_decode(shell, t, di, dj, dk);
+  ReachShell RS{}; // (open boundaries: t counts the cells of the shell cut at the source's reach)
+  if constexpr (OPEN) {
+    RS = reach_shell(S.rl, S.rr, shell);
+    reach_decode(RS, t, di, dj, dk);
+  } else {
+    shell_decode(shell, t, di, dj, dk);
+  }
   Box cut_;
   if constexpr (OPEN) cut_ = source_box(A.box, S);
   const Box &box = OPEN ? cut_ : A.box; // (periodic: the launch's box itself)
@@ -411,12 +425,12 @@ __device__ __forceinline__ void sweep_cell(const SweepArgs &A, const SrcDev &S, 
                       dk <= box.hi[2];
   if (!inside) return;
   const size_t cz = S.cz;
-  const size_t p = (size_t)shell_offset(shell) + (size_t)t;
+  const size_t p = (OPEN ? (size_t)RS.off : (size_t)shell_offset(shell)) + (size_t)t;
   global_double *cs = (global_double *)S.cols;
   const int i = mesh0<OPEN>(S.i0 - 1 + di, g.n1), j = mesh0<OPEN>(S.j0 - 1 + dj, g.n2), k = mesh0<OPEN>(S.k0 - 1 + dk, g.n3);
   const int w_ = 2 * shell + 1;
   double u_HI, u_HeI, u_HeII;
-  sweep_cell_state(A, i, j, k, shell > 0 && t >= 2 * w_ * w_ + 2 * (w_ - 2) * w_, u_HI, u_HeI, u_HeII);
+  sweep_cell_state(A, i, j, k, shell > 0 && t >= (OPEN ? RS.b4 : 2 * w_ * w_ + 2 * (w_ - 2) * w_), u_HI, u_HeI, u_HeII);
   double cin_HI, cin_HeI, cin_HeII, path;
   if (shell == 0) {
     cin_HI = cin_HeI = cin_HeII = 0.0;
@@ -426,7 +440,14 @@ __device__ __forceinline__ void sweep_cell(const SweepArgs &A, const SrcDev &S, 
     short_characteristic(S.i0, S.j0, S.k0, di, dj, dk, s4);
     size_t qc[4];
 #pragma unroll
-    for (int c = 0; c < 4; c++) qc[c] = shell_position(s4.ci[c], s4.cj[c], s4.ck[c]);
+    for (int c = 0; c < 4; c++) {
+      // (open boundaries: a corner beyond the reach has weight exactly 0 -- the nearest cell that exists instead)
+      if constexpr (OPEN)
+        qc[c] = reach_position(S.rl, S.rr, reach_clamp(s4.ci[c], S.rl[0], S.rr[0]), reach_clamp(s4.cj[c], S.rl[1], S.rr[1]),
+                               reach_clamp(s4.ck[c], S.rl[2], S.rr[2]));
+      else
+        qc[c] = shell_position(s4.ci[c], s4.cj[c], s4.ck[c]);
+    }
     cin_HI = interp_column(s4, cs[col_out(qc[0], 0, cz)], cs[col_out(qc[1], 0, cz)], cs[col_out(qc[2], 0, cz)],
                            cs[col_out(qc[3], 0, cz)], sigma_HI_at_ion_freq);
     cin_HeI = interp_column(s4, cs[col_out(qc[0], 1, cz)], cs[col_out(qc[1], 1, cz)], cs[col_out(qc[2], 1, cz)],
@@ -461,7 +482,9 @@ __device__ __forceinline__ void sweep_cell_fast(const SweepArgs &A, const SrcDev
   const Grid &g = A.g;
   const StepScalars &sc = A.sc;
   int di, dj, dk;
-  const int face = shell_decode_fast(G, t, di, dj, dk);
+  ReachShell RS{}; // (open boundaries: t counts the cells of the shell cut at the source's reach)
+  if constexpr (OPEN) RS = reach_shell(S.rl, S.rr, G.s);
+  const int face = OPEN ? reach_decode(RS, t, di, dj, dk) : shell_decode_fast(G, t, di, dj, dk);
   Box cut_;
   if constexpr (OPEN) cut_ = source_box(A.box, S);
   const Box &box = OPEN ? cut_ : A.box; // (periodic: the launch's box itself)
@@ -469,13 +492,14 @@ __device__ __forceinline__ void sweep_cell_fast(const SweepArgs &A, const SrcDev
                       dk <= box.hi[2];
   if (!inside) return;
   const size_t cz = S.cz;
-  const size_t p = (size_t)G.off + (size_t)t;
+  const size_t p = (OPEN ? (size_t)RS.off : (size_t)G.off) + (size_t)t;
   global_double *cs = (global_double *)S.cols;
   const int i = mesh0<OPEN>(S.i0 - 1 + di, g.n1), j = mesh0<OPEN>(S.j0 - 1 + dj, g.n2), k = mesh0<OPEN>(S.k0 - 1 + dk, g.n3);
   double u_HI, u_HeI, u_HeII;
   sweep_cell_state(A, i, j, k, face == 2, u_HI, u_HeI, u_HeII);
   ShellCorners c4;
-  shell_short_characteristic(G, face, S.i0, S.j0, S.k0, di, dj, dk, c4);
+  if constexpr (OPEN) reach_short_characteristic(G, reach_shell(S.rl, S.rr, G.sp), S.rl, S.rr, face, S.i0, S.j0, S.k0, di, dj, dk, c4);
+  else shell_short_characteristic(G, face, S.i0, S.j0, S.k0, di, dj, dk, c4);
   double cin_HI = interp_column_fast(c4.s, cs[col_out((size_t)c4.p[0], 0, cz)], cs[col_out((size_t)c4.p[1], 0, cz)],
                                      cs[col_out((size_t)c4.p[2], 0, cz)], cs[col_out((size_t)c4.p[3], 0, cz)], sigma_HI_at_ion_freq);
   const double cin_HeI = interp_column_fast(c4.s, cs[col_out((size_t)c4.p[0], 1, cz)], cs[col_out((size_t)c4.p[1], 1, cz)],
@@ -513,20 +537,43 @@ __device__ __forceinline__ int sweep_block_cell(int cnt) {
   return t < cnt ? t : -1;
 }
 
-// (OPEN: up to 7/8 of the threads of a corner source's shell lie outside its reach; they leave after the decode and the
-// box test, before any memory access.)
+// The same for a source of an open launch, whose shell is cut at its reach and has `cnt` cells of its own: the launch is
+// sized for the largest cut shell among its sources (launch_shells), the eighths are those of the source's own blocks,
+// and the blocks beyond them leave at once.
+__device__ __forceinline__ int sweep_block_cell_open(int cnt) {
+  const int nblk_shell = (cnt + BLOCK - 1) / BLOCK;
+  int vb = (int)blockIdx.x;
+  if (nblk_shell >= 64) {
+    const int chunk = (nblk_shell + 7) >> 3;
+    if (vb >= 8 * chunk) return -1;
+    vb = (vb & 7) * chunk + (vb >> 3);
+  }
+  if (vb >= nblk_shell) return -1;
+  const int t = vb * BLOCK + (int)threadIdx.x;
+  return t < cnt ? t : -1;
+}
+
+// the cells of shell `shell` of source S (open boundaries: within its reach)
+template <bool OPEN>
+__device__ __forceinline__ int sweep_shell_cells(const SrcDev &S, int shell) {
+  if constexpr (OPEN) return (int)(reach_cells(S.rl, S.rr, shell) - reach_cells(S.rl, S.rr, shell - 1));
+  else return (int)shell_count(shell);
+}
+
 template <bool OPEN>
 __global__ void __launch_bounds__(BLOCK, C2R_SWEEP_WAVES)
 k_sweep_shell(SweepArgs A, const SrcDev *__restrict__ src, const int *__restrict__ active, int shell) {
-  const int t = sweep_block_cell((int)shell_count(shell));
-  if (t >= 0) sweep_cell<OPEN>(A, src[active[blockIdx.y]], shell, t);
+  const SrcDev &S = src[active[blockIdx.y]];
+  const int t = OPEN ? sweep_block_cell_open(sweep_shell_cells<OPEN>(S, shell)) : sweep_block_cell((int)shell_count(shell));
+  if (t >= 0) sweep_cell<OPEN>(A, S, shell, t);
 }
 
 template <bool OPEN>
 __global__ void __launch_bounds__(BLOCK, C2R_SWEEP_WAVES)
 k_sweep_shell_fast(SweepArgs A, const SrcDev *__restrict__ src, const int *__restrict__ active, ShellGeom G) {
-  const int t = sweep_block_cell(24 * G.s * G.s + 2);
-  if (t >= 0) sweep_cell_fast<OPEN>(A, src[active[blockIdx.y]], G, t);
+  const SrcDev &S = src[active[blockIdx.y]];
+  const int t = OPEN ? sweep_block_cell_open(sweep_shell_cells<OPEN>(S, G.s)) : sweep_block_cell(24 * G.s * G.s + 2);
+  if (t >= 0) sweep_cell_fast<OPEN>(A, S, G, t);
 }
 
 // photon_loss_src_thread(tn) += ... (evolve_point.F90:312): sum the block partials of all shells of
@@ -582,19 +629,22 @@ k_loss_probe_rounds(Grid g, const SrcDev *__restrict__ src, const int *__restric
     if (block_base[mid] <= B) lo = mid; else hi = mid - 1;
   }
   const int shell = lo;
-  const long long cnt = shell_count(shell);
+  ReachShell RS{}; // (open boundaries: the shell cut at the source's reach; its blocks are the first of the uncut shell's)
+  if constexpr (OPEN) RS = reach_shell(S.rl, S.rr, shell);
+  const long long cnt = OPEN ? (long long)RS.cnt : shell_count(shell);
   const int slot = threadIdx.x & 31;
   const long long t = (long long)(B - block_base[shell]) * BLOCK + (threadIdx.x >> 5) * 32;
   double loss = 0.0;
   if (t < cnt) {
     int di, dj, dk;
-    shell_decode(shell, (int)t, di, dj, dk);
+    if constexpr (OPEN) reach_decode(RS, (int)t, di, dj, dk);
+    else shell_decode(shell, (int)t, di, dj, dk);
     const bool inside = di >= box.lo[0] && di <= box.hi[0] && dj >= box.lo[1] && dj <= box.hi[1] && dk >= box.lo[2] &&
                         dk <= box.hi[2];
     const bool boundary = on_counted_face<OPEN>(box, S, di, dj, dk, 1);
     if (inside && boundary) {
       const size_t cz = S.cz;
-      const size_t p = (size_t)shell_offset(shell) + (size_t)t;
+      const size_t p = (OPEN ? (size_t)RS.off : (size_t)shell_offset(shell)) + (size_t)t;
       const global_double *cs = (const global_double *)S.cols;
       const double cin_HI = cs[col_in(p, 0, cz)], cin_HeI = cs[col_in(p, 1, cz)], cin_HeII = cs[col_in(p, 2, cz)];
       const double cout_HI = cs[col_out(p, 0, cz)], cout_HeI = cs[col_out(p, 1, cz)], cout_HeII = cs[col_out(p, 2, cz)];
@@ -649,7 +699,10 @@ k_col_to_grid(Grid g, SrcDev S, const double *__restrict__ cs, double *__restric
     dk = wrap0(dk + g.l3, g.n3) - g.l3;
   }
   const bool inside = di >= S.lo[0] && di <= S.hi[0] && dj >= S.lo[1] && dj <= S.hi[1] && dk >= S.lo[2] && dk <= S.hi[2];
-  const size_t p = shell_position(di, dj, dk);
+  // (open boundaries: only a cell of the box, which lies within the reach, has a position)
+  size_t p = 0;
+  if constexpr (OPEN) p = inside ? reach_position(S.rl, S.rr, di, dj, dk) : 0;
+  else p = shell_position(di, dj, dk);
   for (int c = 0; c < 3; c++) out[q + c * g.ncell] = inside ? cs[col_out(p, c, S.cz)] : 0.0;
 }
 
@@ -793,7 +846,7 @@ k_rates(Grid g, const SrcDev *__restrict__ src, int nsrc, StepScalars sc, const 
     if (outside) continue;
     touched = true;
     const size_t cz = S.cz;
-    const size_t p = shell_position(di, dj, dk);
+    const size_t p = OPEN ? reach_position(S.rl, S.rr, di, dj, dk) : shell_position(di, dj, dk);
     global_double *cs = (global_double *)S.cols;
     const double cout_HI = cs[col_out(p, 0, cz)];
     const double cin_HI = cs[col_in(p, 0, cz)], cin_HeI = cs[col_in(p, 1, cz)], cin_HeII = cs[col_in(p, 2, cz)];
@@ -1342,8 +1395,8 @@ k_evolve0d(SweepArgs A, SrcDev S, int di, int dj, int dk, const BandData *__rest
   const size_t nc = g.ncell;
   const int ia = di < 0 ? -di : di, ja = dj < 0 ? -dj : dj, ka = dk < 0 ? -dk : dk;
   const int shell = ia > ja ? (ia > ka ? ia : ka) : (ja > ka ? ja : ka);
-  const size_t p = shell_position(di, dj, dk);
-  sweep_cell<OPEN>(A, S, shell, (int)(p - (size_t)shell_offset(shell)));
+  const size_t p = OPEN ? reach_position(S.rl, S.rr, di, dj, dk) : shell_position(di, dj, dk);
+  sweep_cell<OPEN>(A, S, shell, (int)(p - (OPEN ? (size_t)reach_cells(S.rl, S.rr, shell - 1) : (size_t)shell_offset(shell))));
   __threadfence_block();
   const global_double *cs = (const global_double *)S.cols;
   const size_t cz = S.cz;
@@ -1634,6 +1687,10 @@ struct c2r_ctx {
   double *last_cols = nullptr;      // column block of the last source swept (c2r_download_columns)
   size_t last_cz = 0;
   int last_lo[3] = {0, 0, 0}, last_hi[3] = {0, 0, 0};
+  // c2r_get_source_trace: what the last pass that swept a source did for it, and when (a count of passes over all contexts
+  // of the process, so that a multi-device context can tell which of its devices swept the source last)
+  std::vector<c2r_source_trace> trace;
+  std::vector<long long> trace_stamp;
 
   double photon_loss[C2R_NFREQ] = {0};
   int sum_nbox = 0;
@@ -2258,6 +2315,8 @@ static int set_sources_one(c2r_ctx *c, int nsrc, const int *srcpos, const double
       if (it != known.end()) carried[(size_t)s] = it->second;
     }
     c->prev_nbox.swap(carried);
+    c->trace.clear(); // (c2r_get_source_trace: nothing has been swept of the new list)
+    c->trace_stamp.clear();
   }
   c->nsrc = nsrc;
   if (c->prev_nbox.size() != (size_t)nsrc) c->prev_nbox.assign((size_t)nsrc, 0);
@@ -2560,6 +2619,15 @@ static int source_smax(const c2r_ctx *c, int ns) {
   return m;
 }
 
+// entries per column array of source ns's block for the shells 0..cap: the whole shells, or (open boundaries) their cells
+// within the source's reach -- never more than the mesh has cells
+static size_t source_block_entries(const c2r_ctx *c, int ns, int cap) {
+  if (c->periodic) return block_doubles(cap) / 6;
+  const Reach R = source_reach(c, ns);
+  return (size_t)reach_cells(R.l, R.r, cap);
+}
+static size_t source_block_doubles(const c2r_ctx *c, int ns, int cap) { return 6 * source_block_entries(c, ns, cap); }
+
 static int predicted_shells(const c2r_ctx *c, int ns) {
   const int prev = c->prev_nbox[(size_t)ns - 1];
   const int grow = c->prev_grow.size() == c->prev_nbox.size() ? c->prev_grow[(size_t)ns - 1] : 0;
@@ -2603,10 +2671,10 @@ static int arena_prepare(c2r_ctx *c) {
     size_t sum = 0, spare = 0;
     for (size_t b = b0; b < std::min(mine.size(), b0 + (size_t)limit); b++) {
       const int cap = predicted_shells(c, mine[b]); // pass_list's predicted_cap
-      sum += block_doubles(cap);
+      sum += source_block_doubles(c, mine[b], cap);
       // ... and room for ONE source of the batch to outgrow that (its block then moves to one twice as deep)
       const int smax = source_smax(c, mine[b]);
-      if (cap < smax) spare = std::max(spare, block_doubles(std::min(smax, 2 * cap)));
+      if (cap < smax) spare = std::max(spare, source_block_doubles(c, mine[b], std::min(smax, 2 * cap)));
     }
     need[bi & 1] = std::max(need[bi & 1], sum + spare);
   }
@@ -2696,6 +2764,7 @@ struct SrcRun {
   int smax_prev = -1;     // largest shell already swept
   Reach reach{};          // how far its box can go: the mesh's with periodic boundaries, its own with open ones
   int smax = 0;           // the largest shell within that reach
+  long long sweep_threads = 0; // threads of the shell launches spent on it (c2r_get_source_trace)
 };
 
 // the sub-box after `nbox` rounds (evolve_source.F90:141-144)
@@ -2804,6 +2873,7 @@ struct PassCtx {
   bool packed_early = false;    // the mesh-ordered products need not wait for anything
   bool transposed_seen = false; // the sweep stream has waited for ev_transposed
   int nslab = 0;                // rate-grid slabs of the last batch (0: one rates launch)
+  long long stamp = 0;          // this pass in the count of all passes of the process (c2r_get_source_trace)
   std::vector<hipEvent_t> tev;  // per batch: sweep start, sweep end, rates start, rates end
 };
 
@@ -2947,15 +3017,14 @@ static int place_batch(const PassCtx &P, const std::vector<int> &mine, Batch &B)
     c->seg_used[set] = 0;
     c->vacated[set].clear();
     size_t total = 0;
-    for (int b = 0; b < B.nb; b++) total += block_doubles(predicted_shells(c, mine[B.b0 + b]));
+    for (int b = 0; b < B.nb; b++) total += source_block_doubles(c, mine[B.b0 + b], predicted_shells(c, mine[B.b0 + b]));
     int placed = 0;
     size_t placed_doubles = 0;
     for (; placed < B.nb; placed++) {
       SrcRun &r = B.run[placed];
       r.ns = mine[B.b0 + placed];
       r.cap = predicted_shells(c, r.ns);
-      const size_t w = (size_t)(2 * r.cap + 1);
-      hs[placed].cz = w * w * w;
+      hs[placed].cz = source_block_entries(c, r.ns, r.cap);
       hs[placed].cols = arena_alloc(c, set, 6 * hs[placed].cz, total);
       if (!hs[placed].cols) break;
       total -= 6 * hs[placed].cz;
@@ -2980,7 +3049,7 @@ static int place_batch(const PassCtx &P, const std::vector<int> &mine, Batch &B)
       for (int b = 0; b < keep; b++) {
         used += 6 * hs[b].cz;
         const int smax = source_smax(c, B.run[b].ns);
-        if (B.run[b].cap < smax) reserve += block_doubles(std::min(smax, 2 * B.run[b].cap));
+        if (B.run[b].cap < smax) reserve += source_block_doubles(c, B.run[b].ns, std::min(smax, 2 * B.run[b].cap));
       }
       if (keep <= 1 || used + reserve / 3 <= placed_doubles) break;
       keep--;
@@ -3067,8 +3136,8 @@ static int move_block(const PassCtx &P, Batch &B, int b, int ncap, double *ncols
   // probes in flight read this source's SrcDev entry: they must be through before the entry changes
   if (B.launched > B.settled) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_probe, 0));
   SrcDev &S = c->h_src[B.set][b];
-  const size_t wn = (size_t)(2 * ncap + 1), ncz = wn * wn * wn;
-  const size_t wp = (size_t)(2 * r.smax_prev + 1), have = r.smax_prev >= 0 ? wp * wp * wp : 0;
+  const size_t ncz = source_block_entries(c, r.ns, ncap);
+  const size_t have = r.smax_prev >= 0 ? source_block_entries(c, r.ns, r.smax_prev) : 0;
   // the shells stored so far are a prefix of each half, the incoming triples and the outgoing ones (col_in, col_out)
   for (int half = 0; half < 2 && have > 0; half++)
     HIPCHK(c, hipMemcpyAsync(ncols + 3 * half * ncz, S.cols + 3 * half * S.cz, sizeof(double) * 3 * have,
@@ -3112,6 +3181,7 @@ static int launch_shells(PassCtx &P, Batch &B, const Box &box, int s_lo, int s_h
   SA.g = c->g; SA.box = box; SA.sc = P.sc;
   SA.ndens = c->d_ndens; SA.xh_av = c->d_xh_av; SA.xhe_av = c->d_xhe_av;
   SA.lls_grid = c->lls_on_grid ? c->d_lls : nullptr;
+  const int *act = c->h_list[B.set] + act_off;
   if (c->timing && !B.sweep_started) {
     HIPCHK(c, hipEventRecord(B.ev[0], c->stream));
     B.sweep_started = true;
@@ -3125,10 +3195,23 @@ static int launch_shells(PassCtx &P, Batch &B, const Box &box, int s_lo, int s_h
     SA.packed = SA.packedT = nullptr;
     if (P.transposed_seen || P.packed_early) SA.packed = c->d_stateT;
     if (P.transposed_seen) SA.packedT = c->d_stateT + 3 * c->g.ncell;
-    const int nblk = c->block_base[s + 1] - c->block_base[s];
+    int nblk = c->block_base[s + 1] - c->block_base[s];
+    if (!c->periodic) {
+      // the largest shell s among the active sources, each cut at its own reach; blocks beyond a source's own leave at once
+      long long most = 0;
+      for (int a = 0; a < nact; a++) {
+        const Reach &R = B.run[act[a]].reach;
+        most = std::max(most, reach_cells(R.l, R.r, s) - reach_cells(R.l, R.r, s - 1));
+      }
+      nblk = (int)((most + BLOCK - 1) / BLOCK);
+      if (nblk == 0) continue;
+    }
     // from 64 blocks on: a multiple of 8 blocks, one contiguous eighth of the shell per XCD (see the kernel)
     const int nlaunch = nblk >= 64 ? ((nblk + 7) & ~7) : nblk;
-    const bool fast = s >= 2 && s <= SHELL_FAST_MAX && !P.generic_sweep;
+    for (int a = 0; a < nact; a++)
+      if (s <= B.run[act[a]].smax) B.run[act[a]].sweep_threads += (long long)nlaunch * BLOCK;
+    // (open boundaries: positions are below the mesh's cell count, 32 bits hold them in every shell)
+    const bool fast = s >= 2 && (s <= SHELL_FAST_MAX || !c->periodic) && !P.generic_sweep;
     if (fast && c->periodic)
       hipLaunchKernelGGL(k_sweep_shell_fast<false>, dim3(nlaunch, nact), dim3(BLOCK), 0, c->stream, SA, c->d_src[B.set],
                          c->d_list[B.set] + act_off, c->shell_geom[(size_t)s]);
@@ -3202,7 +3285,7 @@ static int sweep_batch(PassCtx &P, Batch &B) {
       const int need = std::min(s_hi, B.run[act[a]].smax);
       if (cap >= need) continue;
       const int ncap = std::min(B.run[act[a]].smax, std::max(need, 2 * cap));
-      double *ncols = arena_alloc(c, B.set, block_doubles(ncap));
+      double *ncols = arena_alloc(c, B.set, source_block_doubles(c, B.run[act[a]].ns, ncap));
       if (!ncols) return start_over(P, B, round);
       if (move_block(P, B, act[a], ncap, ncols)) return 1;
     }
@@ -3275,6 +3358,17 @@ static int close_boxes(PassCtx &P, Batch &B) {
     const int known = B.known0[(size_t)b];
     c->prev_grow[(size_t)r.ns - 1] = known > 0 ? std::max(0, r.nbox - known) : 0;
     c->prev_nbox[(size_t)r.ns - 1] = r.nbox;
+    c2r_source_trace &T = c->trace[(size_t)r.ns - 1];
+    for (int d = 0; d < 3; d++) {
+      T.reach_l[d] = r.reach.l[d]; T.reach_r[d] = r.reach.r[d];
+      T.box_lo[d] = r.nbox > 0 ? fb.lo[d] : 0; T.box_hi[d] = r.nbox > 0 ? fb.hi[d] : 0;
+    }
+    T.nbox = r.nbox;
+    T.block_shells = r.cap;
+    T.block_cells = (long long)S.cz;
+    T.swept_cells = r.nbox > 0 ? box_cells(fb) : 0;
+    T.sweep_threads = r.sweep_threads;
+    c->trace_stamp[(size_t)r.ns - 1] = P.stamp;
   }
   if (c->timing) { // the sweep's span: from the first shell launch to the last, record uploads on either side left out
     if (!B.sweep_started) HIPCHK(c, hipEventRecord(B.ev[0], c->stream));
@@ -3548,6 +3642,12 @@ static int pass_list(c2r_ctx *c, const std::vector<int> &mine, int nslab = 0) {
   // this list; entries still here belong to a pass that ended in an error and must not be added to this one
   c->tails.clear();
   if (c->prev_nbox.size() != (size_t)c->nsrc) c->prev_nbox.assign((size_t)c->nsrc, 0);
+  if (c->trace.size() != (size_t)c->nsrc) {
+    c->trace.assign((size_t)c->nsrc, c2r_source_trace{});
+    c->trace_stamp.assign((size_t)c->nsrc, 0);
+  }
+  static std::atomic<long long> passes{0};
+  P.stamp = ++passes;
   // a rank without sources writes nothing: a pending zeroing of the rate grids has to happen for real
   if (mine.empty() && flush_rates_zero(c)) return 1;
   // everything queued earlier on the main stream (state upload, zeroing of the rates) must be
@@ -3820,7 +3920,8 @@ extern "C" int c2r_evolve0d(c2r_ctx *c, const int rtpos[3], int ns, int niter, i
     return fail(c, "c2r_evolve0d: cell (%d,%d,%d) is beyond the reach of source %d at (%d,%d,%d)", rtpos[0], rtpos[1], rtpos[2], ns,
                 sp[0], sp[1], sp[2]);
   if (flush_rates_zero(c)) return 1;
-  const size_t w = (size_t)(2 * g.smax + 1), cz = w * w * w;
+  // (open boundaries: the cells within a source's reach, in its own cut shell order, are never more than the mesh has)
+  const size_t w = (size_t)(2 * g.smax + 1), cz = c->periodic ? w * w * w : g.ncell;
   if (!c->d_point_cols) {
     // a block that holds the whole mesh, zeroed once: only ever finite columns afterwards (see the arena)
     HIPCHK(c, hipMalloc(&c->d_point_cols, sizeof(double) * 6 * cz));
@@ -4098,6 +4199,8 @@ extern "C" int c2r_download_columns(c2r_ctx *c, double *coldensh_out, double *co
   S.i0 = p[0]; S.j0 = p[1]; S.k0 = p[2];
   for (int d = 0; d < 3; d++) { S.lo[d] = c->last_lo[d]; S.hi[d] = c->last_hi[d]; }
   S.cz = c->last_cz;
+  const Reach R = source_reach(c, c->last_src);
+  for (int d = 0; d < 3; d++) { S.rl[d] = R.l[d]; S.rr[d] = R.r[d]; }
   if (c->periodic) hipLaunchKernelGGL(k_col_to_grid<false>, dim3(nblk), dim3(BLOCK), 0, c->stream, c->g, S, c->last_cols, c->d_colgrid);
   else hipLaunchKernelGGL(k_col_to_grid<true>, dim3(nblk), dim3(BLOCK), 0, c->stream, c->g, S, c->last_cols, c->d_colgrid);
   HIPCHK(c, hipGetLastError());
@@ -4205,6 +4308,30 @@ extern "C" int c2r_arena_stats(const c2r_ctx *c, long long out[6]) {
   if (!c || !out) return 1;
   for (int i = 0; i < 5; i++) out[i] = c->arena_stats[i];
   out[5] = (long long)c->arena_total;
+  return 0;
+}
+extern "C" int c2r_get_source_trace(c2r_ctx *c, int ns, c2r_source_trace *out) {
+  if (!c || !out) return 1;
+  if (ns < 1 || ns > c->nsrc) return fail(c, "c2r_get_source_trace: source %d not in [1,%d]", ns, c->nsrc);
+  // the context itself or, of a multi-device context, the device that swept the source last
+  const c2r_ctx *from = nullptr;
+  long long stamp = 0;
+  auto look = [&](const c2r_ctx *r) {
+    if (r->trace_stamp.size() >= (size_t)ns && r->trace_stamp[(size_t)ns - 1] > stamp) {
+      stamp = r->trace_stamp[(size_t)ns - 1];
+      from = r;
+    }
+  };
+  look(c);
+  for (const c2r_ctx *r : c->replicas) look(r);
+  if (from) {
+    *out = from->trace[(size_t)ns - 1];
+    return 0;
+  }
+  // not swept yet: its reach, and nothing else
+  *out = c2r_source_trace{};
+  const Reach R = source_reach(c, ns);
+  for (int d = 0; d < 3; d++) { out->reach_l[d] = R.l[d]; out->reach_r[d] = R.r[d]; }
   return 0;
 }
 extern "C" size_t c2r_rates_count(const c2r_ctx *c) { return c ? c->rates_count : 0; }
@@ -4366,6 +4493,8 @@ static int set_boundaries_one(c2r_ctx *c, int periodic) {
   }
   c->prev_nbox.assign((size_t)c->nsrc, 0);
   c->prev_grow.assign((size_t)c->nsrc, 0);
+  c->trace.clear();
+  c->trace_stamp.clear();
   c->last_src = 0;
   c->last_cols = nullptr;
   return 0;

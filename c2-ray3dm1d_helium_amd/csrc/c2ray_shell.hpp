@@ -220,6 +220,169 @@ C2R_HD void shell_short_characteristic(const ShellGeom &G, int face, int i0, int
   }
 }
 
+// ----------------------------------------------------------------------------------------------------------------
+// The shell order cut at a source's REACH (open boundaries): a source at the mesh position p reaches l_d = 1 - p_d <= 0
+// cells to the left and r_d = mesh_d - p_d >= 0 to the right along axis d, and only those cells exist.  Shell s of
+// such a source is the L-infinity shell cut at the box [l, r]:
+//   lo_d(s) = max(l_d, -s), hi_d(s) = min(r_d, s), e_d(s) = hi_d(s) - lo_d(s) + 1,
+// and it occupies the positions [E(s-1), E(s)) of a column array, E(s) = e_x(s) e_y(s) e_z(s), E(-1) = 0: the arrays stay
+// prefixes of one another, a block that holds the shells 0..cap has E(cap) <= n1 n2 n3 entries.  Within a shell the order
+// of the uncut one with the faces that do not exist left out and the others cut: k-faces (+s if s <= r_z, then -s if
+// s <= -l_z; e_x(s) e_y(s) cells, i fastest from lo_x(s), rows j from lo_y(s)), j-faces (s <= r_y, s <= -l_y;
+// e_x(s) e_z(s-1) cells, i fastest, rows k from lo_z(s-1)), i-faces (s <= r_x, s <= -l_x; e_y(s-1) e_z(s-1) cells, j
+// fastest from lo_y(s-1), rows k from lo_z(s-1)).  With l = -cap, r = cap this is shell_position entry for entry
+// (tests/test_reach_shell_host.py).
+C2R_HD int reach_lo(int l, int s) { return l > -s ? l : -s; }
+C2R_HD int reach_hi(int r, int s) { return r < s ? r : s; }
+// E(s): entries of a column array that holds the shells 0..s of a source with reach [l, r]
+C2R_HD long long reach_cells(const int *l, const int *r, int s) {
+  if (s < 0) return 0;
+  long long e = 1;
+  for (int d = 0; d < 3; d++) e *= (long long)(reach_hi(r[d], s) - reach_lo(l[d], s) + 1);
+  return e;
+}
+
+// Shell s of one source: where its faces begin and how wide their rows are.  Six integers and the shell in, a few
+// integer operations, all uniform over a block (the sweep and loss kernels derive it from SrcDev in scalar registers).
+struct ReachShell {
+  int s;
+  int lox, loy;        // lo_x(s), lo_y(s): first column of a k- or j-face row, first row of a k-face
+  int loyp, lozp;      // lo_y(s-1), lo_z(s-1): first column of an i-face row, first row of a j- or i-face
+  int ex, eyp;         // e_x(s), e_y(s-1): cells of a row on the k- and j-faces, on the i-faces
+  int b1, b2, b3, b4, b5; // first thread of the faces -k, +j, -j, +i, -i (+k begins at 0; a face that does not exist is empty)
+  int cnt;             // cells of the shell, E(s) - E(s-1)
+  uint32_t off;        // E(s-1): positions are below n1 n2 n3 < 2^31 for every mesh c2r_create accepts
+};
+C2R_HD ReachShell reach_shell(const int *l, const int *r, int s) {
+  ReachShell G;
+  G.s = s;
+  G.lox = reach_lo(l[0], s);
+  G.loy = reach_lo(l[1], s);
+  G.ex = reach_hi(r[0], s) - G.lox + 1;
+  const int ey = reach_hi(r[1], s) - G.loy + 1;
+  if (s == 0) { // one cell, kept on the +k face
+    G.loyp = G.lozp = 0;
+    G.eyp = 1;
+    G.b1 = G.b2 = G.b3 = G.b4 = G.b5 = G.cnt = 1;
+    G.off = 0;
+    return G;
+  }
+  G.loyp = reach_lo(l[1], s - 1);
+  G.lozp = reach_lo(l[2], s - 1);
+  G.eyp = reach_hi(r[1], s - 1) - G.loyp + 1;
+  const int exp_ = reach_hi(r[0], s - 1) - reach_lo(l[0], s - 1) + 1;
+  const int ezp = reach_hi(r[2], s - 1) - G.lozp + 1;
+  const int A = G.ex * ey, B = G.ex * ezp, C = G.eyp * ezp;
+  G.b1 = s <= r[2] ? A : 0;
+  G.b2 = G.b1 + (s <= -l[2] ? A : 0);
+  G.b3 = G.b2 + (s <= r[1] ? B : 0);
+  G.b4 = G.b3 + (s <= -l[1] ? B : 0);
+  G.b5 = G.b4 + (s <= r[0] ? C : 0);
+  G.cnt = G.b5 + (s <= -l[0] ? C : 0);
+  G.off = (uint32_t)(exp_ * G.eyp * ezp);
+  return G;
+}
+
+// thread t in [0, G.cnt) of the shell -> offset from the source; also tells the face as shell_decode_fast does
+// (selects on VALUES, see there; the row by a division with a divisor that is uniform over the block)
+C2R_HD int reach_decode(const ReachShell &G, int t, int &di, int &dj, int &dk) {
+  const int s = G.s;
+  const int face = t < G.b2 ? 0 : (t < G.b4 ? 1 : 2);
+  const int first = face == 0 ? 0 : (face == 1 ? G.b2 : G.b4); // first cell of the pair of faces
+  const int mid = face == 0 ? G.b1 : (face == 1 ? G.b3 : G.b5); // first cell of its - face
+  const int width = face == 2 ? G.eyp : G.ex;
+  const bool neg = t >= mid;
+  const uint32_t u = (uint32_t)(t - (neg ? mid : first));
+  const uint32_t row = u / (uint32_t)width;
+  const int col = (int)(u - row * (uint32_t)width);
+  const int a = col + (face == 2 ? G.loyp : G.lox); // the coordinate that runs fastest
+  const int b = (int)row + (face == 0 ? G.loy : G.lozp); // the one that counts the rows
+  const int c = neg ? -s : s;                       // the one that is fixed on the face
+  di = face == 2 ? c : a;
+  dj = face == 0 ? b : (face == 1 ? c : a);
+  dk = face == 0 ? c : b;
+  return face;
+}
+
+// position within shell G.s (without G.off) of a cell known to lie in that shell and in reach
+C2R_HD int reach_position_in_shell(const ReachShell &G, int i, int j, int k) {
+  const int s = G.s;
+  const int ja = j < 0 ? -j : j, ka = k < 0 ? -k : k;
+  const int tk = (k > 0 ? 0 : G.b1) + (j - G.loy) * G.ex + (i - G.lox);
+  const int tj = (j > 0 ? G.b2 : G.b3) + (k - G.lozp) * G.ex + (i - G.lox);
+  const int ti = (i > 0 ? G.b4 : G.b5) + (k - G.lozp) * G.eyp + (j - G.loyp);
+  return s == 0 ? 0 : (ka == s ? tk : (ja == s ? tj : ti));
+}
+
+// inverse of reach_decode over all shells: position of the in-reach cell at offset (di,dj,dk) in a column array
+C2R_HD size_t reach_position(const int *l, const int *r, int di, int dj, int dk) {
+  const int ia = di < 0 ? -di : di, ja = dj < 0 ? -dj : dj, ka = dk < 0 ? -dk : dk;
+  const int s = ia > ja ? (ia > ka ? ia : ka) : (ja > ka ? ja : ka);
+  const ReachShell G = reach_shell(l, r, s);
+  return (size_t)G.off + (size_t)reach_position_in_shell(G, di, dj, dk);
+}
+
+// x clamped into [lo, hi]
+C2R_HD int reach_clamp(int x, int lo, int hi) { return x < lo ? lo : (x > hi ? hi : x); }
+
+// shell_short_characteristic for a cell of the cut shell G.s >= 2 (Gp: shell G.s - 1 of the same source): the same
+// weights and path, the corners' positions in the cut layout.  A corner of weight exactly 0 may lie beyond shell s-1
+// (the cell sits on an edge of its face) or beyond the reach (the cell sits on the source's own row or plane at a mesh
+// face): it is read from the nearest cell of shell s-1 that exists, so every position is below E(s-1).
+C2R_HD void reach_short_characteristic(const ShellGeom &G, const ReachShell &Gp, const int *l, const int *r, int face, int i0,
+                                       int j0, int k0, int di, int dj, int dk, ShellCorners &sc) {
+  const int sp = G.sp;
+  const int da = face == 2 ? dj : di, db = face == 0 ? dj : dk;
+  const int a0 = face == 2 ? j0 : i0, b0 = face == 0 ? j0 : k0;
+  const int sga = da >= 0 ? 1 : -1, sgb = db >= 0 ? 1 : -1;
+  const int am = da - sga, bm = db - sgb; // the cell closer to the source along each in-plane axis
+  const double fa = (double)da, fb = (double)db;
+  const double ac = G.alam * fa + (double)a0, bc = G.alam * fb + (double)b0;
+  const double ea = 2.0 * fabs(ac - ((double)(a0 + am) + 0.5 * sga));
+  const double eb = 2.0 * fabs(bc - ((double)(b0 + bm) + 0.5 * sgb));
+  sc.s[0] = (1. - ea) * (1. - eb);
+  sc.s[1] = (1. - eb) * ea;
+  sc.s[2] = (1. - ea) * eb;
+  sc.s[3] = ea * eb;
+  const double num = fa * fa + fb * fb;
+  const double q0 = num * G.rn2;
+  const double quo = __builtin_fma(__builtin_fma(-G.n2, q0, num), G.rn2, q0);
+  sc.path = sqrt(quo + 1.0);
+  // the in-plane ranges of shell s-1 within the reach
+  const int la = face == 2 ? l[1] : l[0], ra = face == 2 ? r[1] : r[0];
+  const int lb = face == 0 ? l[1] : l[2], rb = face == 0 ? r[1] : r[2];
+  const int alo = reach_lo(la, sp), ahi = reach_hi(ra, sp), blo = reach_lo(lb, sp), bhi = reach_hi(rb, sp);
+  const int a1 = reach_clamp(am, alo, ahi), a2 = reach_clamp(da, alo, ahi);
+  const int b1 = reach_clamp(bm, blo, bhi), b2 = reach_clamp(db, blo, bhi);
+  const int dc = face == 0 ? dk : (face == 1 ? dj : di);
+  const int cm = dc > 0 ? sp : -sp; // the plane one step closer to the source
+  const uint32_t offp = Gp.off;
+  if (face == 0) {
+    // both rows lie in the k-face of shell s-1
+    const int base = (cm > 0 ? 0 : Gp.b1) - Gp.lox;
+    const int r1 = base + (b1 - Gp.loy) * Gp.ex, r2 = base + (b2 - Gp.loy) * Gp.ex;
+    sc.p[0] = offp + (uint32_t)(r1 + a1);
+    sc.p[1] = offp + (uint32_t)(r1 + a2);
+    sc.p[2] = offp + (uint32_t)(r2 + a1);
+    sc.p[3] = offp + (uint32_t)(r2 + a2);
+  } else if (face == 1) {
+    // a row (fixed k') of the plane j' = cm lies in a k-face of shell s-1 if |k'| == s-1, else in its j-face
+    const int rk = (cm - Gp.loy) * Gp.ex - Gp.lox, rj = (cm > 0 ? Gp.b2 : Gp.b3) - Gp.lozp * Gp.ex - Gp.lox;
+    const int b1a = b1 < 0 ? -b1 : b1, b2a = b2 < 0 ? -b2 : b2;
+    const int r1 = b1a == sp ? (b1 > 0 ? 0 : Gp.b1) + rk : rj + b1 * Gp.ex;
+    const int r2 = b2a == sp ? (b2 > 0 ? 0 : Gp.b1) + rk : rj + b2 * Gp.ex;
+    sc.p[0] = offp + (uint32_t)(r1 + a1);
+    sc.p[1] = offp + (uint32_t)(r1 + a2);
+    sc.p[2] = offp + (uint32_t)(r2 + a1);
+    sc.p[3] = offp + (uint32_t)(r2 + a2);
+  } else {
+    sc.p[0] = offp + (uint32_t)reach_position_in_shell(Gp, cm, a1, b1);
+    sc.p[1] = offp + (uint32_t)reach_position_in_shell(Gp, cm, a2, b1);
+    sc.p[2] = offp + (uint32_t)reach_position_in_shell(Gp, cm, a1, b2);
+    sc.p[3] = offp + (uint32_t)reach_position_in_shell(Gp, cm, a2, b2);
+  }
+}
+
 // 1 / max(0.6, cd * sig) (weightf, column_density.f90:351-376): the argument of the reciprocal lies in
 // [0.6, 1.2e291] for every finite column, where recip_nr (the division's own instruction sequence without operand
 // scaling) is exact

@@ -343,6 +343,15 @@ class HipEngine:
         self._chk(self.lib.c2r_arena_stats(self.h, out))
         return dict(zip(("segments", "segments_in_pass", "doubles_allocated", "block_moves", "batch_restarts", "doubles_held"), out))
 
+    def source_trace(self, ns):
+        """c2r_get_source_trace for source `ns` (1-based) as a dict: reach, rounds, final sub-box, the column block's shells
+        and entries, cells traced and threads the shell launches spent on it in the last pass that swept it."""
+        t = _lib.SourceTrace()
+        self._chk(self.lib.c2r_get_source_trace(self.h, int(ns), C.byref(t)))
+        out = {k: list(getattr(t, k)) for k in ("reach_l", "reach_r", "box_lo", "box_hi")}
+        out.update({k: int(getattr(t, k)) for k in ("nbox", "block_shells", "block_cells", "swept_cells", "sweep_threads")})
+        return out
+
     def scale_ndens(self, divisor):
         """cosmo_evol's ndens = ndens / zfactor3 on the device copy (cosmology.f90:193)."""
         self._chk(self.lib.c2r_scale_ndens(self.h, float(divisor)))

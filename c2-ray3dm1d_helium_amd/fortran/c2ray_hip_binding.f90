@@ -16,6 +16,17 @@ module c2ray_hip
      integer(c_long_long) :: cells_swept
   end type c2r_timing
 
+  !> c2r_source_trace of include/c2ray_hip.h: what the last pass that swept a source did for it
+  type, bind(C) :: c2r_source_trace
+     integer(c_int) :: reach_l(3), reach_r(3)
+     integer(c_int) :: nbox
+     integer(c_int) :: box_lo(3), box_hi(3)
+     integer(c_int) :: block_shells
+     integer(c_long_long) :: block_cells
+     integer(c_long_long) :: swept_cells
+     integer(c_long_long) :: sweep_threads
+  end type c2r_source_trace
+
   !> c2r_iteration_report of include/c2ray_hip.h: what evolve3D's loop reports about one outer iteration
   type, bind(C) :: c2r_iteration_report
      integer(c_int) :: conv_flag
@@ -531,6 +542,14 @@ module c2ray_hip
        integer(c_int), value :: idev
        type(c2r_timing), intent(out) :: tm
      end function c2r_get_timing_device
+
+     !> ns is 1-based; host bookkeeping only, no device copy
+     integer(c_int) function c2r_get_source_trace(ctx, ns, trace) bind(C, name="c2r_get_source_trace")
+       import :: c_int, c_ptr, c2r_source_trace
+       type(c_ptr), value :: ctx
+       integer(c_int), value :: ns
+       type(c2r_source_trace), intent(out) :: trace
+     end function c2r_get_source_trace
 
      integer(c_int) function c2r_get_timing(ctx, tm) bind(C, name="c2r_get_timing")
        import :: c_int, c_ptr, c2r_timing

@@ -272,8 +272,10 @@ int c2r_set_batch(c2r_ctx *ctx, int nbatch);
  * between c2r_pass_sources_begin and c2r_pass_sources_end.  c2r_pass_sources, c2r_pass_sources_begin, c2r_do_source,
  * c2r_evolve0d (whose cell must lie within the source's reach: inside the mesh), c2r_iteration, c2r_evolve3d,
  * c2r_pass_allreduce_chemistry and c2r_download_columns honour the mode.
- * Memory: the column block of a source in a corner holds (2(N-1)+1)^3 cells of 48 bytes -- 6.4 GB at N = 256 against
- * 0.8 GB with periodic boundaries; blocks are sized per source, from its own reach. */
+ * Memory: the column block of a source holds the cells within its reach and nothing else, in a shell order cut at that
+ * reach (csrc/c2ray_shell.hpp): prod_d(r_d - l_d + 1) <= N^3 cells of 48 bytes at the mesh limit wherever the source
+ * sits -- 0.8 GB at N = 256, never more than a periodic block -- and a shell launch holds threads for the cells of the
+ * cut shell only.  c2r_get_source_trace reports both per source. */
 int c2r_set_boundaries(c2r_ctx *ctx, int periodic);
 /* 1: periodic, 0: open */
 int c2r_get_boundaries(const c2r_ctx *ctx);
@@ -440,6 +442,25 @@ int c2r_get_timing(c2r_ctx *ctx, c2r_timing *out);
 int c2r_arena_stats(const c2r_ctx *ctx, long long out[6]);
 /* the same for device `idev` (0 .. c2r_num_devices-1) of a context made by c2r_create_multi */
 int c2r_get_timing_device(c2r_ctx *ctx, int idev, c2r_timing *out);
+/* What the last pass that swept source ns (1-based) did for it, from the host's bookkeeping (no device copy, no
+ * synchronisation; both boundary modes).  reach_l <= 0 <= reach_r: how far the source's box can go per axis (the mesh's
+ * reach with periodic boundaries, the source's own with open ones); nbox: its rounds (0, with everything below 0, while
+ * it has not been swept since the source list or the boundary mode was set); box_lo / box_hi: its final sub-box as
+ * offsets from the source; block_shells: the shells its column block could hold at the end; block_cells: entries per
+ * column array of that block -- (2 block_shells + 1)^3 periodic, the cells of those shells within the reach open;
+ * swept_cells: cells of the final sub-box; sweep_threads: threads the shell launches of that pass spent on it, the
+ * launches' x-extent times the block size summed over its shells.  A multi-device context answers from the device that
+ * swept ns last. */
+typedef struct {
+  int reach_l[3], reach_r[3];
+  int nbox;
+  int box_lo[3], box_hi[3];
+  int block_shells;
+  long long block_cells;
+  long long swept_cells;
+  long long sweep_threads;
+} c2r_source_trace;
+int c2r_get_source_trace(c2r_ctx *ctx, int ns, c2r_source_trace *out);
 int c2r_enable_timing(c2r_ctx *ctx, int on);
 
 #ifdef __cplusplus
