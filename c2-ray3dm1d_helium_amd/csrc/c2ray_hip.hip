@@ -63,8 +63,11 @@ struct SrcDev {
   int loss_lo;         // >= 0: the rates launch leaves, for every surface cell of the final sub-box in shells >= loss_lo,
                        // the photons that leave the box through it in the cell's N_in(HI) slot (k_loss_stored adds
                        // them up); -1: no such request (set before the rates launch)
-  int rl[3], rr[3];    // open boundaries only: the source's reach, -min(max_subbox, srcpos - 1) and min(max_subbox, mesh - srcpos)
-                       // (the else branch of evolve_source.F90:103-109); the periodic kernels never read them
+  int rl[3], rr[3];    // open and mixed boundaries only: the source's reach per axis (axis_reach, c2ray_shell.hpp: the else
+                       // branch of evolve_source.F90:103-109 on an open axis, the then-branch on a periodic one); the
+                       // all-periodic kernels never read them
+  int wn[3];           // likewise: the wrap extent of each axis (axis_wrap_extent: the mesh extent if the axis is periodic
+                       // while another is open, 0 if it is open)
 };
 // the sub-box of the round in flight: the same for every active source of a batch (all are in the same round)
 struct Box {
@@ -73,6 +76,9 @@ struct Box {
 // Open (non-periodic) boundaries: nothing wraps, so a source's sub-box is the round's box cut at the source's own reach,
 // and it differs from source to source within a round.  OPEN is a template parameter of every kernel that looks at a
 // box: the periodic instantiations are the code they were before the open ones existed.
+// Mixed boundaries (c2r_set_boundaries_axes: some axes periodic, the others open) run on the OPEN instantiations: a
+// periodic axis there is an axis whose reach is the mesh's and whose mesh index wraps by SrcDev::wn, a value that is
+// uniform over a block and 0 on an open axis, where the wrap is then the identity (axis_wrap, c2ray_shell.hpp).
 __device__ __forceinline__ Box source_box(const Box &box, const SrcDev &S) {
   Box b;
   for (int d = 0; d < 3; d++) {
@@ -94,19 +100,13 @@ struct StepScalars {
   double coldensh_lls;  // material: coldensh_LLS (type_of_LLS = 1)
 };
 
-__device__ __forceinline__ int wrap0(int x, int n) { // 0-based periodic index of x in [-n, 2n)
-  // of x, x + n and x - n exactly one lies in [0, n); read as unsigned numbers it is the smallest of the three
-  // (v_add, v_sub, v_min3_u32 instead of two compares, two selects and the arithmetic)
-  const unsigned u = (unsigned)x, m = (unsigned)n;
-  const unsigned a = u + m, b = u - m;
-  const unsigned lo = a < b ? a : b;
-  return (int)(u < lo ? u : lo);
-}
+// 0-based periodic index of x in [-n, 2n) (axis_wrap, c2ray_shell.hpp)
+__device__ __forceinline__ int wrap0(int x, int n) { return axis_wrap(x, n); }
 
-// 0-based mesh index of the cell at offset x from the origin: periodic, or as it is (open boundaries: a cell of a source's
-// box lies in the mesh)
+// 0-based mesh index of the cell at offset x from the origin: periodic, or (open and mixed boundaries: a cell of a source's
+// box lies in the mesh along an open axis) wrapped by the axis's wrap extent w, which is 0 on an open axis
 template <bool OPEN>
-__device__ __forceinline__ int mesh0(int x, int n) { return OPEN ? x : wrap0(x, n); }
+__device__ __forceinline__ int mesh0(int x, int n, int w) { return OPEN ? axis_wrap(x, w) : wrap0(x, n); }
 
 // Does a surface cell of the sub-box `b` count?  Periodic boundaries, and the loss that is KEPT (photon_loss) in open
 // ones: every cell with a coordinate on a face.  The loss that DECIDES whether an open box grows once more (movable_only):
@@ -427,7 +427,8 @@ __device__ __forceinline__ void sweep_cell(const SweepArgs &A, const SrcDev &S, 
   const size_t cz = S.cz;
   const size_t p = (OPEN ? (size_t)RS.off : (size_t)shell_offset(shell)) + (size_t)t;
   global_double *cs = (global_double *)S.cols;
-  const int i = mesh0<OPEN>(S.i0 - 1 + di, g.n1), j = mesh0<OPEN>(S.j0 - 1 + dj, g.n2), k = mesh0<OPEN>(S.k0 - 1 + dk, g.n3);
+  const int i = mesh0<OPEN>(S.i0 - 1 + di, g.n1, S.wn[0]), j = mesh0<OPEN>(S.j0 - 1 + dj, g.n2, S.wn[1]),
+            k = mesh0<OPEN>(S.k0 - 1 + dk, g.n3, S.wn[2]);
   const int w_ = 2 * shell + 1;
   double u_HI, u_HeI, u_HeII;
   sweep_cell_state(A, i, j, k, shell > 0 && t >= (OPEN ? RS.b4 : 2 * w_ * w_ + 2 * (w_ - 2) * w_), u_HI, u_HeI, u_HeII);
@@ -494,7 +495,8 @@ __device__ __forceinline__ void sweep_cell_fast(const SweepArgs &A, const SrcDev
   const size_t cz = S.cz;
   const size_t p = (OPEN ? (size_t)RS.off : (size_t)G.off) + (size_t)t;
   global_double *cs = (global_double *)S.cols;
-  const int i = mesh0<OPEN>(S.i0 - 1 + di, g.n1), j = mesh0<OPEN>(S.j0 - 1 + dj, g.n2), k = mesh0<OPEN>(S.k0 - 1 + dk, g.n3);
+  const int i = mesh0<OPEN>(S.i0 - 1 + di, g.n1, S.wn[0]), j = mesh0<OPEN>(S.j0 - 1 + dj, g.n2, S.wn[1]),
+            k = mesh0<OPEN>(S.k0 - 1 + dk, g.n3, S.wn[2]);
   double u_HI, u_HeI, u_HeII;
   sweep_cell_state(A, i, j, k, face == 2, u_HI, u_HeI, u_HeII);
   ShellCorners c4;
@@ -697,6 +699,10 @@ k_col_to_grid(Grid g, SrcDev S, const double *__restrict__ cs, double *__restric
     di = wrap0(di + g.l1, g.n1) - g.l1;
     dj = wrap0(dj + g.l2, g.n2) - g.l2;
     dk = wrap0(dk + g.l3, g.n3) - g.l3;
+  } else { // per axis: wrapped where the axis is periodic, as it is where it is open
+    di = axis_offset(i, S.i0, S.wn[0]);
+    dj = axis_offset(j, S.j0, S.wn[1]);
+    dk = axis_offset(k, S.k0, S.wn[2]);
   }
   const bool inside = di >= S.lo[0] && di <= S.hi[0] && dj >= S.lo[1] && dj <= S.hi[1] && dk >= S.lo[2] && dk <= S.hi[2];
   // (open boundaries: only a cell of the box, which lies within the reach, has a position)
@@ -725,7 +731,8 @@ k_col_to_grid(Grid g, SrcDev S, const double *__restrict__ cs, double *__restric
 #ifndef C2R_RATES_WAVES_HEAT_MULTI
 #define C2R_RATES_WAVES_HEAT_MULTI 4
 #endif
-// OPEN (open boundaries): the offset of a cell from a source is what it is, no modulo; the final sub-box and the surface
+// OPEN (open and mixed boundaries): the offset of a cell from a source is what it is along an open axis, no modulo, and
+// the image within the mesh's reach along a periodic one (axis_offset); the final sub-box and the surface
 // test come from S.lo / S.hi as they always did.  Instantiations of their own: the periodic kernels have no issue slot
 // to spare and stay the code they were.
 template <bool HEAT, bool MULTI, bool OPEN = false>
@@ -837,6 +844,10 @@ k_rates(Grid g, const SrcDev *__restrict__ src, int nsrc, StepScalars sc, const 
       di = wrap0(di + g.l1, g.n1) - g.l1;
       dj = wrap0(dj + g.l2, g.n2) - g.l2;
       dk = wrap0(dk + g.l3, g.n3) - g.l3;
+    } else { // per axis: wrapped where the axis is periodic (S.wn is uniform over the block), as it is where it is open
+      di = axis_offset(i, S.i0, S.wn[0]);
+      dj = axis_offset(j, S.j0, S.wn[1]);
+      dk = axis_offset(k, S.k0, S.wn[2]);
     }
     // Cells outside the source's last sub-box were never traced (evolve_source.F90:136-144): no
     // contribution.  (The reference's own marker is coldensh_out == 0, evolve_point.F90:120; every cell
@@ -1402,7 +1413,8 @@ k_evolve0d(SweepArgs A, SrcDev S, int di, int dj, int dk, const BandData *__rest
   const size_t cz = S.cz;
   const double cin_HI = cs[col_in(p, 0, cz)], cin_HeI = cs[col_in(p, 1, cz)], cin_HeII = cs[col_in(p, 2, cz)];
   const double cout_HI = cs[col_out(p, 0, cz)], cout_HeI = cs[col_out(p, 1, cz)], cout_HeII = cs[col_out(p, 2, cz)];
-  const int i = mesh0<OPEN>(S.i0 - 1 + di, g.n1), j = mesh0<OPEN>(S.j0 - 1 + dj, g.n2), k = mesh0<OPEN>(S.k0 - 1 + dk, g.n3);
+  const int i = mesh0<OPEN>(S.i0 - 1 + di, g.n1, S.wn[0]), j = mesh0<OPEN>(S.j0 - 1 + dj, g.n2, S.wn[1]),
+            k = mesh0<OPEN>(S.k0 - 1 + dk, g.n3, S.wn[2]);
   const size_t q = (size_t)i + (size_t)g.n1 * ((size_t)j + (size_t)g.n2 * (size_t)k);
   const double nd = A.ndens[q];
   const double h0 = dmax(A.xh_av[q], epsilon), h1 = dmax(A.xh_av[q + nc], epsilon);
@@ -1605,7 +1617,9 @@ struct c2r_ctx {
   size_t rates_count = 0;
 
   int batch = 256;                 // most sources per batch (c2r_set_batch); the scratch arena may allow fewer
-  bool periodic = true;            // mesh boundaries (c2r_set_boundaries): periodic as the reference, or open (nothing wraps)
+  bool periodic = true;            // mesh boundaries (c2r_set_boundaries): periodic on all three axes as the reference, or not
+  bool per[3] = {true, true, true}; // ... per axis (c2r_set_boundaries_axes): periodic == all of them.  All false is the open
+                                   // mode, anything else the mixed one, which runs on the open kernels and host paths
   // Column scratch: per ping-pong set a list of segments; a source's block is cut from the current segment of
   // its set (shell-ordered arrays are prefixes of one another, so a block that turns out too small moves to a
   // deeper one by six copies).  A set that runs out of room gets another segment -- nothing that exists moves, no
@@ -2597,18 +2611,21 @@ static Reach mesh_reach(const Grid &g) {
   return R;
 }
 // open boundaries, the else branch of evolve_source.F90:107-108 (dead code there: lastpos_r = min(srcpos + max_subbox,
-// mesh), lastpos_l = max(srcpos - max_subbox, 1)): up to the mesh faces, per source
-static Reach open_reach(const Grid &g, const int *srcpos) {
+// mesh), lastpos_l = max(srcpos - max_subbox, 1)): up to the mesh faces, per source -- along the axes that are open;
+// along one that is periodic while another is open, the mesh's reach as above (axis_reach, c2ray_shell.hpp)
+static Reach open_reach(const Grid &g, const bool *per, const int *srcpos) {
   const int mesh[3] = {g.n1, g.n2, g.n3};
   Reach R;
-  for (int d = 0; d < 3; d++) {
-    R.r[d] = std::min(MAX_SUBBOX, mesh[d] - srcpos[d]);
-    R.l[d] = -std::min(MAX_SUBBOX, srcpos[d] - 1);
-  }
+  for (int d = 0; d < 3; d++) axis_reach(mesh[d], srcpos[d], per[d], MAX_SUBBOX, R.l[d], R.r[d]);
   return R;
 }
 static Reach source_reach(const c2r_ctx *c, int ns) {
-  return c->periodic ? mesh_reach(c->g) : open_reach(c->g, &c->srcpos[3 * (size_t)(ns - 1)]);
+  return c->periodic ? mesh_reach(c->g) : open_reach(c->g, c->per, &c->srcpos[3 * (size_t)(ns - 1)]);
+}
+// SrcDev::wn of a context that is not all-periodic
+static void source_wrap(const c2r_ctx *c, int *wn) {
+  const int mesh[3] = {c->g.n1, c->g.n2, c->g.n3};
+  for (int d = 0; d < 3; d++) wn[d] = axis_wrap_extent(mesh[d], c->per[d]);
 }
 // the largest shell a source's column block ever has to hold
 static int source_smax(const c2r_ctx *c, int ns) {
@@ -3072,6 +3089,7 @@ static int place_batch(const PassCtx &P, const std::vector<int> &mine, Batch &B)
     r.reach = source_reach(c, r.ns);
     r.smax = source_smax(c, r.ns);
     for (int d = 0; d < 3; d++) { S.rl[d] = r.reach.l[d]; S.rr[d] = r.reach.r[d]; }
+    source_wrap(c, S.wn);
     S.nflux = c->normflux[r.ns - 1];
     for (int k = 0; k < 2; k++) S.nflux_sed[k] = c->normflux_sed[k].empty() ? 0.0 : c->normflux_sed[k][r.ns - 1];
   }
@@ -3625,11 +3643,12 @@ static int pass_list(c2r_ctx *c, const std::vector<int> &mine, int nslab = 0) {
   } in_pass_guard(c);
   static const bool generic_sweep = getenv("C2R_SWEEP_GENERIC") && atoi(getenv("C2R_SWEEP_GENERIC")) > 0;
   static const bool arena_log = getenv("C2R_ARENA_LOG") != nullptr;
-  // (open boundaries: the reach of a source in the far corner on either side -- what no source's box exceeds)
+  // (an open axis: the reach of a source in the far corner on either side -- what no source's box exceeds)
   Reach widest = mesh_reach(c->g);
   if (!c->periodic) {
     const int mesh[3] = {c->g.n1, c->g.n2, c->g.n3};
-    for (int d = 0; d < 3; d++) { widest.r[d] = std::min(MAX_SUBBOX, mesh[d] - 1); widest.l[d] = -widest.r[d]; }
+    for (int d = 0; d < 3; d++)
+      if (!c->per[d]) { widest.r[d] = std::min(MAX_SUBBOX, mesh[d] - 1); widest.l[d] = -widest.r[d]; }
   }
   PassCtx P{c, scalars(c), SedSet(), false, widest, generic_sweep, arena_log};
   P.ss = sedset(c, &P.multi);
@@ -3948,6 +3967,7 @@ extern "C" int c2r_evolve0d(c2r_ctx *c, const int rtpos[3], int ns, int niter, i
   S.cz = cz;
   S.loss_lo = -1;
   for (int d = 0; d < 3; d++) { S.rl[d] = R.l[d]; S.rr[d] = R.r[d]; }
+  source_wrap(c, S.wn);
   double *dl = on_surface ? c->d_point_loss : nullptr;
   if (!c->isothermal) c->phiheat_dirty = true;
 #define C2R_LAUNCH_POINT(H, M) \
@@ -4201,6 +4221,7 @@ extern "C" int c2r_download_columns(c2r_ctx *c, double *coldensh_out, double *co
   S.cz = c->last_cz;
   const Reach R = source_reach(c, c->last_src);
   for (int d = 0; d < 3; d++) { S.rl[d] = R.l[d]; S.rr[d] = R.r[d]; }
+  source_wrap(c, S.wn);
   if (c->periodic) hipLaunchKernelGGL(k_col_to_grid<false>, dim3(nblk), dim3(BLOCK), 0, c->stream, c->g, S, c->last_cols, c->d_colgrid);
   else hipLaunchKernelGGL(k_col_to_grid<true>, dim3(nblk), dim3(BLOCK), 0, c->stream, c->g, S, c->last_cols, c->d_colgrid);
   HIPCHK(c, hipGetLastError());
@@ -4460,11 +4481,12 @@ extern "C" int c2r_set_batch(c2r_ctx *c, int nbatch) {
 // Switching forgets what earlier passes learnt about the sources (sub-box counts, hence predicted block sizes and the
 // rounds swept on trust): none of it holds for the other geometry.  The column scratch stays; it only ever holds finite
 // numbers, whoever wrote them.
-static int set_boundaries_one(c2r_ctx *c, int periodic) {
+static int set_boundaries_one(c2r_ctx *c, const int periodic[3]) {
   if (!c) return 1;
   if (c->pass_open) return fail(c, "c2r_set_boundaries: a pass opened by c2r_pass_sources_begin is still open (close it with c2r_pass_sources_end first)");
-  const bool want = periodic != 0;
-  if (want == c->periodic) return 0;
+  const bool per[3] = {periodic[0] != 0, periodic[1] != 0, periodic[2] != 0};
+  if (per[0] == c->per[0] && per[1] == c->per[1] && per[2] == c->per[2]) return 0;
+  const bool want = per[0] && per[1] && per[2];
   HIPCHK(c, hipSetDevice(c->device));
   // nothing queued may still read the shell bookkeeping or the lists that are about to be replaced
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -4472,6 +4494,7 @@ static int set_boundaries_one(c2r_ctx *c, int periodic) {
   HIPCHK(c, hipStreamSynchronize(c->stream3));
   HIPCHK(c, hipStreamSynchronize(c->stream_probe));
   c->periodic = want;
+  for (int d = 0; d < 3; d++) c->per[d] = per[d];
   shell_bookkeeping(c);
   HIPCHK(c, hipFree(c->d_block_base));
   c->d_block_base = nullptr;
@@ -4500,12 +4523,27 @@ static int set_boundaries_one(c2r_ctx *c, int periodic) {
   return 0;
 }
 
-extern "C" int c2r_set_boundaries(c2r_ctx *c, int periodic) {
+extern "C" int c2r_set_boundaries_axes(c2r_ctx *c, const int periodic[3]) {
+  if (!periodic) return c ? fail(c, "c2r_set_boundaries_axes: null argument") : 1;
   if (int e_ = set_boundaries_one(c, periodic)) return e_;
   return for_replicas(c, [&](c2r_ctx *r) { return set_boundaries_one(r, periodic); });
 }
 
-extern "C" int c2r_get_boundaries(const c2r_ctx *c) { return !c || c->periodic ? 1 : 0; }
+extern "C" int c2r_set_boundaries(c2r_ctx *c, int periodic) {
+  const int all[3] = {periodic, periodic, periodic};
+  return c2r_set_boundaries_axes(c, all);
+}
+
+extern "C" int c2r_get_boundaries(const c2r_ctx *c) {
+  if (!c || c->periodic) return 1;
+  return c->per[0] || c->per[1] || c->per[2] ? 2 : 0;
+}
+
+extern "C" int c2r_get_boundaries_axes(const c2r_ctx *c, int out[3]) {
+  if (!c || !out) return 1;
+  for (int d = 0; d < 3; d++) out[d] = c->per[d] ? 1 : 0;
+  return 0;
+}
 
 extern "C" int c2r_upload_rates(c2r_ctx *c, const double *phih, const double *phihe, const double *phiheat) {
   if (int e_ = upload_rates_one(c, phih, phihe, phiheat)) return e_;

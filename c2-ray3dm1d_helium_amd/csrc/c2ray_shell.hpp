@@ -322,6 +322,45 @@ C2R_HD size_t reach_position(const int *l, const int *r, int di, int dj, int dk)
   return (size_t)G.off + (size_t)reach_position_in_shell(G, di, dj, dk);
 }
 
+// ----------------------------------------------------------------------------------------------------------------
+// Boundaries per axis (c2r_set_boundaries_axes): the cut shell order above takes any reach l <= 0 <= r, so an axis that is
+// periodic while others are open is an axis whose reach is the periodic one and whose mesh index wraps.  One number per
+// axis says which: its WRAP EXTENT w, the mesh extent if the axis is periodic and 0 if it is open -- every map below
+// is the identity on an open axis because adding or subtracting 0 is, without a branch.
+C2R_HD int axis_wrap_extent(int mesh, int periodic) { return periodic ? mesh : 0; }
+
+// x in [-w, 2w) -> its periodic image in [0, w); w == 0: x itself.  Of x, x + w and x - w exactly one lies in [0, w);
+// read as unsigned numbers it is the smallest of the three (v_add, v_sub, v_min3_u32 instead of two compares, two
+// selects and the arithmetic)
+C2R_HD int axis_wrap(int x, int w) {
+  const unsigned u = (unsigned)x, m = (unsigned)w;
+  const unsigned a = u + m, b = u - m;
+  const unsigned lo = a < b ? a : b;
+  return (int)(u < lo ? u : lo);
+}
+
+// reach of a source at the 1-based position pos along an axis of `mesh` cells (evolve_source.F90:103-109): periodic,
+// the then-branch, l = -min(max_subbox, mesh/2), r = min(max_subbox, mesh/2 - 1 + mod(mesh,2)), the same for every
+// source; open, the else branch, up to the mesh faces: l = -min(max_subbox, pos - 1), r = min(max_subbox, mesh - pos)
+C2R_HD void axis_reach(int mesh, int pos, int periodic, int max_subbox, int &l, int &r) {
+  const int left = periodic ? mesh / 2 : pos - 1, right = periodic ? mesh / 2 - 1 + mesh % 2 : mesh - pos;
+  l = -(left < max_subbox ? left : max_subbox);
+  r = right < max_subbox ? right : max_subbox;
+}
+
+// 0-based mesh index of the cell at offset `off` (within the reach) from a source at the 1-based position pos
+C2R_HD int axis_mesh_index(int pos, int off, int w) { return axis_wrap(pos - 1 + off, w); }
+
+// offset from that source of the cell with the 0-based mesh index `cell`.  Periodic axis: the image in
+// [-w/2, w - w/2 - 1], the reach of max_subbox = infinity -- a cell within a shorter reach [l, r] has its offset there
+// and nowhere else, a cell beyond it lands outside [l, r], where the in-box test rejects it.  Open axis: the difference
+// as it is.  (Wrapping an open axis relative to its reach's left end would be the identity only while the reach spans
+// the whole axis; it does not when max_subbox is smaller.)
+C2R_HD int axis_offset(int cell, int pos, int w) {
+  const int h = w >> 1;
+  return axis_wrap(cell + 1 - pos + h, w) - h;
+}
+
 // x clamped into [lo, hi]
 C2R_HD int reach_clamp(int x, int lo, int hi) { return x < lo ? lo : (x > hi ? hi : x); }
 

@@ -448,12 +448,27 @@ class HipEngine:
 
     def set_boundaries(self, periodic=True):
         """Mesh boundaries of the ray trace: periodic (the default, the reference's) or open -- nothing wraps, photons
-        that reach a mesh face are lost (c2r_set_boundaries; include/c2ray_hip.h has the semantics)."""
-        self._chk(self.lib.c2r_set_boundaries(self.h, int(bool(periodic))))
+        that reach a mesh face are lost (c2r_set_boundaries; include/c2ray_hip.h has the semantics).  A sequence of
+        three gives the mode per axis (c2r_set_boundaries_axes): (True, True, False) is periodic in x and y and open in z."""
+        if isinstance(periodic, (bool, int, np.bool_, np.integer)):
+            self._chk(self.lib.c2r_set_boundaries(self.h, int(bool(periodic))))
+            return
+        axes = [int(bool(p)) for p in periodic]
+        if len(axes) != 3:
+            raise ValueError("set_boundaries: a bool or a sequence of three, one per axis")
+        self._chk(self.lib.c2r_set_boundaries_axes(self.h, (C.c_int * 3)(*axes)))
 
     @property
     def periodic(self):
-        return bool(self.lib.c2r_get_boundaries(self.h))
+        """True: periodic on every axis, False: open on every axis, None: mixed (periodic_axes tells which)."""
+        mode = self.lib.c2r_get_boundaries(self.h)
+        return None if mode == 2 else bool(mode)
+
+    @property
+    def periodic_axes(self):
+        out = (C.c_int * 3)()
+        self._chk(self.lib.c2r_get_boundaries_axes(self.h, out))
+        return tuple(bool(v) for v in out)
 
     def enable_timing(self, on=True):
         self._chk(self.lib.c2r_enable_timing(self.h, int(on)))
@@ -554,8 +569,8 @@ class Evolve:
     def __init__(self, mesh, tables: RadiationTables | None = None, device=0, engine=None, comm=None, periodic=True):
         self.mesh = tuple(int(m) for m in mesh)
         self.engine = engine if engine is not None else HipEngine(self.mesh, device)
-        if not periodic:    # open mesh boundaries (HipEngine.set_boundaries); the default leaves the engine as it is
-            self.engine.set_boundaries(False)
+        if periodic is not True:    # open or per-axis mesh boundaries (HipEngine.set_boundaries); the default leaves the engine as it is
+            self.engine.set_boundaries(periodic)
         self.tables = tables if tables is not None else RadiationTables.load()
         self.engine.set_tables(self.tables)
         self.comm = comm

@@ -530,6 +530,19 @@ module c2ray_hip
        type(c_ptr), value :: ctx
      end function c2r_get_boundaries
 
+     !> per axis: periodic(d) /= 0, axis d wraps; 0, it is open (include/c2ray_hip.h)
+     integer(c_int) function c2r_set_boundaries_axes(ctx, periodic) bind(C, name="c2r_set_boundaries_axes")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: ctx
+       integer(c_int), intent(in) :: periodic(3)
+     end function c2r_set_boundaries_axes
+
+     integer(c_int) function c2r_get_boundaries_axes(ctx, periodic) bind(C, name="c2r_get_boundaries_axes")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: ctx
+       integer(c_int), intent(out) :: periodic(3)
+     end function c2r_get_boundaries_axes
+
      integer(c_int) function c2r_enable_timing(ctx, on) bind(C, name="c2r_enable_timing")
        import :: c_int, c_ptr
        type(c_ptr), value :: ctx

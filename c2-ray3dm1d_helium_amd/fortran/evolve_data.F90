@@ -9,7 +9,7 @@ module evolve_data
   use, intrinsic :: iso_c_binding, only: c_ptr, c_null_ptr, c_int, c_char, c_double, c_null_char
   use c2ray_hip, only: c2r_create, c2r_create_multi, c2r_error_text, c2r_device_count, c2r_get_constants
   use c2ray_hip, only: c2r_comm_unique_id, c2r_comm_init, c2r_comm_init_local, c2r_comm_kind, c2r_comm_library
-  use c2ray_hip, only: c2r_set_boundaries
+  use c2ray_hip, only: c2r_set_boundaries_axes
   use file_admin, only: logf
   use my_mpi                                  ! rank, npr, MPI_COMM_NEW
   use precision, only: dp
@@ -26,8 +26,11 @@ module evolve_data
   !> the sweep wraps around the mesh edges (the only mode the reference supports here; the reference's own
   !! evolve_source.F90, linked on top of this module for the cell-by-cell interface, reads this parameter)
   logical, parameter :: periodic_bc = .true.
-  !> C2RAY_HIP_OPEN_BOUNDARIES=1: the device traces a box that does not wrap (c2r_set_boundaries)
+  !> C2RAY_HIP_OPEN_BOUNDARIES=1: the device traces a box that does not wrap (c2r_set_boundaries_axes);
+  !! =x, =z, =xy, ...: only along the axes named
   logical :: hip_open_boundaries = .false.
+  !> the axes that do not wrap
+  logical :: hip_open_axis(3) = .false.
 
   ! host mirrors of device arrays, public under the reference's names
   !> photo-ionisation rates summed over all sources: H, and He (components 0:1)
@@ -69,7 +72,8 @@ contains
     integer(c_int), allocatable :: devices(:)
     character(len=32) :: value
     integer :: length, status
-    integer :: n1, n2, n3, ndev_node, local_rank, offset, i, open_bc
+    integer :: n1, n2, n3, ndev_node, local_rank, offset, i
+    integer(c_int) :: periodic_axes(3)
 
     n1 = mesh(1)
     n2 = mesh(2)
@@ -130,14 +134,25 @@ contains
 
     ! C2RAY_HIP_OPEN_BOUNDARIES=1: open (non-periodic) mesh boundaries, the dead else branch of the reference's
     ! evolve_source.F90:103-109 built out (include/c2ray_hip.h: c2r_set_boundaries).  The reference's own build cannot
-    ! run this mode, so there are no files of its to compare with.
-    open_bc = 0
-    call env_integer ("C2RAY_HIP_OPEN_BOUNDARIES", open_bc)
-    hip_open_boundaries = open_bc /= 0
+    ! run this mode, so there are no files of its to compare with.  Instead of a number the variable may name the open
+    ! axes by any combination of the letters x, y, z; the others stay periodic (c2r_set_boundaries_axes).
+    call env_open_axes ("C2RAY_HIP_OPEN_BOUNDARIES", hip_open_axis)
+    hip_open_boundaries = any(hip_open_axis)
     if (hip_open_boundaries) then
-       ierr = c2r_set_boundaries (hip_ctx, 0_c_int)
+       periodic_axes(:) = merge(0_c_int, 1_c_int, hip_open_axis(:))
+       ierr = c2r_set_boundaries_axes (hip_ctx, periodic_axes)
        if (ierr /= 0) call stop_with (c2r_error_text(hip_ctx))
-       if (rank == 0) write(logf,"(A)") " evolve_ini: open (non-periodic) mesh boundaries (C2RAY_HIP_OPEN_BOUNDARIES)"
+       if (rank == 0) then
+          if (all(hip_open_axis)) then
+             write(logf,"(A)") " evolve_ini: open (non-periodic) mesh boundaries (C2RAY_HIP_OPEN_BOUNDARIES)"
+          else
+             write(logf,"(7A)") " evolve_ini: mesh boundaries open along ", &
+                  trim(merge("x", " ", hip_open_axis(1))), trim(merge("y", " ", hip_open_axis(2))), &
+                  trim(merge("z", " ", hip_open_axis(3))), ", periodic along ", &
+                  trim(merge(" ", "x", hip_open_axis(1)))//trim(merge(" ", "y", hip_open_axis(2)))// &
+                  trim(merge(" ", "z", hip_open_axis(3))), " (C2RAY_HIP_OPEN_BOUNDARIES)"
+          endif
+       endif
     endif
 
     call setup_communicator ()
@@ -244,6 +259,28 @@ contains
        if (ios == 0) value = v
     endif
   end subroutine env_integer
+
+  !> The open axes an environment variable names: a number (non-zero: all three, zero: none) or any combination of the
+  !! letters x, y, z in either case.  Anything else ends the run: a misspelt geometry must not run as another one.
+  subroutine env_open_axes (name, open_axis)
+    character(len=*), intent(in) :: name
+    logical, intent(out) :: open_axis(3)
+    character(len=32) :: text
+    integer :: length, status, v, ios, i, axis
+    open_axis(:) = .false.
+    call get_environment_variable(name, text, length, status)
+    if (status /= 0 .or. length <= 0) return
+    if (verify(text(1:length), "+-0123456789 ") == 0) then
+       read(text(1:length),*,iostat=ios) v
+       if (ios == 0) open_axis(:) = v /= 0
+       return
+    endif
+    do i = 1, length
+       axis = index("xyzXYZ", text(i:i))
+       if (axis == 0) call stop_with (name//"="//text(1:length)//": expected a number or a combination of the letters x, y, z")
+       open_axis(modulo(axis - 1, 3) + 1) = .true.
+    enddo
+  end subroutine env_open_axes
 
   !> log the text and end the run on every rank
   subroutine stop_with (text)

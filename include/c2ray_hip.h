@@ -277,8 +277,33 @@ int c2r_set_batch(c2r_ctx *ctx, int nbatch);
  * sits -- 0.8 GB at N = 256, never more than a periodic block -- and a shell launch holds threads for the cells of the
  * cut shell only.  c2r_get_source_trace reports both per source. */
 int c2r_set_boundaries(c2r_ctx *ctx, int periodic);
-/* 1: periodic, 0: open */
+/* 1: periodic on all three axes, 0: open on all three, 2: mixed (c2r_set_boundaries_axes) */
 int c2r_get_boundaries(const c2r_ctx *ctx);
+
+/* Mesh boundaries per axis: periodic[d] != 0, axis d wraps; periodic[d] == 0, it is open.  All three non-zero is the
+ * periodic mode above -- the same kernels, the same code path --, all three zero is the open mode, anything else is the
+ * MIXED mode: a slab or a light-cone strip, periodic across the sky and open along the line of sight.
+ * c2r_set_boundaries(ctx, p) means {p, p, p}.  The rules are those of c2r_set_boundaries: every device of a multi-device
+ * context, refused between c2r_pass_sources_begin and c2r_pass_sources_end, a real change of mode forgets what earlier
+ * passes learnt; the same entry points honour it (c2r_get_source_trace included), with heating and with three SEDs.
+ * The mixed mode, per axis d of a source at srcpos:
+ *   reach -- open axis, as in open mode: l = -min(max_subbox, srcpos - 1), r = min(max_subbox, mesh - srcpos);
+ *     periodic axis, the then-branch of evolve_source.F90:103-109: l = -min(max_subbox, mesh/2),
+ *     r = min(max_subbox, mesh/2 - 1 + mod(mesh,2)), the same for every source;
+ *   a cell of a box lies at srcpos + offset, taken modulo the mesh on a periodic axis and as it is on an open one;
+ *     cinterp works on the unwrapped offsets, as it always did;
+ *   box growth and the two loss sums follow the OPEN mode's rule on all six faces, periodic axes included: the loss that
+ *     decides runs over the surface cells on faces still short of their reach, the loop goes on while it exceeds
+ *     1e-10 * total_source_flux and some face can still move, and the loss that is kept runs over the whole surface of the
+ *     final box.
+ * The reference's while-test, which looks at z only, and what follows from it -- a box whose z faces have arrived stops
+ * growing along x and y too, and a mesh with (N/2 - 1) mod subboxsize == 0 stops one round short of its last -- belong to
+ * the all-periodic path only.  A mixed run with z periodic therefore traces an open axis to its end where the all-periodic
+ * code on a larger mesh would have stopped with z.
+ * The column block of a source holds prod_d(r_d - l_d + 1) <= n1 n2 n3 cells, as in open mode. */
+int c2r_set_boundaries_axes(c2r_ctx *ctx, const int periodic[3]);
+/* out[d] = 1: axis d is periodic, 0: open */
+int c2r_get_boundaries_axes(const c2r_ctx *ctx, int out[3]);
 
 /* ---- several GPUs: sources over ranks and the sum over ranks ----------------------------------------
  * The reference's MPI strategy (master_slave.F90:74-96 do_grid_static, evolve.F90:505-548
@@ -443,8 +468,8 @@ int c2r_arena_stats(const c2r_ctx *ctx, long long out[6]);
 /* the same for device `idev` (0 .. c2r_num_devices-1) of a context made by c2r_create_multi */
 int c2r_get_timing_device(c2r_ctx *ctx, int idev, c2r_timing *out);
 /* What the last pass that swept source ns (1-based) did for it, from the host's bookkeeping (no device copy, no
- * synchronisation; both boundary modes).  reach_l <= 0 <= reach_r: how far the source's box can go per axis (the mesh's
- * reach with periodic boundaries, the source's own with open ones); nbox: its rounds (0, with everything below 0, while
+ * synchronisation; every boundary mode).  reach_l <= 0 <= reach_r: how far the source's box can go per axis (the mesh's
+ * reach along a periodic axis, the source's own along an open one); nbox: its rounds (0, with everything below 0, while
  * it has not been swept since the source list or the boundary mode was set); box_lo / box_hi: its final sub-box as
  * offsets from the source; block_shells: the shells its column block could hold at the end; block_cells: entries per
  * column array of that block -- (2 block_shells + 1)^3 periodic, the cells of those shells within the reach open;
