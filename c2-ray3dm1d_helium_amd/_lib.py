@@ -53,6 +53,11 @@ class CommTiming(C.Structure):
     _fields_ = [("slabs", C.c_int), ("allreduce_ms", C.c_double), ("allreduce_exposed_ms", C.c_double), ("tail_ms", C.c_double)]
 
 
+class PlaneSource(C.Structure):
+    """c2r_plane_source (include/c2ray_hip.h)."""
+    _fields_ = [("axis", C.c_int), ("from_high", C.c_int), ("normflux", C.c_double * 3)]
+
+
 class SedSetup(C.Structure):
     """struct c2r_sed_setup (include/c2ray_hip.h)."""
     _fields_ = [("nfreq", C.c_int), ("sed", C.c_int), ("freq_min", _dp), ("delta_freq", _dp), ("xsec_index", _dp),
@@ -119,6 +124,11 @@ SYMBOLS = {
     "c2r_get_boundaries": (C.c_int, [C.c_void_p]),
     "c2r_set_boundaries_axes": (C.c_int, [C.c_void_p, _ip]),
     "c2r_get_boundaries_axes": (C.c_int, [C.c_void_p, _ip]),
+    "c2r_set_plane_sources": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(PlaneSource)]),
+    "c2r_get_plane_count": (C.c_int, [C.c_void_p]),
+    "c2r_set_plane_entry_columns": (C.c_int, [C.c_void_p, C.c_int, _dp]),
+    "c2r_download_plane_exit_columns": (C.c_int, [C.c_void_p, C.c_int, _dp]),
+    "c2r_get_plane_loss": (C.c_int, [C.c_void_p, C.c_int, _dp]),
     "c2r_evolve0d_global": (C.c_int, [C.c_void_p, C.c_double, _ip, _ip]),
     "c2r_evolve0d": (C.c_int, [C.c_void_p, _ip, C.c_int, C.c_int, C.c_int, _dp]),
     "c2r_fraction_minima": (C.c_int, [C.c_void_p, C.c_int, _dp]),

@@ -768,12 +768,10 @@ extern "C" int c2r_global_pass(c2r_ctx *c, double dt, int *conv_flag) {
 static int pass_slabs_one(c2r_ctx *d, bool own_sums, int first, int stride, int nslab, double dt) {
   if (check_ready(d, "c2r_pass_allreduce_chemistry")) return 1;
   HIPCHK(d, hipSetDevice(d->device));
-  std::vector<int> mine;
-  for (int ns = first; ns <= d->nsrc; ns += stride) mine.push_back(ns);
   d->last_first = first;
   d->last_stride = stride;
   if (comm_timing_prepare(d)) return 1;
-  if (pass_list(d, mine, nslab)) return 1;
+  if (pass_list(d, dealt_share(d, first, stride), nslab)) return 1;
   d->slab_passes++;
   // C2R_FAULT_INJECT="rank:pass" (test hook): that rank returns from its pass-th slab-wise pass with an error, after its
   // sweeps and before its share of the sums -- the failure "in the middle of a pass" that fail-together is about
@@ -884,7 +882,7 @@ extern "C" int c2r_evolve3d(c2r_ctx *c, double dt, int *niter_out, int *conv_fla
   int niter = 0;
   const Grid g = c->g;
   int conv_flag = (int)g.ncell;
-  const int conv_criterion = std::min((int)(convergence_fraction * g.n1 * g.n2 * g.n3), c->nsrc); // evolve.F90:147
+  const int conv_criterion = std::min((int)(convergence_fraction * g.n1 * g.n2 * g.n3), c->nsrc + c->nplane); // evolve.F90:147 (a plane counts as a source)
   const int ndev = c2r_num_devices(c);
   for (;;) {
     if (conv_flag < conv_criterion && niter > 1) { // evolve.F90:163
@@ -902,7 +900,7 @@ extern "C" int c2r_evolve3d(c2r_ctx *c, double dt, int *niter_out, int *conv_fla
       const int nslab = env && atoi(env) > 0 ? atoi(env) : 4;
       if (c2r_pass_allreduce_chemistry(c, 1 + c->comm_rank / ndev, std::max(1, c->comm_nranks / ndev), nslab, dt, &conv_flag)) return 1;
     } else {
-      if (c->nsrc > 0 && c2r_pass_sources(c, 1, 1)) return 1;
+      if (c->nsrc + c->nplane > 0 && c2r_pass_sources(c, 1, 1)) return 1;
       if (c2r_global_pass(c, dt, &conv_flag)) return 1;
     }
     if (conv_flags_out && niter <= cap) conv_flags_out[niter - 1] = conv_flag;

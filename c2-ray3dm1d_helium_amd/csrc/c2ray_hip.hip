@@ -14,6 +14,8 @@
 //   chemistry      k_chemistry     evolve0D_global / do_chemistry / doric / thermal per cell
 //   statistics     k_state_sums, k_total_rates, k_stat_finish   the grid sums of photonstatistics.f90
 //   tables         k_build_tables  spec_integration: the photo-ionisation / heating tables of one SED
+//   plane sources  k_plane_columns, k_plane_rates, k_plane_exit   a plane wave entering through an open mesh face: the 1-D
+//                                  march of every line of cells along the axis, its rates, what leaves through the far face
 //
 // Compile: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fPIC -shared
 #include <hip/hip_runtime.h>
@@ -34,6 +36,7 @@
 
 #include "../../include/c2ray_hip.h"
 #include "c2ray_device.hpp"
+#include "c2ray_plane.hpp"
 #include "c2ray_shell.hpp"
 
 using namespace c2r;
@@ -1544,6 +1547,116 @@ __global__ void __launch_bounds__(BLOCK) k_divide_by(double *__restrict__ a, siz
   for (size_t i = (size_t)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (size_t)gridDim.x * BLOCK) a[i] = a[i] / d;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Plane-parallel sources (c2r_set_plane_sources; the per-cell rule is c2ray_plane.hpp): a plane
+// wave enters through an open face and travels along one axis, every line of cells a 1-D problem of its own.  Three
+// kernels per plane and pass, all on the sweep stream: the columns (a march, one lane per line), the rates (no
+// dependencies, one lane per cell) and what leaves through the far face.
+struct PlaneDev {
+  double nf[NSED]; // NormFlux per cm^2 of face: black body, power law, quasar-like
+};
+
+// The march: lane f owns column f of the face and walks the mesh[axis] cells behind it in travel order, handing each
+// cell's outgoing columns to the next as its incoming ones.  Writes the incoming columns of every cell (LLS fog applied),
+// 3 doubles per cell in mesh order, and the outgoing columns of the last cell (species slowest).  Memory-bound and cheap
+// next to the rates: 32 bytes read and 24 written per cell.  Along axis 0 the lanes of a wave are n1 doubles apart, but
+// 16 consecutive steps of a lane stay within one 128-byte line of each grid, so the lines are fetched once.
+__global__ void __launch_bounds__(BLOCK)
+k_plane_columns(PlaneGeom G, StepScalars sc, double path, size_t nc, const double *__restrict__ ndens, const double *__restrict__ xh_av,
+                const double *__restrict__ xhe_av, const float *__restrict__ lls_grid, const double *__restrict__ entry,
+                double *__restrict__ cin_out, double *__restrict__ exit_cols) {
+  const int face = G.fa * G.fb;
+  const int f = (int)blockIdx.x * BLOCK + (int)threadIdx.x;
+  if (f >= face) return;
+  double c_HI = 0.0, c_HeI = 0.0, c_HeII = 0.0;
+  if (entry) { c_HI = entry[f]; c_HeI = entry[face + f]; c_HeII = entry[2 * face + f]; }
+  long long q = (long long)plane_cell(G, f, 0);
+  const long long step = G.from_high ? -(long long)G.sa : (long long)G.sa;
+  for (int m = 0; m < G.na; m++, q += step) {
+    const double lls = sc.use_lls ? (lls_grid ? (double)lls_grid[q] : sc.coldensh_lls) : 0.0;
+    double o_HI, o_HeI, o_HeII;
+    plane_cell_columns(ndens[q], xh_av[q], xhe_av[q], xhe_av[q + (long long)nc], path, sc.dr1, sc.use_lls, lls, c_HI, c_HeI, c_HeII,
+                       o_HI, o_HeI, o_HeII);
+    cin_out[3 * q] = c_HI; // (with the fog: what the rates and the exit loss see)
+    cin_out[3 * q + 1] = c_HeI;
+    cin_out[3 * q + 2] = c_HeII;
+    c_HI = o_HI; c_HeI = o_HeI; c_HeII = o_HeII;
+  }
+  exit_cols[f] = c_HI;
+  exit_cols[face + f] = c_HeI;
+  exit_cols[2 * face + f] = c_HeII;
+}
+
+// The rates of every cell from one plane, added to the rate grids: k_rates' shape -- a block is a tile of 8 x 8 x 4
+// cells, a wave a 4 x 4 x 4 cube of it (neighbours see similar optical depths and take the same branches), the log's
+// table in LDS -- with one source whose columns come in mesh order and whose vol_ph is dr[axis].  One lane per cell and
+// not per line: the rates are some thousands of fp64 instructions per cell, and N^2 lanes would leave the device idle.
+// The outgoing columns are formed again from the incoming ones (plane_cell_out, the expression the march used).
+template <bool HEAT, bool MULTI>
+__global__ void __launch_bounds__(BLOCK, MULTI ? (HEAT ? C2R_RATES_WAVES_HEAT_MULTI : 4) : (HEAT ? C2R_RATES_WAVES_HEAT : C2R_RATES_WAVES_ISO))
+k_plane_rates(Grid g, double path, PlaneDev pl, const double *__restrict__ ndens, const double *__restrict__ xh_av,
+              const double *__restrict__ xhe_av, const BandDataByRow *__restrict__ bdr, SedSet ss, const double *__restrict__ cin,
+              double *__restrict__ rates) {
+  const size_t nc = g.ncell;
+  __shared__ gm::LogEntry s_logtab[256];
+  s_logtab[threadIdx.x] = gm::make_log_entry((int)threadIdx.x);
+  __syncthreads();
+  const BandData *const bd = bdr;
+  gm::LogPins pins_ = {0.0, 0.0};
+  const gm::LogPins *pins = nullptr;
+  if (!HEAT) {
+    pins_ = gm::pin_log_constants();
+    pins = &pins_;
+  }
+  const int ti = (g.n1 + 7) >> 3, tj = (g.n2 + 7) >> 3;
+  const int tile = (int)blockIdx.x;
+  const int bi = tile % ti, bj = (tile / ti) % tj, bk = tile / (ti * tj);
+  const int lane = threadIdx.x & 63;
+  const int w_ = threadIdx.x >> 6;
+  const int i = bi * 8 + (w_ & 1) * 4 + (lane & 3), j = bj * 8 + (w_ >> 1) * 4 + ((lane >> 2) & 3), k = bk * 4 + (lane >> 4);
+  if (i >= g.n1 || j >= g.n2 || k >= g.n3) return;
+  const size_t q = (size_t)i + (size_t)g.n1 * ((size_t)j + (size_t)g.n2 * (size_t)k);
+  double u_HI, u_HeI, u_HeII;
+  plane_cell_state(ndens[q], xh_av[q], xhe_av[q], xhe_av[q + nc], u_HI, u_HeI, u_HeII);
+  const double cin_HI = cin[3 * q], cin_HeI = cin[3 * q + 1], cin_HeII = cin[3 * q + 2];
+  double cout_HI, cout_HeI, cout_HeII;
+  plane_cell_out(cin_HI, cin_HeI, cin_HeII, u_HI, u_HeI, u_HeII, path, cout_HI, cout_HeI, cout_HeII);
+  const double h_av1 = HEAT ? xh_av[q + nc] : 0.0;
+  double add[4];
+  bool lit;
+  if constexpr (HEAT && MULTI) // cross sections and factors band by band, as k_rates' three-SED heating kernel reads them
+    lit = plane_cell_rates<HEAT, MULTI>(*bdr, ss, cin_HI, cout_HI, cin_HeI, cout_HeI, cin_HeII, cout_HeII, path, pl.nf, h_av1, u_HI, u_HeI,
+                                        u_HeII, add, &s_logtab[0], pins);
+  else
+    lit = plane_cell_rates<HEAT, MULTI>(*bd, ss, cin_HI, cout_HI, cin_HeI, cout_HeI, cin_HeII, cout_HeII, path, pl.nf, h_av1, u_HI, u_HeI,
+                                        u_HeII, add, &s_logtab[0], pins);
+  if (!lit) return; // beyond max_coldensh: nothing is added
+  rates[q] = rates[q] + add[0];
+  rates[q + nc] = rates[q + nc] + add[1];
+  rates[q + 2 * nc] = rates[q + 2 * nc] + add[2];
+  if (HEAT) rates[q + 3 * nc] = rates[q + 3 * nc] + add[3];
+}
+
+// What the plane loses through the far face: lane f evaluates photo_out of the last cell of column f
+// (plane_exit_term), the block adds its 256 terms in block_sum's fixed tree; k_loss_finish then adds the block sums in
+// order.  No float atomics: the same bits every time.
+template <bool MULTI>
+__global__ void __launch_bounds__(BLOCK)
+k_plane_exit(PlaneGeom G, StepScalars sc, double path, PlaneDev pl, const BandData *__restrict__ bd, SedSet ss,
+             const double *__restrict__ cin, const double *__restrict__ exit_cols, double *__restrict__ partial) {
+  __shared__ double sh[BLOCK / 64];
+  const int face = G.fa * G.fb;
+  const int f = (int)blockIdx.x * BLOCK + (int)threadIdx.x;
+  double term = 0.0;
+  if (f < face) {
+    const size_t q = plane_cell(G, f, G.na - 1);
+    term = plane_exit_term<MULTI>(*bd, ss, cin[3 * q], exit_cols[f], cin[3 * q + 1], exit_cols[face + f], cin[3 * q + 2],
+                                  exit_cols[2 * face + f], pl.nf, sc.vol, path);
+  }
+  const double bs = block_sum(term, sh);
+  if (threadIdx.x == 0) partial[blockIdx.x] = bs;
+}
+
 } // namespace
 
 // =============================================================================================
@@ -1708,6 +1821,19 @@ struct c2r_ctx {
 
   double photon_loss[C2R_NFREQ] = {0};
   int sum_nbox = 0;
+
+  // plane-parallel sources (c2r_set_plane_sources): plane p (1-based) is "source nsrc + p" of every deal.  The buffers are
+  // made by c2r_set_plane_sources and live until the planes are removed: never allocated inside a pass.
+  int nplane = 0;
+  c2r_plane_source planes[PLANE_MAX] = {};
+  double *d_plane_cin = nullptr;    // 3 ncell: the incoming columns of every cell, of the plane being run (planes run one after another)
+  double *d_plane_entry[PLANE_MAX] = {}, *d_plane_exit[PLANE_MAX] = {}; // 3 x face each: (HI, HeI, HeII) x face cells
+  bool plane_entry_set[PLANE_MAX] = {}; // entry columns were given (else zero)
+  double *d_plane_partial = nullptr; // block sums of the exit loss
+  double *d_plane_loss = nullptr, *h_plane_loss = nullptr; // PLANE_MAX each (h: pinned): the exit loss of the pass in flight
+  double plane_loss[PLANE_MAX] = {}; // the term plane p added to photon_loss(1) in the last pass that ran it
+  long long plane_stamp[PLANE_MAX] = {}; // ... and which pass that was (as trace_stamp)
+  std::vector<int> pass_planes;     // planes (0-based) of the pass in flight, in order
 
   // second stream for the rates kernels: the (latency-bound) column sweep of batch n+1 runs beside
   // the (ALU-bound) rates kernel of batch n; two scratch sets ping-pong between them
@@ -2034,6 +2160,21 @@ extern "C" int c2r_create(c2r_ctx **out, int device, const int mesh[3]) {
   return 0;
 }
 
+// the device and pinned buffers of the plane sources (c2r_set_plane_sources makes them, removal and c2r_destroy free them)
+static void free_plane_buffers(c2r_ctx *c) {
+  for (int p = 0; p < PLANE_MAX; p++) {
+    if (c->d_plane_entry[p]) (void)hipFree(c->d_plane_entry[p]);
+    if (c->d_plane_exit[p]) (void)hipFree(c->d_plane_exit[p]);
+    c->d_plane_entry[p] = c->d_plane_exit[p] = nullptr;
+    c->plane_entry_set[p] = false;
+  }
+  if (c->d_plane_cin) (void)hipFree(c->d_plane_cin);
+  if (c->d_plane_partial) (void)hipFree(c->d_plane_partial);
+  if (c->d_plane_loss) (void)hipFree(c->d_plane_loss);
+  if (c->h_plane_loss) (void)hipHostFree(c->h_plane_loss);
+  c->d_plane_cin = c->d_plane_partial = c->d_plane_loss = c->h_plane_loss = nullptr;
+}
+
 extern "C" void c2r_destroy(c2r_ctx *c) {
   if (!c) return;
   (void)c2r_comm_destroy(c);
@@ -2087,6 +2228,7 @@ extern "C" void c2r_destroy(c2r_ctx *c) {
     for (void *q : host)
       if (q) (void)hipHostFree(q);
   }
+  free_plane_buffers(c);
   if (c->h_conv) (void)hipHostFree(c->h_conv);
   if (c->h_stat) (void)hipHostFree(c->h_stat);
   if (c->h_iter) (void)hipHostFree(c->h_iter);
@@ -3630,12 +3772,99 @@ static int queue_kept_losses(const PassCtx &P, Batch &B) {
   return 0;
 }
 
+// The share of one caller in the static deal (do_grid_static): first, first + stride, ... over the point sources
+// 1..NumSrc and, behind them, the planes NumSrc + 1 .. NumSrc + nplane.
+static std::vector<int> dealt_share(const c2r_ctx *c, int first, int stride) {
+  std::vector<int> mine;
+  for (int ns = first; ns <= c->nsrc + c->nplane; ns += stride) mine.push_back(ns);
+  return mine;
+}
+
+static int plane_face_cells(const c2r_ctx *c, int axis) {
+  const PlaneGeom G = plane_geometry(c->g.n1, c->g.n2, c->g.n3, axis, 0);
+  return G.fa * G.fb;
+}
+
+// The planes of a pass (0-based numbers, in order), queued on the sweep stream: columns, rates, exit loss of each, one
+// plane after the other -- they share the column scratch, and every addition to a rate grid is grid = grid + term in plane
+// order.  The rate grids must hold what they are to be added to (the caller has carried out a pending zeroing).
+static int run_planes(PassCtx &P, const std::vector<int> &planes) {
+  c2r_ctx *c = P.c;
+  const Grid &g = c->g;
+  SedSet ss = P.ss; // a plane's SEDs need the tables only, whatever the point sources use
+  for (int k = 0; k < 2; k++) {
+    const bool on = c->have_sed[k];
+    ss.photo_thick[k + 1] = on ? c->d_sed_tab[k][0] : nullptr;
+    ss.photo_thin[k + 1] = on ? c->d_sed_tab[k][1] : nullptr;
+    ss.heat_thick[k + 1] = on && c->have_sed_heat[k] ? c->d_heat_woven[k + 1][0] : nullptr;
+    ss.heat_thin[k + 1] = on && c->have_sed_heat[k] ? c->d_heat_woven[k + 1][1] : nullptr;
+    ss.lo[k + 1] = on ? c->sed_lo[k] : 0;
+    ss.hi[k + 1] = on ? c->sed_hi[k] : 0;
+  }
+  const int tiles = ((g.n1 + 7) / 8) * ((g.n2 + 7) / 8) * ((g.n3 + 3) / 4);
+  for (int p : planes) {
+    const c2r_plane_source &pl = c->planes[p];
+    PlaneDev pd;
+    for (int s = 0; s < NSED; s++) pd.nf[s] = pl.normflux[s];
+    const bool multi = pd.nf[1] != 0.0 || pd.nf[2] != 0.0;
+    for (int k = 0; k < 2; k++) {
+      if (pd.nf[k + 1] != 0.0 && !c->have_sed[k]) return fail(c, "plane %d: flux of SED %d without c2r_set_sed_tables(%d)", p + 1, k + 1, k + 1);
+      if (pd.nf[k + 1] != 0.0 && !c->isothermal && !c->have_sed_heat[k])
+        return fail(c, "plane %d: non-isothermal run needs the heating tables of SED %d", p + 1, k + 1);
+    }
+    const PlaneGeom G = plane_geometry(g.n1, g.n2, g.n3, pl.axis, pl.from_high);
+    const double path = pl.axis == 0 ? P.sc.dr1 : (pl.axis == 1 ? P.sc.dr2 : P.sc.dr3);
+    const int face = G.fa * G.fb, fblk = (face + BLOCK - 1) / BLOCK;
+    hipEvent_t ev[3] = {};
+    for (hipEvent_t &e : ev)
+      if (c->timing && pool_event(c, &e)) return 1;
+    if (c->timing) HIPCHK(c, hipEventRecord(ev[0], c->stream));
+    hipLaunchKernelGGL(k_plane_columns, dim3(fblk), dim3(BLOCK), 0, c->stream, G, P.sc, path, g.ncell, c->d_ndens, c->d_xh_av, c->d_xhe_av,
+                       c->lls_on_grid ? c->d_lls : nullptr, c->plane_entry_set[p] ? c->d_plane_entry[p] : nullptr, c->d_plane_cin,
+                       c->d_plane_exit[p]);
+    c->tm.sweep_launches++;
+    if (c->timing) HIPCHK(c, hipEventRecord(ev[1], c->stream));
+    auto go = [&](auto kernel) {
+      hipLaunchKernelGGL(kernel, dim3(tiles), dim3(BLOCK), 0, c->stream, g, path, pd, c->d_ndens, c->d_xh_av, c->d_xhe_av, c->d_bands, ss,
+                         c->d_plane_cin, c->d_rates);
+    };
+    if (c->isothermal) multi ? go(k_plane_rates<false, true>) : go(k_plane_rates<false, false>);
+    else multi ? go(k_plane_rates<true, true>) : go(k_plane_rates<true, false>);
+    if (multi)
+      hipLaunchKernelGGL(k_plane_exit<true>, dim3(fblk), dim3(BLOCK), 0, c->stream, G, P.sc, path, pd, c->d_bands, ss, c->d_plane_cin,
+                         c->d_plane_exit[p], c->d_plane_partial);
+    else
+      hipLaunchKernelGGL(k_plane_exit<false>, dim3(fblk), dim3(BLOCK), 0, c->stream, G, P.sc, path, pd, c->d_bands, ss, c->d_plane_cin,
+                         c->d_plane_exit[p], c->d_plane_partial);
+    hipLaunchKernelGGL(k_loss_finish, dim3(1), dim3(BLOCK), 0, c->stream, c->d_plane_partial, fblk, fblk, c->d_plane_loss + p);
+    HIPCHK(c, hipGetLastError());
+    c->tm.rates_launches += 3;
+    if (c->timing) {
+      HIPCHK(c, hipEventRecord(ev[2], c->stream));
+      const hipEvent_t quad[4] = {ev[0], ev[1], ev[1], ev[2]}; // sweep start, sweep end, rates start, rates end (pass_finish)
+      P.tev.insert(P.tev.end(), quad, quad + 4);
+    }
+    HIPCHK(c, hipMemcpyAsync(c->h_plane_loss + p, c->d_plane_loss + p, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (!c->isothermal) c->phiheat_dirty = true;
+    c->plane_stamp[p] = P.stamp;
+    c->pass_planes.push_back(p);
+  }
+  return 0;
+}
+
 // nslab > 0: the caller wants to consume the rate grids slab by slab (z ranges) while later slabs are
 // still being computed: the rates launch of the LAST batch is cut into nslab launches, an event is
 // recorded after each, and the final synchronisation is left to pass_finish.
-static int pass_list(c2r_ctx *c, const std::vector<int> &mine, int nslab = 0) {
+// `dealt`: the caller's share of the deal -- point sources 1..NumSrc and planes NumSrc + 1 .. (dealt_share).  The planes
+// are added first, in plane order, then the point sources as they always were.
+static int pass_list(c2r_ctx *c, const std::vector<int> &dealt, int nslab = 0) {
   HIPCHK(c, hipSetDevice(c->device));
   if (c->pass_open) return fail(c, "previous c2r_pass_sources_begin was not closed by c2r_pass_sources_end");
+  std::vector<int> mine, planes;
+  for (int ns : dealt) {
+    if (ns > c->nsrc) planes.push_back(ns - c->nsrc - 1);
+    else mine.push_back(ns);
+  }
   struct InPass {
     c2r_ctx *c;
     explicit InPass(c2r_ctx *c_) : c(c_) { c->in_pass = true; }
@@ -3669,6 +3898,11 @@ static int pass_list(c2r_ctx *c, const std::vector<int> &mine, int nslab = 0) {
   P.stamp = ++passes;
   // a rank without sources writes nothing: a pending zeroing of the rate grids has to happen for real
   if (mine.empty() && flush_rates_zero(c)) return 1;
+  // planes add to the grids, so for them too; they are queued here, in front of the event the rates stream waits for:
+  // the point sources' rates launches then accumulate on top of them, and a pass without point sources records its slab
+  // events behind them
+  c->pass_planes.clear();
+  if (!planes.empty() && (flush_rates_zero(c) || run_planes(P, planes))) return 1;
   // everything queued earlier on the main stream (state upload, zeroing of the rates) must be
   // visible to the rates stream
   HIPCHK(c, hipEventRecord(c->ev_sweep_done[0], c->stream));
@@ -3746,6 +3980,11 @@ static int pass_finish(c2r_ctx *c) {
   // source, now that the losses the rates launches left behind have arrived
   resolve_tails(c, 0);
   resolve_tails(c, 1);
+  for (int p : c->pass_planes) { // the planes came first
+    c->plane_loss[p] = c->h_plane_loss[p];
+    c->photon_loss[0] = c->photon_loss[0] + c->plane_loss[p];
+  }
+  c->pass_planes.clear();
   for (const c2r_ctx::BatchTail &bt : c->tails)
     for (size_t b = 0; b < bt.loss.size(); b++) {
       c->photon_loss[0] = c->photon_loss[0] + bt.loss[b];
@@ -3772,11 +4011,9 @@ static int pass_finish(c2r_ctx *c) {
 static int pass_sources_one(c2r_ctx *c, int first, int stride) {
   if (check_ready(c, "c2r_pass_sources")) return 1;
   if (first < 1 || stride < 1) return fail(c, "c2r_pass_sources: first=%d stride=%d", first, stride);
-  std::vector<int> mine;
-  for (int ns = first; ns <= c->nsrc; ns += stride) mine.push_back(ns);
   c->last_first = first;
   c->last_stride = stride;
-  return pass_list(c, mine);
+  return pass_list(c, dealt_share(c, first, stride));
 }
 
 extern "C" int c2r_pass_sources_begin(c2r_ctx *c, int first, int stride, int nslab) {
@@ -3784,9 +4021,7 @@ extern "C" int c2r_pass_sources_begin(c2r_ctx *c, int first, int stride, int nsl
   if (!c->replicas.empty()) return fail(c, "c2r_pass_sources_begin: not available on a multi-device context");
   if (check_ready(c, "c2r_pass_sources_begin")) return 1;
   if (first < 1 || stride < 1 || nslab < 1) return fail(c, "c2r_pass_sources_begin: first=%d stride=%d nslab=%d", first, stride, nslab);
-  std::vector<int> mine;
-  for (int ns = first; ns <= c->nsrc; ns += stride) mine.push_back(ns);
-  return pass_list(c, mine, nslab);
+  return pass_list(c, dealt_share(c, first, stride), nslab);
 }
 
 extern "C" int c2r_pass_slab_count(c2r_ctx *c) { return c && c->pass_open ? c->pass_slabs : 0; }
@@ -3812,7 +4047,8 @@ extern "C" int c2r_do_source(c2r_ctx *c, int ns) {
   if (!c) return 1;
   if (!c->replicas.empty()) return fail(c, "c2r_do_source: not available on a multi-device context");
   if (check_ready(c, "c2r_do_source")) return 1;
-  if (ns < 1 || ns > c->nsrc) return fail(c, "c2r_do_source: source %d not in [1,%d]", ns, c->nsrc);
+  // (NumSrc < ns <= NumSrc + nplane: plane ns - NumSrc)
+  if (ns < 1 || ns > c->nsrc + c->nplane) return fail(c, "c2r_do_source: source %d not in [1,%d]", ns, c->nsrc + c->nplane);
   return pass_list(c, std::vector<int>{ns});
 }
 
@@ -4428,6 +4664,107 @@ extern "C" int c2r_set_sources(c2r_ctx *c, int nsrc, const int *srcpos, const do
   return for_replicas(c, [&](c2r_ctx *r) { return set_sources_one(r, nsrc, srcpos, normflux, s_star); });
 }
 
+// ---------------------------------------------------------------------------------------------
+// plane-parallel sources
+static int set_plane_sources_one(c2r_ctx *c, int nplane, const c2r_plane_source *planes) {
+  if (!c) return 1;
+  if (c->pass_open) return fail(c, "c2r_set_plane_sources: a pass opened by c2r_pass_sources_begin is still open (close it with c2r_pass_sources_end first)");
+  if (nplane < 0 || nplane > PLANE_MAX) return fail(c, "c2r_set_plane_sources: %d planes, expected 0..%d", nplane, PLANE_MAX);
+  if (nplane > 0 && !planes) return fail(c, "c2r_set_plane_sources: null argument");
+  for (int p = 0; p < nplane; p++) {
+    const c2r_plane_source &pl = planes[p];
+    if (pl.axis < 0 || pl.axis > 2) return fail(c, "c2r_set_plane_sources: plane %d: axis %d, expected 0, 1 or 2", p + 1, pl.axis);
+    if (pl.from_high != 0 && pl.from_high != 1) return fail(c, "c2r_set_plane_sources: plane %d: from_high %d, expected 0 or 1", p + 1, pl.from_high);
+    if (c->per[pl.axis])
+      return fail(c, "c2r_set_plane_sources: plane %d travels along axis %d, which is periodic (open it with c2r_set_boundaries_axes first)",
+                  p + 1, pl.axis);
+    for (int k = 0; k < NSED; k++)
+      if (!(pl.normflux[k] >= 0.0) || !std::isfinite(pl.normflux[k]))
+        return fail(c, "c2r_set_plane_sources: plane %d: normflux[%d] = %g", p + 1, k, pl.normflux[k]);
+    for (int k = 0; k < 2; k++)
+      if (pl.normflux[k + 1] != 0.0 && !c->have_sed[k])
+        return fail(c, "c2r_set_plane_sources: plane %d has a flux of SED %d, whose tables have not been set (c2r_set_sed_tables(%d))",
+                    p + 1, k + 1, k + 1);
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipStreamSynchronize(c->stream)); // nothing queued may still use the buffers that are about to go
+  free_plane_buffers(c);
+  c->nplane = 0;
+  c->pass_planes.clear();
+  for (int p = 0; p < PLANE_MAX; p++) { c->plane_loss[p] = 0.0; c->plane_stamp[p] = 0; }
+  if (nplane == 0) return 0;
+  int face_max = 0;
+  HIPCHK(c, hipMalloc(&c->d_plane_cin, sizeof(double) * 3 * c->g.ncell));
+  for (int p = 0; p < nplane; p++) {
+    const size_t n3 = 3 * (size_t)plane_face_cells(c, planes[p].axis);
+    face_max = std::max(face_max, (int)(n3 / 3));
+    HIPCHK(c, hipMalloc(&c->d_plane_entry[p], sizeof(double) * n3));
+    HIPCHK(c, hipMalloc(&c->d_plane_exit[p], sizeof(double) * n3));
+    HIPCHK(c, zero_device(c->d_plane_exit[p], sizeof(double) * n3, c->stream));
+  }
+  HIPCHK(c, hipMalloc(&c->d_plane_partial, sizeof(double) * (size_t)((face_max + BLOCK - 1) / BLOCK)));
+  HIPCHK(c, hipMalloc(&c->d_plane_loss, sizeof(double) * PLANE_MAX));
+  HIPCHK(c, hipHostMalloc(&c->h_plane_loss, sizeof(double) * PLANE_MAX));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  std::copy(planes, planes + nplane, c->planes);
+  c->nplane = nplane;
+  return 0;
+}
+
+extern "C" int c2r_set_plane_sources(c2r_ctx *c, int nplane, const c2r_plane_source *planes) {
+  if (int e_ = set_plane_sources_one(c, nplane, planes)) return e_;
+  return for_replicas(c, [&](c2r_ctx *r) { return set_plane_sources_one(r, nplane, planes); });
+}
+
+extern "C" int c2r_get_plane_count(const c2r_ctx *c) { return c ? c->nplane : 0; }
+
+static int set_plane_entry_columns_one(c2r_ctx *c, int plane, const double *cols3) {
+  if (!c) return 1;
+  if (plane < 1 || plane > c->nplane) return fail(c, "c2r_set_plane_entry_columns: plane %d not in [1,%d]", plane, c->nplane);
+  if (c->pass_open) return fail(c, "c2r_set_plane_entry_columns: a pass opened by c2r_pass_sources_begin is still open");
+  const int p = plane - 1;
+  c->plane_entry_set[p] = false;
+  if (!cols3) return 0;
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t n3 = 3 * (size_t)plane_face_cells(c, c->planes[p].axis);
+  HIPCHK(c, hipMemcpyAsync(c->d_plane_entry[p], cols3, sizeof(double) * n3, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  c->plane_entry_set[p] = true;
+  return 0;
+}
+
+extern "C" int c2r_set_plane_entry_columns(c2r_ctx *c, int plane, const double *cols3) {
+  if (int e_ = set_plane_entry_columns_one(c, plane, cols3)) return e_;
+  return for_replicas(c, [&](c2r_ctx *r) { return set_plane_entry_columns_one(r, plane, cols3); });
+}
+
+// the device of the context that ran plane p (0-based) last: the deal gives a plane to one device per pass
+static c2r_ctx *plane_owner(c2r_ctx *c, int p) {
+  c2r_ctx *best = c;
+  for (c2r_ctx *r : c->replicas)
+    if (r->plane_stamp[p] > best->plane_stamp[p]) best = r;
+  return best;
+}
+
+extern "C" int c2r_download_plane_exit_columns(c2r_ctx *c, int plane, double *cols3) {
+  if (!c) return 1;
+  if (plane < 1 || plane > c->nplane || !cols3) return fail(c, "c2r_download_plane_exit_columns: plane %d not in [1,%d], or null argument", plane, c->nplane);
+  c2r_ctx *d = plane_owner(c, plane - 1);
+  HIPCHK(c, hipSetDevice(d->device));
+  const size_t n3 = 3 * (size_t)plane_face_cells(d, d->planes[plane - 1].axis);
+  HIPCHK(c, hipMemcpyAsync(cols3, d->d_plane_exit[plane - 1], sizeof(double) * n3, hipMemcpyDeviceToHost, d->stream));
+  HIPCHK(c, hipStreamSynchronize(d->stream));
+  return 0;
+}
+
+extern "C" int c2r_get_plane_loss(c2r_ctx *c, int plane, double *loss) {
+  if (!c) return 1;
+  if (plane < 1 || plane > c->nplane || !loss) return fail(c, "c2r_get_plane_loss: plane %d not in [1,%d], or null argument", plane, c->nplane);
+  if (c->pass_open) return fail(c, "c2r_get_plane_loss: a pass opened by c2r_pass_sources_begin is still open");
+  *loss = plane_owner(c, plane - 1)->plane_loss[plane - 1];
+  return 0;
+}
+
 extern "C" int c2r_set_sed_tables(c2r_ctx *c, int sed, const double *photo_thick, const double *photo_thin, const double *heat_thick, const double *heat_thin, int lower, int upper) {
   if (int e_ = set_sed_tables_one(c, sed, photo_thick, photo_thin, heat_thick, heat_thin, lower, upper)) return e_;
   return for_replicas(c, [&](c2r_ctx *r) { return set_sed_tables_one(r, sed, photo_thick, photo_thin, heat_thick, heat_thin, lower, upper); });
@@ -4485,6 +4822,10 @@ static int set_boundaries_one(c2r_ctx *c, const int periodic[3]) {
   if (!c) return 1;
   if (c->pass_open) return fail(c, "c2r_set_boundaries: a pass opened by c2r_pass_sources_begin is still open (close it with c2r_pass_sources_end first)");
   const bool per[3] = {periodic[0] != 0, periodic[1] != 0, periodic[2] != 0};
+  for (int p = 0; p < c->nplane; p++)
+    if (per[c->planes[p].axis])
+      return fail(c, "c2r_set_boundaries: plane source %d travels along axis %d, which has to stay open (remove the planes with "
+                  "c2r_set_plane_sources(ctx, 0, NULL) first)", p + 1, c->planes[p].axis);
   if (per[0] == c->per[0] && per[1] == c->per[1] && per[2] == c->per[2]) return 0;
   const bool want = per[0] && per[1] && per[2];
   HIPCHK(c, hipSetDevice(c->device));

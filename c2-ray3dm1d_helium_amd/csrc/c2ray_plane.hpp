@@ -1,0 +1,112 @@
+// Plane-parallel sources: the per-cell rule of a plane wave that enters through an open mesh face and travels along
+// one axis (include/c2ray_hip.h c2r_set_plane_sources).
+//
+// Every line of cells along the axis is a 1-D problem of its own: no cinterp (the incoming column of a cell is the
+// outgoing column of the cell before it), no 1/r^2 dilution (NormFlux per cm^2 of face enters a column of cross-section
+// A and is absorbed in the volume A * dr[axis]: vol_ph = dr[axis]).  Everything per cell is what a point source gets:
+// coldens, the LLS fog, the max_coldensh guard, photoion_rates / photoion_rates_multi, the secondary-ionisation
+// parameters, the denominators of evolve_point.F90:288-296 -- the functions of c2ray_device.hpp, unchanged.
+//
+// Like c2ray_device.hpp this file compiles with a host C++ compiler (tests/plane_harness.cpp marches whole meshes with
+// these functions on the CPU against a NumPy reference built from the oracle's per-cell routines).
+#pragma once
+
+#include "c2ray_device.hpp"
+
+namespace c2r {
+
+constexpr int PLANE_MAX = 6; // most planes of a context: one per face of the mesh
+
+// Step 1: neufrac * ndens of the three species with the fractions clamped at epsilon (evolve_point.F90:132-136), the
+// first product of coldens (doric.f90:358-372) -- what sweep_cell_state reads or forms for a point source.
+C2R_HD void plane_cell_state(double nd, double xh_av0, double xhe_av0, double xhe_av1, double &u_HI, double &u_HeI, double &u_HeII) {
+  u_HI = dmax(xh_av0, epsilon) * nd;
+  u_HeI = dmax(xhe_av0, epsilon) * nd;
+  u_HeII = dmax(xhe_av1, epsilon) * nd;
+}
+
+// Step 4: the Lyman-limit-system fog on the incoming HI column (evolve_point.F90:177-180), every cell of the march
+C2R_HD double plane_fog(double cin_HI, double coldensh_LLS, double path, double dr1) { return cin_HI + coldensh_LLS * path / dr1; }
+
+// Step 5: the outgoing columns, coldens evaluated from the left (neufrac * ndens * path * abundance)
+C2R_HD void plane_cell_out(double cin_HI, double cin_HeI, double cin_HeII, double u_HI, double u_HeI, double u_HeII, double path,
+                           double &cout_HI, double &cout_HeI, double &cout_HeII) {
+  cout_HI = cin_HI + u_HI * path * (1.0 - abu_he);
+  cout_HeI = cin_HeI + u_HeI * path * abu_he;
+  cout_HeII = cin_HeII + u_HeII * path * abu_he;
+}
+
+// Steps 1-5 for one cell of a march: `cin_*` come in as the outgoing columns of the cell before (or the entry columns)
+// and leave with the fog applied, as every later step sees them.
+C2R_HD void plane_cell_columns(double nd, double xh_av0, double xhe_av0, double xhe_av1, double path, double dr1, int use_lls,
+                               double coldensh_LLS, double &cin_HI, double cin_HeI, double cin_HeII, double &cout_HI,
+                               double &cout_HeI, double &cout_HeII) {
+  double u_HI, u_HeI, u_HeII;
+  plane_cell_state(nd, xh_av0, xhe_av0, xhe_av1, u_HI, u_HeI, u_HeII);
+  if (use_lls) cin_HI = plane_fog(cin_HI, coldensh_LLS, path, dr1);
+  plane_cell_out(cin_HI, cin_HeI, cin_HeII, u_HI, u_HeI, u_HeII, path, cout_HI, cout_HeI, cout_HeII);
+}
+
+// Step 6: what the plane adds to the four rate grids of one cell (add = phih, phihe0, phihe1, phiheat terms).  Returns
+// false -- nothing is added -- where the incoming HI column has reached max_coldensh (evolve_point.F90:246).
+// u_*: the cell's neufrac * ndens (plane_cell_state); the denominators of evolve_point.F90:288-296,
+// neufrac * ndens * abundance from the left, are their products with the abundances.  h_av1: xh_av(q,1), the ionised
+// fraction the secondary-ionisation parameters depend on (:255).  nf: NormFlux per cm^2 of face of the three SEDs;
+// MULTI: the power-law or the quasar-like flux is non-zero (photoion_rates_multi).
+template <bool HEAT, bool MULTI, class LT, class BD>
+C2R_HD bool plane_cell_rates(const BD &bd, const SedSet &ss, double cin_HI, double cout_HI, double cin_HeI, double cout_HeI,
+                             double cin_HeII, double cout_HeII, double vol_ph, const double (&nf)[NSED], double h_av1, double u_HI,
+                             double u_HeI, double u_HeII, double (&add)[4], const LT *logtab, const gm::LogPins *pins = nullptr) {
+  if (!(cin_HI < max_coldensh)) return false;
+  Ricotti ric = {};
+  if (HEAT) ric = ricotti_parameters(dmax(h_av1, epsilon));
+  PhotoOut o;
+  if (MULTI)
+    photoion_rates_multi<HEAT>(bd, ss, cin_HI, cout_HI, cin_HeI, cout_HeI, cin_HeII, cout_HeII, vol_ph, nf, ric, o, logtab, pins);
+  else
+    photoion_rates<HEAT>(bd, ss.photo_thick[0], ss.photo_thin[0], ss.heat_thick[0], ss.heat_thin[0], cin_HI, cout_HI, cin_HeI,
+                         cout_HeI, cin_HeII, cout_HeII, vol_ph, nf[0], ric, o, logtab, pins);
+  add[0] = o.photo_HI / (u_HI * (1.0 - abu_he));
+  add[1] = o.photo_HeI / (u_HeI * abu_he);
+  add[2] = o.photo_HeII / (u_HeII * abu_he);
+  add[3] = HEAT ? o.heat : 0.0;
+  return true;
+}
+
+// Step 7: what one column of the plane loses through the far face, from the columns of its last cell
+// (evolve_point.F90:310-315 with vol_ph = dr[axis]); 0 where that cell is beyond max_coldensh.
+template <bool MULTI>
+C2R_HD double plane_exit_term(const BandData &bd, const SedSet &ss, double cin_HI, double cout_HI, double cin_HeI, double cout_HeI,
+                              double cin_HeII, double cout_HeII, const double (&nf)[NSED], double vol, double dr_axis) {
+  if (!(cin_HI < max_coldensh)) return 0.0;
+  const double po = MULTI ? photo_out_multi(bd, ss, cin_HI, cout_HI, cin_HeI, cout_HeI, cin_HeII, cout_HeII, nf)
+                          : photo_out_only(bd, ss.photo_thick[0], ss.photo_thin[0], cin_HI, cout_HI, cin_HeI, cout_HeI, cin_HeII,
+                                           cout_HeII, nf[0]);
+  return po * vol / dr_axis;
+}
+
+// The cells of a march.  Column f of the face (mesh order of the two remaining axes, the lower axis fastest), step m in
+// travel order: the 0-based mesh cell number.  from_high: the wave enters at index mesh[axis] and travels towards 1.
+struct PlaneGeom {
+  int n[3];      // mesh
+  int axis, from_high;
+  int na;        // cells along the axis
+  int fa, fb;    // extents of the two remaining axes (lower first)
+  size_t sa, sf, sg; // strides, in cells, of the axis and of the two face axes
+};
+C2R_HD PlaneGeom plane_geometry(int n1, int n2, int n3, int axis, int from_high) {
+  PlaneGeom G;
+  G.n[0] = n1; G.n[1] = n2; G.n[2] = n3;
+  G.axis = axis; G.from_high = from_high;
+  const size_t stride[3] = {1, (size_t)n1, (size_t)n1 * (size_t)n2};
+  const int a = axis, f = axis == 0 ? 1 : 0, g = axis == 2 ? 1 : 2;
+  G.na = G.n[a]; G.fa = G.n[f]; G.fb = G.n[g];
+  G.sa = stride[a]; G.sf = stride[f]; G.sg = stride[g];
+  return G;
+}
+C2R_HD size_t plane_cell(const PlaneGeom &G, int f, int m) {
+  const int along = G.from_high ? G.na - 1 - m : m;
+  return (size_t)(f % G.fa) * G.sf + (size_t)(f / G.fa) * G.sg + (size_t)along * G.sa;
+}
+
+} // namespace c2r

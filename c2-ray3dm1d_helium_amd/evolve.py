@@ -470,6 +470,59 @@ class HipEngine:
         self._chk(self.lib.c2r_get_boundaries_axes(self.h, out))
         return tuple(bool(v) for v in out)
 
+    # -- plane-parallel sources (c2r_set_plane_sources; include/c2ray_hip.h has the rule) ---------------------
+    def set_plane_sources(self, planes):
+        """Plane waves entering through open mesh faces.  `planes`: a list of (axis, from_high, normflux) or of dicts with
+        those keys -- axis 0..2 (it must be open), from_high 0 / 1 (entering at index 1 / at index mesh[axis]), normflux a
+        number (black body only) or three, one per SED, per cm^2 of face.  An empty list removes them.  Plane p (1-based)
+        is source NumSrc + p of every deal."""
+        items = []
+        for pl in planes or ():
+            axis, from_high, flux = (pl["axis"], pl["from_high"], pl["normflux"]) if isinstance(pl, dict) else pl
+            flux = [float(x) for x in np.atleast_1d(np.asarray(flux, dtype=np.float64))]
+            if len(flux) not in (1, 3):
+                raise ValueError("set_plane_sources: normflux is one number or three (black body, power law, quasar-like)")
+            items.append((int(axis), int(from_high), (flux + [0.0, 0.0])[:3]))
+        arr = (_lib.PlaneSource * max(1, len(items)))()
+        for a, (axis, from_high, flux) in zip(arr, items):
+            a.axis, a.from_high = axis, from_high
+            a.normflux[:] = flux
+        self._chk(self.lib.c2r_set_plane_sources(self.h, len(items), arr if items else None))
+        self._plane_axes = [axis for axis, _, _ in items]
+
+    @property
+    def plane_count(self):
+        return int(self.lib.c2r_get_plane_count(self.h))
+
+    def _face_cells(self, p):
+        """Face cells of plane p (1-based): the product of the two extents across its axis."""
+        axes = getattr(self, "_plane_axes", [])
+        if not 1 <= int(p) <= len(axes):
+            raise C2RayHipError(f"plane {p} not in [1,{len(axes)}]")
+        return self.ncell // self.mesh[axes[int(p) - 1]]
+
+    def set_plane_entry_columns(self, p, cols3=None):
+        """Entry columns of plane p (1-based): 3 x face cells (HI, HeI, HeII; face cells in mesh order of the two remaining
+        axes, the lower axis fastest), e.g. the plane_exit_columns of the slab upstream.  None: zero again."""
+        a = None
+        if cols3 is not None:
+            a = _f64(cols3).reshape(-1)
+            if a.size != 3 * self._face_cells(p):
+                raise ValueError(f"set_plane_entry_columns: {a.size} values, expected 3 x {self._face_cells(p)}")
+        self._chk(self.lib.c2r_set_plane_entry_columns(self.h, int(p), _dp(a)))
+
+    def plane_exit_columns(self, p):
+        """Outgoing columns of the last cell of every column of plane p, from the last pass that ran it (3 x face cells)."""
+        out = np.empty(3 * self._face_cells(p))
+        self._chk(self.lib.c2r_download_plane_exit_columns(self.h, int(p), _dp(out)))
+        return out
+
+    def plane_loss(self, p):
+        """What plane p added to photon_loss(1) in the last pass that ran it."""
+        loss = C.c_double(0.0)
+        self._chk(self.lib.c2r_get_plane_loss(self.h, int(p), C.byref(loss)))
+        return loss.value
+
     def enable_timing(self, on=True):
         self._chk(self.lib.c2r_enable_timing(self.h, int(on)))
 
@@ -629,6 +682,7 @@ class Evolve:
             niter = int(dump["niter"])
             conv_flag = e.global_pass(dt)
             self.conv_flags.append(conv_flag)
+        numsrc += getattr(e, "plane_count", 0)    # a plane (HipEngine.set_plane_sources) is source NumSrc + p of every deal
         conv_criterion = min(int(convergence_fraction * self.mesh[0] * self.mesh[1] * self.mesh[2]), numsrc)
         while True:
             if conv_flag < conv_criterion and niter > 1:

@@ -56,6 +56,12 @@ module c2ray_hip
      real(c_double) :: allreduce_ms, allreduce_exposed_ms, tail_ms
   end type c2r_comm_timing
 
+  !> c2r_plane_source of include/c2ray_hip.h: a plane wave entering through an open mesh face (axis is 0-based)
+  type, bind(C) :: c2r_plane_source
+     integer(c_int) :: axis, from_high
+     real(c_double) :: normflux(3)
+  end type c2r_plane_source
+
   !> c2r_sed_setup of include/c2ray_hip.h: what spec_integration starts from for one SED
   type, bind(C) :: c2r_sed_setup
      integer(c_int) :: nfreq, sed
@@ -542,6 +548,40 @@ module c2ray_hip
        type(c_ptr), value :: ctx
        integer(c_int), intent(out) :: periodic(3)
      end function c2r_get_boundaries_axes
+
+     !> plane-parallel sources (include/c2ray_hip.h): plane p is "source NumSrc + p" of every deal; nplane = 0 removes them
+     integer(c_int) function c2r_set_plane_sources(ctx, nplane, planes) bind(C, name="c2r_set_plane_sources")
+       import :: c_int, c_ptr, c2r_plane_source
+       type(c_ptr), value :: ctx
+       integer(c_int), value :: nplane
+       type(c2r_plane_source), intent(in) :: planes(*)
+     end function c2r_set_plane_sources
+
+     integer(c_int) function c2r_get_plane_count(ctx) bind(C, name="c2r_get_plane_count")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: ctx
+     end function c2r_get_plane_count
+
+     !> cols3: (face cells, 3) -- HI, HeI, HeII; a c_null_ptr sets the entry columns to zero again
+     integer(c_int) function c2r_set_plane_entry_columns(ctx, plane, cols3) bind(C, name="c2r_set_plane_entry_columns")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: ctx, cols3
+       integer(c_int), value :: plane
+     end function c2r_set_plane_entry_columns
+
+     integer(c_int) function c2r_download_plane_exit_columns(ctx, plane, cols3) bind(C, name="c2r_download_plane_exit_columns")
+       import :: c_int, c_ptr, c_double
+       type(c_ptr), value :: ctx
+       integer(c_int), value :: plane
+       real(c_double), intent(out) :: cols3(*)
+     end function c2r_download_plane_exit_columns
+
+     integer(c_int) function c2r_get_plane_loss(ctx, plane, loss) bind(C, name="c2r_get_plane_loss")
+       import :: c_int, c_ptr, c_double
+       type(c_ptr), value :: ctx
+       integer(c_int), value :: plane
+       real(c_double), intent(out) :: loss
+     end function c2r_get_plane_loss
 
      integer(c_int) function c2r_enable_timing(ctx, on) bind(C, name="c2r_enable_timing")
        import :: c_int, c_ptr

@@ -305,6 +305,50 @@ int c2r_set_boundaries_axes(c2r_ctx *ctx, const int periodic[3]);
 /* out[d] = 1: axis d is periodic, 0: open */
 int c2r_get_boundaries_axes(const c2r_ctx *ctx, int out[3]);
 
+/* Plane-parallel sources: a plane wave that enters the mesh through an OPEN face and travels along one axis -- a slab lit
+ * from outside, or slabs stacked along the line of sight that hand radiation to each other.  Axis-aligned incidence, one
+ * uniform flux per plane.  A plane is not a many-source approximation: every line of cells along the axis is a 1-D
+ * problem of its own, without cinterp (the incoming columns of a cell are the outgoing columns of the cell before it)
+ * and without 1/r^2 dilution; everything per cell is what a point source gets (csrc/c2ray_plane.hpp).
+ *   axis       0, 1 or 2: the axis the photons travel along; it must be open (c2r_set_boundaries_axes)
+ *   from_high  0: they enter through the face at index 1 and travel towards index mesh[axis]; 1: the other way
+ *   normflux   NormFlux of c2r_set_sources PER CM^2 OF FACE, one value per SED (black body, power law, quasar-like);
+ *              S_star / pl_S_star / qpl_S_star stay those of c2r_set_sources / c2r_set_sources_sed.  A non-zero
+ *              normflux[1] / [2] needs that SED's tables (c2r_set_sed_tables).
+ * For every column (the two other indices fixed), in travel order, with q the cell, path = dr[axis]:
+ *   N_in of the first cell = its entry column (0 unless set below), of every other cell N_out of the cell before;
+ *   with LLS in force N_in(HI) = N_in(HI) + coldensh_LLS*path/dr(1), in every cell;
+ *   N_out = N_in + max(x_av(q), epsilon)*ndens(q)*path*abundance (coldens, from the left);
+ *   if N_in(HI) < max_coldensh: photoion_rates with these columns, vol_ph = dr[axis] (NormFlux*A photons per second are
+ *   absorbed in the volume A*dr[axis]), the plane's flux and the cell's secondary-ionisation parameters, and
+ *   phih += photo_HI / (x_av*ndens*(1-abu_he)), phihe likewise, phiheat += heat (evolve_point.F90:288-306);
+ *   after the last cell the column adds photo_out*vol/dr[axis] to photon_loss(1) (0 beyond max_coldensh).  sum_nbox is
+ *   not touched.  The sum over the columns has a fixed order: the same bits every time.
+ * Plane p (1-based) is "source NumSrc + p" of the static deal: c2r_pass_sources(first, stride), its slab-wise form, the
+ * per-device deal of a multi-device context, c2r_pass_allreduce_chemistry, c2r_iteration and c2r_evolve3d (whose
+ * convergence criterion counts a plane as a source) give it to exactly one caller, and c2r_do_source(NumSrc + p) runs it.
+ * The planes a caller owns are added before its point sources, in plane order.
+ * c2r_set_plane_sources replaces the list (nplane = 0 removes it; at most 6) on every device of a multi-device context
+ * and allocates what the planes need: 3 doubles per cell and two face buffers per plane.  It is refused for a plane
+ * along a periodic axis, a bad axis, and between c2r_pass_sources_begin and c2r_pass_sources_end; c2r_set_boundaries*
+ * refuses to make a plane's axis periodic while planes are set.  c2r_set_sources leaves the planes alone.
+ * c2r_evolve0d and c2r_get_source_trace do not know planes. */
+typedef struct {
+  int axis;
+  int from_high;
+  double normflux[3];
+} c2r_plane_source;
+int c2r_set_plane_sources(c2r_ctx *ctx, int nplane, const c2r_plane_source *planes);
+int c2r_get_plane_count(const c2r_ctx *ctx);
+/* Entry columns of plane `plane` (1-based): (HI, HeI, HeII) x the face, the face cells in mesh order of the two remaining
+ * axes (the lower axis fastest), species slowest -- what a slab upstream handed over.  NULL: zero again. */
+int c2r_set_plane_entry_columns(c2r_ctx *ctx, int plane, const double *cols3);
+/* The outgoing columns of the last cell of every column, same layout, from the last pass that ran the plane: the entry
+ * columns of the next slab downstream. */
+int c2r_download_plane_exit_columns(c2r_ctx *ctx, int plane, double *cols3);
+/* What the plane added to photon_loss(1) in the last pass that ran it. */
+int c2r_get_plane_loss(c2r_ctx *ctx, int plane, double *loss);
+
 /* ---- several GPUs: sources over ranks and the sum over ranks ----------------------------------------
  * The reference's MPI strategy (master_slave.F90:74-96 do_grid_static, evolve.F90:505-548
  * mpi_accumulate_grid_quantities): every rank holds the full grid, rank r sweeps sources r+1, r+1+npr, ...,
