@@ -16,6 +16,8 @@
 //   tables         k_build_tables  spec_integration: the photo-ionisation / heating tables of one SED
 //   plane sources  k_plane_columns, k_plane_rates, k_plane_exit   a plane wave entering through an open mesh face: the 1-D
 //                                  march of every line of cells along the axis, its rates, what leaves through the far face
+//   escape maps    k_face_loss, k_face_plane_exit   the kept loss of an open box per cell of the mesh face it leaves through
+//                                  (c2r_enable_face_loss): a gather, one lane per face cell, the sources in source order
 //
 // Compile: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fPIC -shared
 #include <hip/hip_runtime.h>
@@ -36,6 +38,7 @@
 
 #include "../../include/c2ray_hip.h"
 #include "c2ray_device.hpp"
+#include "c2ray_face.hpp"
 #include "c2ray_plane.hpp"
 #include "c2ray_shell.hpp"
 
@@ -1657,6 +1660,92 @@ k_plane_exit(PlaneGeom G, StepScalars sc, double path, PlaneDev pl, const BandDa
   if (threadIdx.x == 0) partial[blockIdx.x] = bs;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Escape maps (c2r_enable_face_loss; the rule is c2ray_face.hpp): the terms of the kept loss of an
+// open box, photo_out * vol / vol_ph of the cells on open mesh faces, kept per face cell instead of summed.
+struct FaceLayout {
+  int n[3];    // mesh
+  int open[3]; // the axis is open
+};
+
+// A gather: lane f of block (x, face) owns face cell x * 256 + f of that face and walks the batch's sources in source
+// order, as k_rates walks them for a mesh cell, map = map + term for every source whose final sub-box holds the cell and
+// whose rule (face_of_cell) gives the cell to this face.  No atomics: the same bits every time and for every batch size.
+// The term is k_loss<true, false>'s, from the same columns through the same functions -- the kernel runs on the sweep
+// stream between the batch's last shell and the rates launch, which overwrites N_in(HI) of these cells with the term
+// itself (SrcDev::loss_lo).  A wave sits on one face; the source record is uniform over the block (scalar loads); the face
+// cells of a source's outermost shell are contiguous runs of its shell-ordered block, so a wave's loads coalesce.
+// One lane per face cell leaves the device mostly idle (6 N^2 lanes) -- and costs 6/N of k_rates' cell.source pairs.
+template <bool MULTI>
+__global__ void __launch_bounds__(BLOCK)
+k_face_loss(FaceLayout L, const SrcDev *__restrict__ src, int nsrc, StepScalars sc, const BandData *__restrict__ bd, SedSet ss,
+            double *__restrict__ maps) {
+  const int face = (int)blockIdx.y;
+  const int axis = face >> 1;
+  if (!face_pick(axis, L.open[0], L.open[1], L.open[2])) return;
+  const int f = (int)blockIdx.x * BLOCK + (int)threadIdx.x;
+  if (f >= face_cells(L.n, axis)) return;
+  int m[3];
+  face_cell_decode(L.n, face, f, m);
+  const double dr[3] = {sc.dr1, sc.dr2, sc.dr3};
+  double *const slot = maps + face_map_offset(L.n, L.open, face) + f;
+  double acc = *slot;
+  bool touched = false;
+  for (int e = 0; e < nsrc; e++) {
+    const SrcDev &S = src[e];
+    const int o[3] = {axis_offset(m[0], S.i0, S.wn[0]), axis_offset(m[1], S.j0, S.wn[1]), axis_offset(m[2], S.k0, S.wn[2])};
+    const bool outside = o[0] < S.lo[0] || o[0] > S.hi[0] || o[1] < S.lo[1] || o[1] > S.hi[1] || o[2] < S.lo[2] || o[2] > S.hi[2];
+    if (outside) continue;
+    if (face_of_cell(L.n, L.open, m, o, dr) != face) continue;
+    const size_t cz = S.cz;
+    const size_t p = reach_position(S.rl, S.rr, o[0], o[1], o[2]);
+    const global_double *cs = (const global_double *)S.cols;
+    const double cin_HI = cs[col_in(p, 0, cz)], cin_HeI = cs[col_in(p, 1, cz)], cin_HeII = cs[col_in(p, 2, cz)];
+    const double cout_HI = cs[col_out(p, 0, cz)], cout_HeI = cs[col_out(p, 1, cz)], cout_HeII = cs[col_out(p, 2, cz)];
+    if (!(cin_HI < max_coldensh)) continue;
+    double vol_ph;
+    if (o[0] == 0 && o[1] == 0 && o[2] == 0) {
+      vol_ph = sc.dr1 * sc.dr2 * sc.dr3;
+    } else {
+      const double path = sc_path(o[0], o[1], o[2]) * sc.dr1;
+      const double xs = sc.dr1 * (double)o[0], ys = sc.dr2 * (double)o[1], zs = sc.dr3 * (double)o[2];
+      const double dist2 = xs * xs + ys * ys + zs * zs;
+      vol_ph = 4.0 * pi * dist2 * path;
+    }
+    double po;
+    if (MULTI) {
+      const double nf[NSED] = {S.nflux, S.nflux_sed[0], S.nflux_sed[1]};
+      po = photo_out_multi(*bd, ss, cin_HI, cout_HI, cin_HeI, cout_HeI, cin_HeII, cout_HeII, nf);
+    } else {
+      po = photo_out_only(*bd, ss.photo_thick[0], ss.photo_thin[0], cin_HI, cout_HI, cin_HeI, cout_HeI, cin_HeII, cout_HeII, S.nflux);
+    }
+    acc = acc + po * sc.vol / vol_ph;
+    touched = true;
+  }
+  if (touched) *slot = acc;
+}
+
+// k_plane_exit with the per-line term kept: the same terms, the same block sums, and map = map + term at the line's
+// face cell of the plane's far face (`map`: that face's map; a plane's face cells are the map's, in its order).
+template <bool MULTI>
+__global__ void __launch_bounds__(BLOCK)
+k_face_plane_exit(PlaneGeom G, StepScalars sc, double path, PlaneDev pl, const BandData *__restrict__ bd, SedSet ss,
+                 const double *__restrict__ cin, const double *__restrict__ exit_cols, double *__restrict__ partial,
+                 double *__restrict__ map) {
+  __shared__ double sh[BLOCK / 64];
+  const int face = G.fa * G.fb;
+  const int f = (int)blockIdx.x * BLOCK + (int)threadIdx.x;
+  double term = 0.0;
+  if (f < face) {
+    const size_t q = plane_cell(G, f, G.na - 1);
+    term = plane_exit_term<MULTI>(*bd, ss, cin[3 * q], exit_cols[f], cin[3 * q + 1], exit_cols[face + f], cin[3 * q + 2],
+                                  exit_cols[2 * face + f], pl.nf, sc.vol, path);
+    map[f] = map[f] + term;
+  }
+  const double bs = block_sum(term, sh);
+  if (threadIdx.x == 0) partial[blockIdx.x] = bs;
+}
+
 } // namespace
 
 // =============================================================================================
@@ -1834,6 +1923,12 @@ struct c2r_ctx {
   double plane_loss[PLANE_MAX] = {}; // the term plane p added to photon_loss(1) in the last pass that ran it
   long long plane_stamp[PLANE_MAX] = {}; // ... and which pass that was (as trace_stamp)
   std::vector<int> pass_planes;     // planes (0-based) of the pass in flight, in order
+
+  // escape maps (c2r_enable_face_loss): the maps of the open faces one behind the other, in face order (face_map_offset,
+  // c2ray_face.hpp); made by c2r_enable_face_loss and made anew by a change of boundary mode: never allocated inside a pass
+  bool face_on = false;
+  double *d_face_maps = nullptr;    // null while the feature is off or no axis is open
+  size_t face_total = 0;            // doubles in it
 
   // second stream for the rates kernels: the (latency-bound) column sweep of batch n+1 runs beside
   // the (ALU-bound) rates kernel of batch n; two scratch sets ping-pong between them
@@ -2160,6 +2255,28 @@ extern "C" int c2r_create(c2r_ctx **out, int device, const int mesh[3]) {
   return 0;
 }
 
+// the escape maps of one device (c2r_enable_face_loss, set_boundaries_one, c2r_destroy)
+static void free_face_maps(c2r_ctx *c) {
+  if (c->d_face_maps) (void)hipFree(c->d_face_maps);
+  c->d_face_maps = nullptr;
+  c->face_total = 0;
+}
+
+// ... made anew for the boundary mode in force, and zeroed (no buffer when no axis is open)
+static int alloc_face_maps(c2r_ctx *c) {
+  HIPCHK(c, hipSetDevice(c->device));
+  if (c->d_face_maps) HIPCHK(c, hipStreamSynchronize(c->stream)); // nothing queued may still add to them
+  free_face_maps(c);
+  const int n[3] = {c->g.n1, c->g.n2, c->g.n3}, open[3] = {!c->per[0], !c->per[1], !c->per[2]};
+  const size_t total = (size_t)face_map_offset(n, open, 6);
+  if (total == 0) return 0;
+  HIPCHK(c, hipMalloc(&c->d_face_maps, sizeof(double) * total));
+  c->face_total = total;
+  HIPCHK(c, zero_device(c->d_face_maps, sizeof(double) * total, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return 0;
+}
+
 // the device and pinned buffers of the plane sources (c2r_set_plane_sources makes them, removal and c2r_destroy free them)
 static void free_plane_buffers(c2r_ctx *c) {
   for (int p = 0; p < PLANE_MAX; p++) {
@@ -2229,6 +2346,7 @@ extern "C" void c2r_destroy(c2r_ctx *c) {
       if (q) (void)hipHostFree(q);
   }
   free_plane_buffers(c);
+  free_face_maps(c);
   if (c->h_conv) (void)hipHostFree(c->h_conv);
   if (c->h_stat) (void)hipHostFree(c->h_stat);
   if (c->h_iter) (void)hipHostFree(c->h_iter);
@@ -2892,6 +3010,8 @@ static int set_rates_to_zero_one(c2r_ctx *c) {
   c->rates_zero_pending = true;
   std::memset(c->photon_loss, 0, sizeof c->photon_loss);
   c->sum_nbox = 0;
+  // the escape maps follow photon_loss (on the sweep stream, which every kernel that adds to them runs on)
+  if (c->d_face_maps) HIPCHK(c, zero_device(c->d_face_maps, sizeof(double) * c->face_total, c->stream));
   return 0;
 }
 
@@ -3493,6 +3613,31 @@ static int sweep_batch(PassCtx &P, Batch &B) {
   }
 }
 
+static FaceLayout face_layout(const c2r_ctx *c) {
+  FaceLayout L;
+  L.n[0] = c->g.n1; L.n[1] = c->g.n2; L.n[2] = c->g.n3;
+  for (int d = 0; d < 3; d++) L.open[d] = c->per[d] ? 0 : 1;
+  return L;
+}
+
+// The escape-map terms of a batch whose SrcDev records, final boxes included, are on their way to the device on the sweep
+// stream: one launch, a block row per face (the rows of periodic axes leave at once).
+static int queue_face_loss(const PassCtx &P, const Batch &B) {
+  c2r_ctx *c = P.c;
+  const FaceLayout L = face_layout(c);
+  int most = 0;
+  for (int d = 0; d < 3; d++)
+    if (L.open[d]) most = std::max(most, face_cells(L.n, d));
+  const dim3 grid((unsigned)((most + BLOCK - 1) / BLOCK), 6);
+  if (P.multi)
+    hipLaunchKernelGGL(k_face_loss<true>, grid, dim3(BLOCK), 0, c->stream, L, c->d_src[B.set], B.nb, P.sc, c->d_bands, P.ss, c->d_face_maps);
+  else
+    hipLaunchKernelGGL(k_face_loss<false>, grid, dim3(BLOCK), 0, c->stream, L, c->d_src[B.set], B.nb, P.sc, c->d_bands, P.ss, c->d_face_maps);
+  HIPCHK(c, hipGetLastError());
+  c->tm.sweep_launches++;
+  return 0;
+}
+
 // Final sub-boxes for the rates launch, what the next pass learns from this one (prev_nbox, prev_grow), the upload of the
 // SrcDev entries; then the rates stream takes the batch over.
 static int close_boxes(PassCtx &P, Batch &B) {
@@ -3530,11 +3675,23 @@ static int close_boxes(PassCtx &P, Batch &B) {
     T.sweep_threads = r.sweep_threads;
     c->trace_stamp[(size_t)r.ns - 1] = P.stamp;
   }
+  // Escape maps: the batch's terms, here -- the final boxes are known, the batch will not start over, and the N_in(HI)
+  // slots still hold columns (the rates launch, which waits for the event below, overwrites them where SrcDev::loss_lo
+  // asks it to).  The records go up first, and the kernel counts into the sweep's span.
+  const bool maps = c->d_face_maps != nullptr;
+  if (maps) {
+    if (c->timing && !B.sweep_started) {
+      HIPCHK(c, hipEventRecord(B.ev[0], c->stream));
+      B.sweep_started = true;
+    }
+    HIPCHK(c, hipMemcpyAsync(c->d_src[B.set], c->h_src[B.set], sizeof(SrcDev) * B.nb, hipMemcpyHostToDevice, c->stream));
+    if (queue_face_loss(P, B)) return 1;
+  }
   if (c->timing) { // the sweep's span: from the first shell launch to the last, record uploads on either side left out
     if (!B.sweep_started) HIPCHK(c, hipEventRecord(B.ev[0], c->stream));
     HIPCHK(c, hipEventRecord(B.ev[1], c->stream));
   }
-  HIPCHK(c, hipMemcpyAsync(c->d_src[B.set], c->h_src[B.set], sizeof(SrcDev) * B.nb, hipMemcpyHostToDevice, c->stream));
+  if (!maps) HIPCHK(c, hipMemcpyAsync(c->d_src[B.set], c->h_src[B.set], sizeof(SrcDev) * B.nb, hipMemcpyHostToDevice, c->stream));
   if (!P.transposed_seen) {
     // small boxes only: nobody needed the copies, but whatever follows this sweep (the global pass rewrites the
     // state) has to come after the kernel that reads it
@@ -3830,7 +3987,16 @@ static int run_planes(PassCtx &P, const std::vector<int> &planes) {
     };
     if (c->isothermal) multi ? go(k_plane_rates<false, true>) : go(k_plane_rates<false, false>);
     else multi ? go(k_plane_rates<true, true>) : go(k_plane_rates<true, false>);
-    if (multi)
+    if (c->d_face_maps) { // escape maps: the same sum with every line's term kept, at the far face
+      const FaceLayout L = face_layout(c);
+      double *map = c->d_face_maps + face_map_offset(L.n, L.open, 2 * pl.axis + (1 - pl.from_high));
+      if (multi)
+        hipLaunchKernelGGL(k_face_plane_exit<true>, dim3(fblk), dim3(BLOCK), 0, c->stream, G, P.sc, path, pd, c->d_bands, ss, c->d_plane_cin,
+                           c->d_plane_exit[p], c->d_plane_partial, map);
+      else
+        hipLaunchKernelGGL(k_face_plane_exit<false>, dim3(fblk), dim3(BLOCK), 0, c->stream, G, P.sc, path, pd, c->d_bands, ss, c->d_plane_cin,
+                           c->d_plane_exit[p], c->d_plane_partial, map);
+    } else if (multi)
       hipLaunchKernelGGL(k_plane_exit<true>, dim3(fblk), dim3(BLOCK), 0, c->stream, G, P.sc, path, pd, c->d_bands, ss, c->d_plane_cin,
                          c->d_plane_exit[p], c->d_plane_partial);
     else
@@ -4765,6 +4931,78 @@ extern "C" int c2r_get_plane_loss(c2r_ctx *c, int plane, double *loss) {
   return 0;
 }
 
+// ---------------------------------------------------------------------------------------------
+// escape maps
+static int enable_face_loss_one(c2r_ctx *c, int on) {
+  if (!c) return 1;
+  if (c->pass_open) return fail(c, "c2r_enable_face_loss: a pass opened by c2r_pass_sources_begin is still open (close it with c2r_pass_sources_end first)");
+  HIPCHK(c, hipSetDevice(c->device));
+  if (!on) {
+    if (c->d_face_maps) HIPCHK(c, hipStreamSynchronize(c->stream)); // nothing queued may still add to them
+    free_face_maps(c);
+    c->face_on = false;
+    return 0;
+  }
+  if (c->face_on) return 0;
+  if (alloc_face_maps(c)) return 1;
+  c->face_on = true;
+  return 0;
+}
+
+extern "C" int c2r_enable_face_loss(c2r_ctx *c, int on) {
+  if (int e_ = enable_face_loss_one(c, on)) return e_;
+  return for_replicas(c, [&](c2r_ctx *r) { return enable_face_loss_one(r, on); });
+}
+
+extern "C" int c2r_get_face_loss_enabled(const c2r_ctx *c) { return c && c->face_on ? 1 : 0; }
+
+// the map of one face, the devices of the context added in device order
+static int face_map_to_host(c2r_ctx *c, const char *who, int face, std::vector<double> &map) {
+  if (!c->face_on) return fail(c, "%s: the escape maps are off (c2r_enable_face_loss)", who);
+  if (face < 0 || face > 5) return fail(c, "%s: face %d, expected 0..5 (2 * axis + high)", who, face);
+  if (c->per[face >> 1]) return fail(c, "%s: face %d lies across axis %d, which is periodic: it has no map", who, face, face >> 1);
+  if (c->pass_open) return fail(c, "%s: a pass opened by c2r_pass_sources_begin is still open", who);
+  const FaceLayout L = face_layout(c);
+  const size_t n = (size_t)face_cells(L.n, face >> 1), off = (size_t)face_map_offset(L.n, L.open, face);
+  map.assign(n, 0.0);
+  std::vector<double> one(n);
+  std::vector<c2r_ctx *> dev(1, c);
+  dev.insert(dev.end(), c->replicas.begin(), c->replicas.end());
+  for (size_t k = 0; k < dev.size(); k++) {
+    c2r_ctx *d = dev[k];
+    if (!d->d_face_maps) return fail(c, "%s: internal: device %d has no maps", who, d->device);
+    HIPCHK(c, hipSetDevice(d->device));
+    HIPCHK(c, hipMemcpyAsync(k == 0 ? map.data() : one.data(), d->d_face_maps + off, sizeof(double) * n, hipMemcpyDeviceToHost, d->stream));
+    HIPCHK(c, hipStreamSynchronize(d->stream));
+    if (k > 0)
+      for (size_t i = 0; i < n; i++) map[i] = map[i] + one[i];
+  }
+  return 0;
+}
+
+extern "C" int c2r_download_face_loss(c2r_ctx *c, int face, double *map) {
+  if (!c) return 1;
+  if (!map) return fail(c, "c2r_download_face_loss: null argument");
+  std::vector<double> m;
+  if (face_map_to_host(c, "c2r_download_face_loss", face, m)) return 1;
+  std::copy(m.begin(), m.end(), map);
+  return 0;
+}
+
+extern "C" int c2r_get_face_loss(c2r_ctx *c, double out6[6]) {
+  if (!c) return 1;
+  if (!out6) return fail(c, "c2r_get_face_loss: null argument");
+  if (!c->face_on) return fail(c, "c2r_get_face_loss: the escape maps are off (c2r_enable_face_loss)");
+  std::vector<double> m;
+  for (int face = 0; face < 6; face++) {
+    out6[face] = 0.0;
+    if (c->per[face >> 1]) continue;
+    if (face_map_to_host(c, "c2r_get_face_loss", face, m)) return 1;
+    out6[face] = face_sum(m.data(), m.size());
+  }
+  return 0;
+}
+
 extern "C" int c2r_set_sed_tables(c2r_ctx *c, int sed, const double *photo_thick, const double *photo_thin, const double *heat_thick, const double *heat_thin, int lower, int upper) {
   if (int e_ = set_sed_tables_one(c, sed, photo_thick, photo_thin, heat_thick, heat_thin, lower, upper)) return e_;
   return for_replicas(c, [&](c2r_ctx *r) { return set_sed_tables_one(r, sed, photo_thick, photo_thin, heat_thick, heat_thin, lower, upper); });
@@ -4836,6 +5074,7 @@ static int set_boundaries_one(c2r_ctx *c, const int periodic[3]) {
   HIPCHK(c, hipStreamSynchronize(c->stream_probe));
   c->periodic = want;
   for (int d = 0; d < 3; d++) c->per[d] = per[d];
+  if (c->face_on && alloc_face_maps(c)) return 1; // other faces are open now: maps of the new sizes, zeroed
   shell_bookkeeping(c);
   HIPCHK(c, hipFree(c->d_block_base));
   c->d_block_base = nullptr;

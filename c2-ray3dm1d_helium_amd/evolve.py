@@ -523,6 +523,33 @@ class HipEngine:
         self._chk(self.lib.c2r_get_plane_loss(self.h, int(p), C.byref(loss)))
         return loss.value
 
+    # -- escape maps (c2r_enable_face_loss; include/c2ray_hip.h has the rule) ---------------------------------
+    def enable_face_loss(self, on=True):
+        """Keep the kept photon loss of open boxes per cell of the open mesh face it leaves through (off by default)."""
+        self._chk(self.lib.c2r_enable_face_loss(self.h, int(on)))
+
+    @property
+    def face_loss_enabled(self):
+        return bool(self.lib.c2r_get_face_loss_enabled(self.h))
+
+    def face_loss_map(self, face):
+        """The map of face 2 * axis + high (high = 0: the face at mesh index 1) since the last set_rates_to_zero, indexed
+        [b, a] by the 0-based mesh indices along the two remaining axes, a the lower one (it runs fastest).  An error for a
+        face of a periodic axis."""
+        face = int(face)
+        if not 0 <= face <= 5:
+            raise C2RayHipError(f"face {face} not in [0,5]")
+        a, b = [d for d in range(3) if d != face // 2]
+        out = np.empty((self.mesh[b], self.mesh[a]))
+        self._chk(self.lib.c2r_download_face_loss(self.h, face, _dp(out)))
+        return out
+
+    def face_loss(self):
+        """The six faces' totals, each map added up in a fixed order; 0 for a face of a periodic axis."""
+        out = np.zeros(6)
+        self._chk(self.lib.c2r_get_face_loss(self.h, _dp(out)))
+        return out
+
     def enable_timing(self, on=True):
         self._chk(self.lib.c2r_enable_timing(self.h, int(on)))
 

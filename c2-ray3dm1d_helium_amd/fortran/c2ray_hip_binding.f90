@@ -583,6 +583,33 @@ module c2ray_hip
        real(c_double), intent(out) :: loss
      end function c2r_get_plane_loss
 
+     !> escape maps (include/c2ray_hip.h): the kept photon loss per cell of the open mesh face it leaves through;
+     !> face = 2*axis + high, axis 0-based, high = 0 the face at index 1
+     integer(c_int) function c2r_enable_face_loss(ctx, on) bind(C, name="c2r_enable_face_loss")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: ctx
+       integer(c_int), value :: on
+     end function c2r_enable_face_loss
+
+     integer(c_int) function c2r_get_face_loss_enabled(ctx) bind(C, name="c2r_get_face_loss_enabled")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: ctx
+     end function c2r_get_face_loss_enabled
+
+     !> map: the face's cells in mesh order of the two remaining axes, the lower axis fastest
+     integer(c_int) function c2r_download_face_loss(ctx, face, map) bind(C, name="c2r_download_face_loss")
+       import :: c_int, c_ptr, c_double
+       type(c_ptr), value :: ctx
+       integer(c_int), value :: face
+       real(c_double), intent(out) :: map(*)
+     end function c2r_download_face_loss
+
+     integer(c_int) function c2r_get_face_loss(ctx, out6) bind(C, name="c2r_get_face_loss")
+       import :: c_int, c_ptr, c_double
+       type(c_ptr), value :: ctx
+       real(c_double), intent(out) :: out6(6)
+     end function c2r_get_face_loss
+
      integer(c_int) function c2r_enable_timing(ctx, on) bind(C, name="c2r_enable_timing")
        import :: c_int, c_ptr
        type(c_ptr), value :: ctx

@@ -349,6 +349,49 @@ int c2r_download_plane_exit_columns(c2r_ctx *ctx, int plane, double *cols3);
 /* What the plane added to photon_loss(1) in the last pass that ran it. */
 int c2r_get_plane_loss(c2r_ctx *ctx, int plane, double *loss);
 
+/* Escape maps: WHERE the photons that photon_loss(1) counts left an open box -- the kept loss per cell of the open mesh
+ * face it leaves through.  Off by default; with it off nothing is allocated, launched or waited for.
+ * Faces: face = 2*axis + high, axis 0, 1, 2; high = 0 is the face at mesh index 1, high = 1 the one at index mesh[axis].
+ * Only faces of an OPEN axis have a map: one double per face cell, the face cells in mesh order of the two remaining
+ * axes, the lower axis fastest (the layout of c2r_set_plane_entry_columns without the species index).
+ * Point sources.  For every point source s a pass sweeps and every cell q of its FINAL sub-box, with o the cell's offset
+ * from the source and m_d = srcpos_d + o_d its mesh index along an open axis d:
+ *   the cell's candidate faces are (d, low) for every open d with m_d == 1 and (d, high) for every open d with
+ *   m_d == mesh_d; a cell without candidate adds nothing;
+ *   a cell with several candidates (mesh edges and corners) gives its whole term to exactly one: the candidate whose
+ *   axis has the largest |o_d|*dr_d (compared as doubles, the product as written) -- the face the ray from the source
+ *   leaves through --, on a tie the lowest axis, within one axis (a mesh one cell deep) low before high;
+ *   the term is the one that enters the kept loss of open mode, photo_out*vol/vol_ph (vol_ph = 4 pi dist^2 path, the
+ *   cell volume for the source's own cell), 0 where N_in(HI) >= max_coldensh: the same bits the pass adds into
+ *   photon_loss(1) for that cell, from the same device functions (LLS fog, three SEDs and heating runs included).
+ *   A cell of the final box on a mesh face of an open axis always lies on the box's surface.
+ * Planes.  The per-line term of a plane (step 7 above) goes to the far face of its axis, high = 1 - from_high, at the
+ * line's face cell.
+ * Order.  Per face cell map = map + term in the order in which a pass adds to the rate grids: the planes the caller owns
+ * first, in plane order, then its point sources in source order, across batches.  No float atomics: the same bits on
+ * every run and for every c2r_set_batch.
+ * Lifetime: that of photon_loss.  c2r_set_rates_to_zero clears the maps; every pass adds to them -- c2r_pass_sources, its
+ * slab-wise form (complete after c2r_pass_sources_end), c2r_do_source, c2r_pass_allreduce_chemistry, c2r_iteration,
+ * c2r_evolve3d (after which they hold the last iteration's pass).  c2r_evolve0d does not know them.
+ * Several devices and ranks.  The maps are NOT part of the reduction buffer (c2r_rates_count and its layout are what
+ * they were).  On a multi-device context a download returns the sum of the devices' maps, added in device order.  Across
+ * processes the maps hold this rank's sources only; adding them over the ranks is the host's business.
+ * Identities.  The sum of all maps is the part of the kept loss that comes from cells on open mesh faces, so it is
+ * <= photon_loss(1) up to rounding; it equals photon_loss(1) to rounding when all axes are open and every source's final
+ * box is its whole reach; in a mixed mode the faces of a periodic axis at +-N/2 count in photon_loss(1) and in no map.
+ *
+ * c2r_enable_face_loss allocates (on != 0) or frees the maps of the open faces on every device of the context; it is
+ * refused between c2r_pass_sources_begin and c2r_pass_sources_end.  A later change of boundary mode re-sizes the maps and
+ * zeroes them. */
+int c2r_enable_face_loss(c2r_ctx *ctx, int on);
+int c2r_get_face_loss_enabled(const c2r_ctx *ctx);
+/* The map of `face`.  An error for a face of a periodic axis, for a face outside 0..5, while the feature is off, and
+ * while a slab-wise pass is open. */
+int c2r_download_face_loss(c2r_ctx *ctx, int face, double *map);
+/* out6[face]: the sum of that face's map (0 for a face of a periodic axis) in a fixed order -- every 256 consecutive face
+ * cells by a tree, then the block sums in order, the shape of the device's loss sums (face_sum, csrc/c2ray_face.hpp). */
+int c2r_get_face_loss(c2r_ctx *ctx, double out6[6]);
+
 /* ---- several GPUs: sources over ranks and the sum over ranks ----------------------------------------
  * The reference's MPI strategy (master_slave.F90:74-96 do_grid_static, evolve.F90:505-548
  * mpi_accumulate_grid_quantities): every rank holds the full grid, rank r sweeps sources r+1, r+1+npr, ...,
