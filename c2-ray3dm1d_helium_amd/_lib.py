@@ -129,6 +129,8 @@ SYMBOLS = {
     "c2r_set_plane_entry_columns": (C.c_int, [C.c_void_p, C.c_int, _dp]),
     "c2r_download_plane_exit_columns": (C.c_int, [C.c_void_p, C.c_int, _dp]),
     "c2r_get_plane_loss": (C.c_int, [C.c_void_p, C.c_int, _dp]),
+    "c2r_set_plane_tilt": (C.c_int, [C.c_void_p, C.c_int, _dp]),
+    "c2r_get_plane_tilt": (C.c_int, [C.c_void_p, C.c_int, _dp]),
     "c2r_enable_face_loss": (C.c_int, [C.c_void_p, C.c_int]),
     "c2r_get_face_loss_enabled": (C.c_int, [C.c_void_p]),
     "c2r_download_face_loss": (C.c_int, [C.c_void_p, C.c_int, _dp]),

@@ -16,6 +16,7 @@
 //   tables         k_build_tables  spec_integration: the photo-ionisation / heating tables of one SED
 //   plane sources  k_plane_columns, k_plane_rates, k_plane_exit   a plane wave entering through an open mesh face: the 1-D
 //                                  march of every line of cells along the axis, its rates, what leaves through the far face
+//                  k_plane_layer   one layer of the march of a tilted plane (c2r_set_plane_tilt), one launch per layer
 //   escape maps    k_face_loss, k_face_plane_exit   the kept loss of an open box per cell of the mesh face it leaves through
 //                                  (c2r_enable_face_loss): a gather, one lane per face cell, the sources in source order
 //
@@ -1554,7 +1555,8 @@ __global__ void __launch_bounds__(BLOCK) k_divide_by(double *__restrict__ a, siz
 // Plane-parallel sources (c2r_set_plane_sources; the per-cell rule is c2ray_plane.hpp): a plane
 // wave enters through an open face and travels along one axis, every line of cells a 1-D problem of its own.  Three
 // kernels per plane and pass, all on the sweep stream: the columns (a march, one lane per line), the rates (no
-// dependencies, one lane per cell) and what leaves through the far face.
+// dependencies, one lane per cell) and what leaves through the far face.  A tilted plane (c2r_set_plane_tilt) replaces the
+// first by one launch of k_plane_layer per layer; the other two are the same kernels with the tilted path.
 struct PlaneDev {
   double nf[NSED]; // NormFlux per cm^2 of face: black body, power law, quasar-like
 };
@@ -1588,6 +1590,40 @@ k_plane_columns(PlaneGeom G, StepScalars sc, double path, size_t nc, const doubl
   exit_cols[f] = c_HI;
   exit_cols[face + f] = c_HeI;
   exit_cols[2 * face + f] = c_HeII;
+}
+
+// One layer of the march of a tilted plane (c2r_set_plane_tilt, PlaneTilt): lane (u, v) owns face cell (u, v) of layer m
+// (travel order), interpolates its incoming columns from four cells of the layer before (`prev`: that layer's outgoing
+// columns, 3 x face, or the entry columns, or null = zero) and writes the fogged incoming columns into the cell's place of
+// cin_out and the outgoing ones into `next`.  The layers depend on each other as the shells of a point source do, and are
+// ordered the same way: one launch per layer on the sweep stream.  prev and next are different
+// buffers: every lane of the launch reads only what earlier launches wrote.
+// A block is 64 x 4 face cells, a wave one row of 64 along f: its 12 loads of prev are unit-stride (shifted by at most one
+// cell, and by whole rows), u and v come from the block and thread indices (no division), the wrap is a compare and an
+// add.  The loads of the mesh grids are unit-stride for axis 1 and 2 and n1 doubles apart for axis 0, where 16
+// consecutive layers share each 128-byte line.
+constexpr int PLANE_LAYER_BX = 64, PLANE_LAYER_BY = 4;
+__global__ void __launch_bounds__(PLANE_LAYER_BX * PLANE_LAYER_BY)
+k_plane_layer(PlaneGeom G, PlaneTilt T, StepScalars sc, int m, size_t nc, const double *__restrict__ ndens,
+              const double *__restrict__ xh_av, const double *__restrict__ xhe_av, const float *__restrict__ lls_grid,
+              const double *__restrict__ prev, double *__restrict__ cin_out, double *__restrict__ next) {
+  const int u = (int)blockIdx.x * PLANE_LAYER_BX + (int)threadIdx.x, v = (int)blockIdx.y * PLANE_LAYER_BY + (int)threadIdx.y;
+  if (u >= G.fa || v >= G.fb) return;
+  const int face = G.fa * G.fb, f = u + G.fa * v;
+  const int along = G.from_high ? G.na - 1 - m : m;
+  const size_t q = (size_t)u * G.sf + (size_t)v * G.sg + (size_t)along * G.sa;
+  double c_HI, c_HeI, c_HeII;
+  plane_layer_in(T, G.fa, G.fb, u, v, prev, c_HI, c_HeI, c_HeII);
+  const double lls = sc.use_lls ? (lls_grid ? (double)lls_grid[q] : sc.coldensh_lls) : 0.0;
+  double o_HI, o_HeI, o_HeII;
+  plane_cell_columns(ndens[q], xh_av[q], xhe_av[q], xhe_av[q + nc], T.path, sc.dr1, sc.use_lls, lls, c_HI, c_HeI, c_HeII, o_HI, o_HeI,
+                     o_HeII);
+  cin_out[3 * q] = c_HI;
+  cin_out[3 * q + 1] = c_HeI;
+  cin_out[3 * q + 2] = c_HeII;
+  next[f] = o_HI;
+  next[face + f] = o_HeI;
+  next[2 * face + f] = o_HeII;
 }
 
 // The rates of every cell from one plane, added to the rate grids: k_rates' shape -- a block is a tile of 8 x 8 x 4
@@ -1918,6 +1954,8 @@ struct c2r_ctx {
   double *d_plane_cin = nullptr;    // 3 ncell: the incoming columns of every cell, of the plane being run (planes run one after another)
   double *d_plane_entry[PLANE_MAX] = {}, *d_plane_exit[PLANE_MAX] = {}; // 3 x face each: (HI, HeI, HeII) x face cells
   bool plane_entry_set[PLANE_MAX] = {}; // entry columns were given (else zero)
+  double plane_tilt[PLANE_MAX][2] = {}; // c2r_set_plane_tilt: tangents towards the two face axes ({0, 0}: normal incidence)
+  double *d_plane_layer[2] = {};    // 3 x the largest face each: the outgoing columns of a tilted plane's layers, used alternately
   double *d_plane_partial = nullptr; // block sums of the exit loss
   double *d_plane_loss = nullptr, *h_plane_loss = nullptr; // PLANE_MAX each (h: pinned): the exit loss of the pass in flight
   double plane_loss[PLANE_MAX] = {}; // the term plane p added to photon_loss(1) in the last pass that ran it
@@ -2284,6 +2322,11 @@ static void free_plane_buffers(c2r_ctx *c) {
     if (c->d_plane_exit[p]) (void)hipFree(c->d_plane_exit[p]);
     c->d_plane_entry[p] = c->d_plane_exit[p] = nullptr;
     c->plane_entry_set[p] = false;
+    c->plane_tilt[p][0] = c->plane_tilt[p][1] = 0.0;
+  }
+  for (double *&b : c->d_plane_layer) {
+    if (b) (void)hipFree(b);
+    b = nullptr;
   }
   if (c->d_plane_cin) (void)hipFree(c->d_plane_cin);
   if (c->d_plane_partial) (void)hipFree(c->d_plane_partial);
@@ -3959,6 +4002,19 @@ static int run_planes(PassCtx &P, const std::vector<int> &planes) {
     ss.hi[k + 1] = on ? c->sed_hi[k] : 0;
   }
   const int tiles = ((g.n1 + 7) / 8) * ((g.n2 + 7) / 8) * ((g.n3 + 3) / 4);
+  // a tilted plane (c2r_set_plane_tilt): the weights and the path from the dr of this pass, the wrap from its boundaries;
+  // refused before anything is queued where dr has changed so that the beam moves more than a cell sideways per layer
+  PlaneTilt tilt_of[PLANE_MAX] = {};
+  for (int p : planes) {
+    if (!plane_tilted(c->plane_tilt[p])) continue;
+    const double dr[3] = {P.sc.dr1, P.sc.dr2, P.sc.dr3};
+    const int per[3] = {c->per[0], c->per[1], c->per[2]};
+    tilt_of[p] = PlaneTilt(c->plane_tilt[p], dr, c->planes[p].axis, per);
+    if (!tilt_of[p].valid())
+      return fail(c, "plane %d: with the cell sizes of this pass its tilt moves the beam %g and %g cells sideways per layer, more than 1 "
+                  "(c2r_set_plane_tilt)", p + 1, tilt_of[p].a_f, tilt_of[p].a_g);
+    if (!c->d_plane_layer[0] || !c->d_plane_layer[1]) return fail(c, "plane %d: tilted, but the layer buffers are missing", p + 1);
+  }
   for (int p : planes) {
     const c2r_plane_source &pl = c->planes[p];
     PlaneDev pd;
@@ -3970,16 +4026,30 @@ static int run_planes(PassCtx &P, const std::vector<int> &planes) {
         return fail(c, "plane %d: non-isothermal run needs the heating tables of SED %d", p + 1, k + 1);
     }
     const PlaneGeom G = plane_geometry(g.n1, g.n2, g.n3, pl.axis, pl.from_high);
-    const double path = pl.axis == 0 ? P.sc.dr1 : (pl.axis == 1 ? P.sc.dr2 : P.sc.dr3);
+    const bool tilted = plane_tilted(c->plane_tilt[p]);
+    const PlaneTilt &T = tilt_of[p];
+    const double path = tilted ? T.path : (pl.axis == 0 ? P.sc.dr1 : (pl.axis == 1 ? P.sc.dr2 : P.sc.dr3));
     const int face = G.fa * G.fb, fblk = (face + BLOCK - 1) / BLOCK;
     hipEvent_t ev[3] = {};
     for (hipEvent_t &e : ev)
       if (c->timing && pool_event(c, &e)) return 1;
     if (c->timing) HIPCHK(c, hipEventRecord(ev[0], c->stream));
-    hipLaunchKernelGGL(k_plane_columns, dim3(fblk), dim3(BLOCK), 0, c->stream, G, P.sc, path, g.ncell, c->d_ndens, c->d_xh_av, c->d_xhe_av,
-                       c->lls_on_grid ? c->d_lls : nullptr, c->plane_entry_set[p] ? c->d_plane_entry[p] : nullptr, c->d_plane_cin,
-                       c->d_plane_exit[p]);
-    c->tm.sweep_launches++;
+    if (tilted) { // one launch per layer, in travel order; the last layer's outgoing columns are the exit columns
+      const dim3 lgrid((unsigned)((G.fa + PLANE_LAYER_BX - 1) / PLANE_LAYER_BX), (unsigned)((G.fb + PLANE_LAYER_BY - 1) / PLANE_LAYER_BY));
+      const double *prev = c->plane_entry_set[p] ? c->d_plane_entry[p] : nullptr;
+      for (int m = 0; m < G.na; m++) {
+        double *next = m == G.na - 1 ? c->d_plane_exit[p] : c->d_plane_layer[m & 1];
+        hipLaunchKernelGGL(k_plane_layer, lgrid, dim3(PLANE_LAYER_BX, PLANE_LAYER_BY), 0, c->stream, G, T, P.sc, m, g.ncell, c->d_ndens,
+                           c->d_xh_av, c->d_xhe_av, c->lls_on_grid ? c->d_lls : nullptr, prev, c->d_plane_cin, next);
+        prev = next;
+      }
+      c->tm.sweep_launches += G.na;
+    } else {
+      hipLaunchKernelGGL(k_plane_columns, dim3(fblk), dim3(BLOCK), 0, c->stream, G, P.sc, path, g.ncell, c->d_ndens, c->d_xh_av, c->d_xhe_av,
+                         c->lls_on_grid ? c->d_lls : nullptr, c->plane_entry_set[p] ? c->d_plane_entry[p] : nullptr, c->d_plane_cin,
+                         c->d_plane_exit[p]);
+      c->tm.sweep_launches++;
+    }
     if (c->timing) HIPCHK(c, hipEventRecord(ev[1], c->stream));
     auto go = [&](auto kernel) {
       hipLaunchKernelGGL(kernel, dim3(tiles), dim3(BLOCK), 0, c->stream, g, path, pd, c->d_ndens, c->d_xh_av, c->d_xhe_av, c->d_bands, ss,
@@ -4902,6 +4972,47 @@ static int set_plane_entry_columns_one(c2r_ctx *c, int plane, const double *cols
 extern "C" int c2r_set_plane_entry_columns(c2r_ctx *c, int plane, const double *cols3) {
   if (int e_ = set_plane_entry_columns_one(c, plane, cols3)) return e_;
   return for_replicas(c, [&](c2r_ctx *r) { return set_plane_entry_columns_one(r, plane, cols3); });
+}
+
+static int set_plane_tilt_one(c2r_ctx *c, int plane, const double *tilt) {
+  if (!c) return 1;
+  if (plane < 1 || plane > c->nplane) return fail(c, "c2r_set_plane_tilt: plane %d not in [1,%d]", plane, c->nplane);
+  if (c->pass_open) return fail(c, "c2r_set_plane_tilt: a pass opened by c2r_pass_sources_begin is still open");
+  const int p = plane - 1;
+  const double t[2] = {tilt ? tilt[0] : 0.0, tilt ? tilt[1] : 0.0};
+  if (!std::isfinite(t[0]) || !std::isfinite(t[1])) return fail(c, "c2r_set_plane_tilt: plane %d: tilt (%g, %g) is not finite", plane, t[0], t[1]);
+  if (plane_tilted(t)) {
+    const double dr[3] = {c->sc.dr1, c->sc.dr2, c->sc.dr3};
+    const int per[3] = {c->per[0], c->per[1], c->per[2]};
+    if (!(dr[0] > 0.0 && dr[1] > 0.0 && dr[2] > 0.0))
+      return fail(c, "c2r_set_plane_tilt: the cell sizes are not set yet (c2r_set_step first: the tilt is checked against them)");
+    const PlaneTilt T(t, dr, c->planes[p].axis, per);
+    if (!T.valid())
+      return fail(c, "c2r_set_plane_tilt: plane %d: tilt (%g, %g) moves the beam %g and %g cells sideways per layer of axis %d; more than 1 "
+                  "makes another axis the dominant one (send the plane along that axis instead)", plane, t[0], t[1], T.a_f, T.a_g,
+                  c->planes[p].axis);
+    if (!c->d_plane_layer[0]) { // first tilted plane of this list: the two layer buffers, for the largest face of the list
+      HIPCHK(c, hipSetDevice(c->device));
+      size_t face_max = 0;
+      for (int k = 0; k < c->nplane; k++) face_max = std::max(face_max, (size_t)plane_face_cells(c, c->planes[k].axis));
+      for (double *&b : c->d_plane_layer) HIPCHK(c, hipMalloc(&b, sizeof(double) * 3 * face_max));
+    }
+  }
+  c->plane_tilt[p][0] = t[0];
+  c->plane_tilt[p][1] = t[1];
+  return 0;
+}
+
+extern "C" int c2r_set_plane_tilt(c2r_ctx *c, int plane, const double tilt[2]) {
+  if (int e_ = set_plane_tilt_one(c, plane, tilt)) return e_;
+  return for_replicas(c, [&](c2r_ctx *r) { return set_plane_tilt_one(r, plane, tilt); });
+}
+
+extern "C" int c2r_get_plane_tilt(const c2r_ctx *c, int plane, double tilt[2]) {
+  if (!c || !tilt || plane < 1 || plane > c->nplane) return 1;
+  tilt[0] = c->plane_tilt[plane - 1][0];
+  tilt[1] = c->plane_tilt[plane - 1][1];
+  return 0;
 }
 
 // the device of the context that ran plane p (0-based) last: the deal gives a plane to one device per pass

@@ -109,4 +109,68 @@ C2R_HD size_t plane_cell(const PlaneGeom &G, int f, int m) {
   return (size_t)(f % G.fa) * G.sf + (size_t)(f / G.fa) * G.sg + (size_t)along * G.sa;
 }
 
+// Oblique incidence (c2r_set_plane_tilt, include/c2ray_hip.h): the beam leans towards the two face axes f < g by the
+// tangents tilt[0], tilt[1].  The incoming column of a cell is then cinterp's weighted mean over four cells of the layer
+// before it (column_density.f90:116-163) with the weights s1..s4 of a source at infinity: the same for every cell, host
+// doubles formed once per pass from the current dr.  Everything behind N_in is the normal plane's cell with this `path`.
+struct PlaneTilt {
+  double a_f, a_g; // cells moved sideways per layer, 0 <= a <= 1
+  double s[4];     // weights of c1 (diagonal), c2 (displaced along g), c3 (displaced along f), c4 (straight behind)
+  double path;     // dr[axis] / cos(theta)
+  int e_f, e_g;    // the upstream neighbour lies at index - e
+  int wrap_f, wrap_g; // the face axis is periodic: an index outside the mesh wraps (else that corner's columns are 0)
+
+  PlaneTilt() = default;
+  C2R_HD PlaneTilt(const double tilt[2], const double dr[3], int axis, const int periodic[3]) {
+    const int f = axis == 0 ? 1 : 0, g = axis == 2 ? 1 : 2;
+    a_f = (fabs(tilt[0]) * dr[axis]) / dr[f];
+    a_g = (fabs(tilt[1]) * dr[axis]) / dr[g];
+    s[0] = a_f * a_g;
+    s[1] = (1.0 - a_f) * a_g;
+    s[2] = a_f * (1.0 - a_g);
+    s[3] = (1.0 - a_f) * (1.0 - a_g);
+    path = dr[axis] * sqrt(1.0 + (tilt[0] * tilt[0] + tilt[1] * tilt[1]));
+    e_f = tilt[0] > 0.0 ? 1 : -1;
+    e_g = tilt[1] > 0.0 ? 1 : -1;
+    wrap_f = periodic[f] != 0;
+    wrap_g = periodic[g] != 0;
+  }
+  // the axis is still the dominant one (cinterp's own case split); false for a non-finite tilt too
+  C2R_HD bool valid() const { return a_f <= 1.0 && a_g <= 1.0; }
+};
+C2R_HD bool plane_tilted(const double tilt[2]) { return tilt[0] != 0.0 || tilt[1] != 0.0; }
+
+// The upstream index u - e along a face axis of n cells, e = +-1: wrapped on a periodic axis (a compare and an add),
+// -1 where the ray came in through an open side of the mesh.
+C2R_HD int plane_upstream(int u, int e, int n, int wrap) {
+  int uu = u - e;
+  if (uu < 0) uu = wrap ? uu + n : -1;
+  else if (uu >= n) uu = wrap ? uu - n : -1;
+  return uu;
+}
+
+// cinterp's weighted mean of one species (column_density.f90:145-163, weightf :351-376) with the plane's weights; no
+// sqrt2 / sqrt3 factor (that belongs to cells adjacent to a source).  Never used when both tilts are zero: it would
+// give c * w / w instead of c.
+C2R_HD double plane_interp(const double (&s)[4], double c1, double c2, double c3, double c4, double sig) {
+  const double w1 = s[0] * weightf(c1, sig), w2 = s[1] * weightf(c2, sig), w3 = s[2] * weightf(c3, sig), w4 = s[3] * weightf(c4, sig);
+  return (c1 * w1 + c2 * w2 + c3 * w3 + c4 * w4) / (w1 + w2 + w3 + w4);
+}
+
+// N_in of the three species of face cell (u, v) from the outgoing columns of the layer before (`prev`: 3 x face, species
+// slowest, u fastest; null: all zero -- a first layer without entry columns).
+C2R_HD void plane_layer_in(const PlaneTilt &T, int fa, int fb, int u, int v, const double *prev, double &c_HI, double &c_HeI,
+                           double &c_HeII) {
+  const int uu = plane_upstream(u, T.e_f, fa, T.wrap_f), vv = plane_upstream(v, T.e_g, fb, T.wrap_g);
+  const int face = fa * fb;
+  // c1 .. c4: (u - e_f, v - e_g), (u, v - e_g), (u - e_f, v), (u, v)
+  const int at[4] = {uu >= 0 && vv >= 0 ? uu + fa * vv : -1, vv >= 0 ? u + fa * vv : -1, uu >= 0 ? uu + fa * v : -1, u + fa * v};
+  double c[3][4];
+  for (int k = 0; k < 3; k++)
+    for (int i = 0; i < 4; i++) c[k][i] = prev && at[i] >= 0 ? prev[k * face + at[i]] : 0.0;
+  c_HI = plane_interp(T.s, c[0][0], c[0][1], c[0][2], c[0][3], sigma_HI_at_ion_freq);
+  c_HeI = plane_interp(T.s, c[1][0], c[1][1], c[1][2], c[1][3], sigma_HeI_at_ion_freq);
+  c_HeII = plane_interp(T.s, c[2][0], c[2][1], c[2][2], c[2][3], sigma_HeII_at_ion_freq);
+}
+
 } // namespace c2r

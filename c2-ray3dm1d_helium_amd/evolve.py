@@ -523,6 +523,20 @@ class HipEngine:
         self._chk(self.lib.c2r_get_plane_loss(self.h, int(p), C.byref(loss)))
         return loss.value
 
+    def set_plane_tilt(self, p, tilt=None):
+        """Oblique incidence of plane p (1-based): `tilt` = the tangents of the beam's inclination towards the two face axes
+        (the lower axis first), in physical lengths.  None or (0, 0): normal incidence again.  set_plane_sources resets
+        every tilt to (0, 0)."""
+        a = None if tilt is None else (C.c_double * 2)(float(tilt[0]), float(tilt[1]))
+        self._chk(self.lib.c2r_set_plane_tilt(self.h, int(p), a))
+
+    def plane_tilt(self, p):
+        """The tilt of plane p (1-based) as set_plane_tilt took it."""
+        self._face_cells(p)
+        out = (C.c_double * 2)()
+        self._chk(self.lib.c2r_get_plane_tilt(self.h, int(p), out))
+        return (out[0], out[1])
+
     # -- escape maps (c2r_enable_face_loss; include/c2ray_hip.h has the rule) ---------------------------------
     def enable_face_loss(self, on=True):
         """Keep the kept photon loss of open boxes per cell of the open mesh face it leaves through (off by default)."""

@@ -583,6 +583,22 @@ module c2ray_hip
        real(c_double), intent(out) :: loss
      end function c2r_get_plane_loss
 
+     !> oblique incidence of plane `plane`: tilt = the tangents towards the two face axes (the lower axis first);
+     !> (0, 0) is normal incidence, as after c2r_set_plane_sources
+     integer(c_int) function c2r_set_plane_tilt(ctx, plane, tilt) bind(C, name="c2r_set_plane_tilt")
+       import :: c_int, c_ptr, c_double
+       type(c_ptr), value :: ctx
+       integer(c_int), value :: plane
+       real(c_double), intent(in) :: tilt(2)
+     end function c2r_set_plane_tilt
+
+     integer(c_int) function c2r_get_plane_tilt(ctx, plane, tilt) bind(C, name="c2r_get_plane_tilt")
+       import :: c_int, c_ptr, c_double
+       type(c_ptr), value :: ctx
+       integer(c_int), value :: plane
+       real(c_double), intent(out) :: tilt(2)
+     end function c2r_get_plane_tilt
+
      !> escape maps (include/c2ray_hip.h): the kept photon loss per cell of the open mesh face it leaves through;
      !> face = 2*axis + high, axis 0-based, high = 0 the face at index 1
      integer(c_int) function c2r_enable_face_loss(ctx, on) bind(C, name="c2r_enable_face_loss")

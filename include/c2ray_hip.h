@@ -306,8 +306,8 @@ int c2r_set_boundaries_axes(c2r_ctx *ctx, const int periodic[3]);
 int c2r_get_boundaries_axes(const c2r_ctx *ctx, int out[3]);
 
 /* Plane-parallel sources: a plane wave that enters the mesh through an OPEN face and travels along one axis -- a slab lit
- * from outside, or slabs stacked along the line of sight that hand radiation to each other.  Axis-aligned incidence, one
- * uniform flux per plane.  A plane is not a many-source approximation: every line of cells along the axis is a 1-D
+ * from outside, or slabs stacked along the line of sight that hand radiation to each other.  Axis-aligned incidence (a tilt:
+ * c2r_set_plane_tilt below), one uniform flux per plane.  A plane is not a many-source approximation: every line of cells along the axis is a 1-D
  * problem of its own, without cinterp (the incoming columns of a cell are the outgoing columns of the cell before it)
  * and without 1/r^2 dilution; everything per cell is what a point source gets (csrc/c2ray_plane.hpp).
  *   axis       0, 1 or 2: the axis the photons travel along; it must be open (c2r_set_boundaries_axes)
@@ -348,6 +348,48 @@ int c2r_set_plane_entry_columns(c2r_ctx *ctx, int plane, const double *cols3);
 int c2r_download_plane_exit_columns(c2r_ctx *ctx, int plane, double *cols3);
 /* What the plane added to photon_loss(1) in the last pass that ran it. */
 int c2r_get_plane_loss(c2r_ctx *ctx, int plane, double *loss);
+
+/* Oblique incidence: a tilt per plane, by short characteristics.  tilt[0] and tilt[1] are the tangents, in physical
+ * lengths, of the beam's inclination towards the two face axes f < g (the two axes that are not the plane's axis):
+ * travelling D along the axis in its travel direction (towards higher index for from_high = 0, towards lower index
+ * otherwise) a photon moves tilt[0]*D along +f and tilt[1]*D along +g.  c2r_set_plane_sources sets every plane's tilt to
+ * {0, 0}; tilt = NULL or {0, 0} returns plane `plane` (1-based) to normal incidence, which is the march above, unchanged
+ * and with the same bits (the interpolation below is never used then: it would give c*w/w instead of c).  The tilt
+ * applies to every device of a multi-device context.
+ * Geometry of a tilted plane, host doubles formed once per pass from the dr of that pass:
+ *   a_f = (|tilt[0]| * dr[axis]) / dr[f]       a_g = (|tilt[1]| * dr[axis]) / dr[g]     (cells moved sideways per layer)
+ *   s_1 = a_f * a_g   s_2 = (1.0 - a_f) * a_g   s_3 = a_f * (1.0 - a_g)   s_4 = (1.0 - a_f) * (1.0 - a_g)
+ *   path = dr[axis] * sqrt(1.0 + (tilt[0]*tilt[0] + tilt[1]*tilt[1]))
+ *   e_f = +1 if tilt[0] > 0 else -1, e_g likewise                              (the upstream neighbour lies at index - e)
+ * -- cinterp's weights s1..s4 (column_density.f90:116-122) for a source at infinity, where they are the same for every
+ * cell: s_4 belongs to the cell straight behind, s_3 to the one displaced along f only, s_2 to the one displaced along g
+ * only, s_1 to the diagonal one (the reference's corners c1..c4 with i -> f, j -> g).
+ * The march.  For layer m = 0 .. mesh[axis]-1 in travel order and every face cell (u, v) of it (u along f, v along g):
+ *   1. the four upstream cells c1..c4 are (u - e_f, v - e_g), (u, v - e_g), (u - e_f, v), (u, v): for m > 0 cells of
+ *      layer m - 1 with that layer's outgoing columns, for m = 0 cells of the plane's entry columns (zero when not set);
+ *   2. an index outside 1..mesh along a face axis wraps where that axis is periodic; where it is open that corner's three
+ *      columns are 0 (the ray came in through the side of the mesh, and outside is empty);
+ *   3. per species, sig = sigma_HI / HeI / HeII at the species' threshold as weightf takes them for point sources:
+ *        w_i = s_i * (1.0 / max(0.6, c_i*sig)),   N_in = (c1*w1 + c2*w2 + c3*w3 + c4*w4) / (w1 + w2 + w3 + w4),
+ *      the sums from the left; no factor sqrt2 / sqrt3 (that belongs to cells adjacent to a source);
+ *   4. from here on the normal plane's cell with this N_in, this path and vol_ph = path: the LLS fog
+ *      coldensh_LLS*path/dr(1), N_out = N_in + max(x_av, epsilon)*ndens*path*abundance, the max_coldensh guard,
+ *      photoion_rates.  A beam of normflux photons per cm^2 PERPENDICULAR TO ITSELF puts normflux*cos(theta)*A photons
+ *      into a column of volume A*dr[axis], and dr[axis]/cos(theta) = path: normflux of a tilted plane is per cm^2
+ *      perpendicular to the beam;
+ *   5. the exit columns are the outgoing columns of the last layer; the loss term of a line is photo_out*vol/path of its
+ *      last cell, added to photon_loss(1), to c2r_get_plane_loss and to the escape map of the far face at the line's face
+ *      cell exactly as for the normal plane.  What crosses an open SIDE face, in or out, is in no loss and no map; the
+ *      loss identity of the escape maps therefore holds for a tilted plane only when the tilted face axes are periodic.
+ * Two slabs stacked along the axis with the same tilt, the upstream slab's exit columns given to the downstream slab as
+ * entry columns, reproduce one mesh of the combined depth bit for bit.
+ * Refused, each with an error text: a non-finite tilt; a_f > 1 or a_g > 1 with the current dr (the axis would no longer be
+ * the dominant one, cinterp's own case split); a bad plane number; a call between c2r_pass_sources_begin and
+ * c2r_pass_sources_end.  A pass refuses a tilted plane whose a has grown beyond 1 because dr changed since the tilt was
+ * set.  c2r_set_boundaries* may change the face axes of a tilted plane at any time: the next pass takes the new wrap.
+ * The first tilted plane allocates two buffers of 3 x face doubles; every layer is one kernel launch. */
+int c2r_set_plane_tilt(c2r_ctx *ctx, int plane, const double tilt[2]);
+int c2r_get_plane_tilt(const c2r_ctx *ctx, int plane, double tilt[2]);
 
 /* Escape maps: WHERE the photons that photon_loss(1) counts left an open box -- the kept loss per cell of the open mesh
  * face it leaves through.  Off by default; with it off nothing is allocated, launched or waited for.
