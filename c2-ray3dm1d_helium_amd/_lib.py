@@ -131,6 +131,9 @@ SYMBOLS = {
     "c2r_get_plane_loss": (C.c_int, [C.c_void_p, C.c_int, _dp]),
     "c2r_set_plane_tilt": (C.c_int, [C.c_void_p, C.c_int, _dp]),
     "c2r_get_plane_tilt": (C.c_int, [C.c_void_p, C.c_int, _dp]),
+    "c2r_set_plane_flux_map": (C.c_int, [C.c_void_p, C.c_int, _dp]),
+    "c2r_get_plane_flux_map_set": (C.c_int, [C.c_void_p, C.c_int]),
+    "c2r_download_plane_exit_flux": (C.c_int, [C.c_void_p, C.c_int, _dp]),
     "c2r_enable_face_loss": (C.c_int, [C.c_void_p, C.c_int]),
     "c2r_get_face_loss_enabled": (C.c_int, [C.c_void_p]),
     "c2r_download_face_loss": (C.c_int, [C.c_void_p, C.c_int, _dp]),

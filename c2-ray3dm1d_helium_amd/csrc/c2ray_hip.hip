@@ -17,6 +17,8 @@
 //   plane sources  k_plane_columns, k_plane_rates, k_plane_exit   a plane wave entering through an open mesh face: the 1-D
 //                                  march of every line of cells along the axis, its rates, what leaves through the far face
 //                  k_plane_layer   one layer of the march of a tilted plane (c2r_set_plane_tilt), one launch per layer
+//                  k_pflux_layer, k_pflux_rates, k_pflux_exit, k_face_pflux_exit   the same for a plane whose flux is a map
+//                                  over its face (c2r_set_plane_flux_map); a plane without a map never runs them
 //   escape maps    k_face_loss, k_face_plane_exit   the kept loss of an open box per cell of the mesh face it leaves through
 //                                  (c2r_enable_face_loss): a gather, one lane per face cell, the sources in source order
 //
@@ -1603,12 +1605,13 @@ k_plane_columns(PlaneGeom G, StepScalars sc, double path, size_t nc, const doubl
 // add.  The loads of the mesh grids are unit-stride for axis 1 and 2 and n1 doubles apart for axis 0, where 16
 // consecutive layers share each 128-byte line.
 constexpr int PLANE_LAYER_BX = 64, PLANE_LAYER_BY = 4;
-__global__ void __launch_bounds__(PLANE_LAYER_BX * PLANE_LAYER_BY)
-k_plane_layer(PlaneGeom G, PlaneTilt T, StepScalars sc, int m, size_t nc, const double *__restrict__ ndens,
-              const double *__restrict__ xh_av, const double *__restrict__ xhe_av, const float *__restrict__ lls_grid,
-              const double *__restrict__ prev, double *__restrict__ cin_out, double *__restrict__ next) {
-  const int u = (int)blockIdx.x * PLANE_LAYER_BX + (int)threadIdx.x, v = (int)blockIdx.y * PLANE_LAYER_BY + (int)threadIdx.y;
-  if (u >= G.fa || v >= G.fb) return;
+// The columns of face cell (u, v) of layer m, what k_plane_layer and k_pflux_layer have in common: N_in from the layer
+// before, the fog, N_out; cin_out at the cell, `next` at the face cell.  Returns the cell.
+__device__ __forceinline__ size_t plane_layer_cell(const PlaneGeom &G, const PlaneTilt &T, const StepScalars &sc, int m, size_t nc,
+                                                   const double *__restrict__ ndens, const double *__restrict__ xh_av,
+                                                   const double *__restrict__ xhe_av, const float *__restrict__ lls_grid,
+                                                   const double *__restrict__ prev, double *__restrict__ cin_out,
+                                                   double *__restrict__ next, int u, int v) {
   const int face = G.fa * G.fb, f = u + G.fa * v;
   const int along = G.from_high ? G.na - 1 - m : m;
   const size_t q = (size_t)u * G.sf + (size_t)v * G.sg + (size_t)along * G.sa;
@@ -1624,6 +1627,16 @@ k_plane_layer(PlaneGeom G, PlaneTilt T, StepScalars sc, int m, size_t nc, const 
   next[f] = o_HI;
   next[face + f] = o_HeI;
   next[2 * face + f] = o_HeII;
+  return q;
+}
+
+__global__ void __launch_bounds__(PLANE_LAYER_BX * PLANE_LAYER_BY)
+k_plane_layer(PlaneGeom G, PlaneTilt T, StepScalars sc, int m, size_t nc, const double *__restrict__ ndens,
+              const double *__restrict__ xh_av, const double *__restrict__ xhe_av, const float *__restrict__ lls_grid,
+              const double *__restrict__ prev, double *__restrict__ cin_out, double *__restrict__ next) {
+  const int u = (int)blockIdx.x * PLANE_LAYER_BX + (int)threadIdx.x, v = (int)blockIdx.y * PLANE_LAYER_BY + (int)threadIdx.y;
+  if (u >= G.fa || v >= G.fb) return;
+  plane_layer_cell(G, T, sc, m, nc, ndens, xh_av, xhe_av, lls_grid, prev, cin_out, next, u, v);
 }
 
 // The rates of every cell from one plane, added to the rate grids: k_rates' shape -- a block is a tile of 8 x 8 x 4
@@ -1631,30 +1644,24 @@ k_plane_layer(PlaneGeom G, PlaneTilt T, StepScalars sc, int m, size_t nc, const 
 // table in LDS -- with one source whose columns come in mesh order and whose vol_ph is dr[axis].  One lane per cell and
 // not per line: the rates are some thousands of fp64 instructions per cell, and N^2 lanes would leave the device idle.
 // The outgoing columns are formed again from the incoming ones (plane_cell_out, the expression the march used).
-template <bool HEAT, bool MULTI>
-__global__ void __launch_bounds__(BLOCK, MULTI ? (HEAT ? C2R_RATES_WAVES_HEAT_MULTI : 4) : (HEAT ? C2R_RATES_WAVES_HEAT : C2R_RATES_WAVES_ISO))
-k_plane_rates(Grid g, double path, PlaneDev pl, const double *__restrict__ ndens, const double *__restrict__ xh_av,
-              const double *__restrict__ xhe_av, const BandDataByRow *__restrict__ bdr, SedSet ss, const double *__restrict__ cin,
-              double *__restrict__ rates) {
-  const size_t nc = g.ncell;
-  __shared__ gm::LogEntry s_logtab[256];
-  s_logtab[threadIdx.x] = gm::make_log_entry((int)threadIdx.x);
-  __syncthreads();
-  const BandData *const bd = bdr;
-  gm::LogPins pins_ = {0.0, 0.0};
-  const gm::LogPins *pins = nullptr;
-  if (!HEAT) {
-    pins_ = gm::pin_log_constants();
-    pins = &pins_;
-  }
+// What k_plane_rates and k_pflux_rates have in common.  The tile decode: the cell (i, j, k) of this lane, false outside the
+// mesh ...
+__device__ __forceinline__ bool plane_rates_lane(const Grid &g, int &i, int &j, int &k) {
   const int ti = (g.n1 + 7) >> 3, tj = (g.n2 + 7) >> 3;
   const int tile = (int)blockIdx.x;
   const int bi = tile % ti, bj = (tile / ti) % tj, bk = tile / (ti * tj);
   const int lane = threadIdx.x & 63;
   const int w_ = threadIdx.x >> 6;
-  const int i = bi * 8 + (w_ & 1) * 4 + (lane & 3), j = bj * 8 + (w_ >> 1) * 4 + ((lane >> 2) & 3), k = bk * 4 + (lane >> 4);
-  if (i >= g.n1 || j >= g.n2 || k >= g.n3) return;
-  const size_t q = (size_t)i + (size_t)g.n1 * ((size_t)j + (size_t)g.n2 * (size_t)k);
+  i = bi * 8 + (w_ & 1) * 4 + (lane & 3), j = bj * 8 + (w_ >> 1) * 4 + ((lane >> 2) & 3), k = bk * 4 + (lane >> 4);
+  return i < g.n1 && j < g.n2 && k < g.n3;
+}
+// ... and the rates of cell q from the flux nf, added to the rate grids.
+template <bool HEAT, bool MULTI>
+__device__ __forceinline__ void plane_rates_cell(size_t q, size_t nc, double path, const double (&nf)[NSED], const double *__restrict__ ndens,
+                                                 const double *__restrict__ xh_av, const double *__restrict__ xhe_av,
+                                                 const BandDataByRow *__restrict__ bdr, const SedSet &ss, const double *__restrict__ cin,
+                                                 double *__restrict__ rates, const gm::LogEntry *logtab, const gm::LogPins *pins) {
+  const BandData *const bd = bdr;
   double u_HI, u_HeI, u_HeII;
   plane_cell_state(ndens[q], xh_av[q], xhe_av[q], xhe_av[q + nc], u_HI, u_HeI, u_HeII);
   const double cin_HI = cin[3 * q], cin_HeI = cin[3 * q + 1], cin_HeII = cin[3 * q + 2];
@@ -1664,16 +1671,37 @@ k_plane_rates(Grid g, double path, PlaneDev pl, const double *__restrict__ ndens
   double add[4];
   bool lit;
   if constexpr (HEAT && MULTI) // cross sections and factors band by band, as k_rates' three-SED heating kernel reads them
-    lit = plane_cell_rates<HEAT, MULTI>(*bdr, ss, cin_HI, cout_HI, cin_HeI, cout_HeI, cin_HeII, cout_HeII, path, pl.nf, h_av1, u_HI, u_HeI,
-                                        u_HeII, add, &s_logtab[0], pins);
+    lit = plane_cell_rates<HEAT, MULTI>(*bdr, ss, cin_HI, cout_HI, cin_HeI, cout_HeI, cin_HeII, cout_HeII, path, nf, h_av1, u_HI, u_HeI,
+                                        u_HeII, add, logtab, pins);
   else
-    lit = plane_cell_rates<HEAT, MULTI>(*bd, ss, cin_HI, cout_HI, cin_HeI, cout_HeI, cin_HeII, cout_HeII, path, pl.nf, h_av1, u_HI, u_HeI,
-                                        u_HeII, add, &s_logtab[0], pins);
+    lit = plane_cell_rates<HEAT, MULTI>(*bd, ss, cin_HI, cout_HI, cin_HeI, cout_HeI, cin_HeII, cout_HeII, path, nf, h_av1, u_HI, u_HeI,
+                                        u_HeII, add, logtab, pins);
   if (!lit) return; // beyond max_coldensh: nothing is added
   rates[q] = rates[q] + add[0];
   rates[q + nc] = rates[q + nc] + add[1];
   rates[q + 2 * nc] = rates[q + 2 * nc] + add[2];
   if (HEAT) rates[q + 3 * nc] = rates[q + 3 * nc] + add[3];
+}
+
+template <bool HEAT, bool MULTI>
+__global__ void __launch_bounds__(BLOCK, MULTI ? (HEAT ? C2R_RATES_WAVES_HEAT_MULTI : 4) : (HEAT ? C2R_RATES_WAVES_HEAT : C2R_RATES_WAVES_ISO))
+k_plane_rates(Grid g, double path, PlaneDev pl, const double *__restrict__ ndens, const double *__restrict__ xh_av,
+              const double *__restrict__ xhe_av, const BandDataByRow *__restrict__ bdr, SedSet ss, const double *__restrict__ cin,
+              double *__restrict__ rates) {
+  const size_t nc = g.ncell;
+  __shared__ gm::LogEntry s_logtab[256];
+  s_logtab[threadIdx.x] = gm::make_log_entry((int)threadIdx.x);
+  __syncthreads();
+  gm::LogPins pins_ = {0.0, 0.0};
+  const gm::LogPins *pins = nullptr;
+  if (!HEAT) {
+    pins_ = gm::pin_log_constants();
+    pins = &pins_;
+  }
+  int i, j, k;
+  if (!plane_rates_lane(g, i, j, k)) return;
+  const size_t q = (size_t)i + (size_t)g.n1 * ((size_t)j + (size_t)g.n2 * (size_t)k);
+  plane_rates_cell<HEAT, MULTI>(q, nc, path, pl.nf, ndens, xh_av, xhe_av, bdr, ss, cin, rates, &s_logtab[0], pins);
 }
 
 // What the plane loses through the far face: lane f evaluates photo_out of the last cell of column f
@@ -1776,6 +1804,116 @@ k_face_plane_exit(PlaneGeom G, StepScalars sc, double path, PlaneDev pl, const B
     const size_t q = plane_cell(G, f, G.na - 1);
     term = plane_exit_term<MULTI>(*bd, ss, cin[3 * q], exit_cols[f], cin[3 * q + 1], exit_cols[face + f], cin[3 * q + 2],
                                   exit_cols[2 * face + f], pl.nf, sc.vol, path);
+    map[f] = map[f] + term;
+  }
+  const double bs = block_sum(term, sh);
+  if (threadIdx.x == 0) partial[blockIdx.x] = bs;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Flux maps (c2r_set_plane_flux_map; the rule is c2ray_plane.hpp): the NormFlux of a plane as a
+// field over its face.  Only a plane with a map runs the kernels below; every other plane runs the ones above, as before.
+// A plane at normal incidence keeps k_plane_columns (the columns do not know the flux) and every cell of line f reads
+// map[k][f]; a tilted plane carries the flux from layer to layer with the geometric weights (plane_layer_flux) next to
+// the columns, and the rates read the flux of their own cell.
+
+// k_plane_layer with the three fluxes carried along: 12 more loads of the layer before (`fprev`: 3 x face; the map in
+// front of the first layer), the same shifted unit-stride rows as the loads of the columns, one store of 3 doubles at the
+// cell (cell_flux, 3 per cell like cin_out) and one into the next flux layer (`fnext`; the last layer's is the exit flux).
+// All three SEDs are carried whether the plane uses them or not: the loads are issued together with those of the
+// columns, and a test per SED would save none of the latency.
+__global__ void __launch_bounds__(PLANE_LAYER_BX * PLANE_LAYER_BY)
+k_pflux_layer(PlaneGeom G, PlaneTilt T, StepScalars sc, int m, size_t nc, const double *__restrict__ ndens,
+              const double *__restrict__ xh_av, const double *__restrict__ xhe_av, const float *__restrict__ lls_grid,
+              const double *__restrict__ prev, double *__restrict__ cin_out, double *__restrict__ next,
+              const double *__restrict__ fprev, double *__restrict__ cell_flux, double *__restrict__ fnext) {
+  const int u = (int)blockIdx.x * PLANE_LAYER_BX + (int)threadIdx.x, v = (int)blockIdx.y * PLANE_LAYER_BY + (int)threadIdx.y;
+  if (u >= G.fa || v >= G.fb) return;
+  double nf[NSED];
+  plane_layer_flux(T, G.fa, G.fb, u, v, fprev, nf);
+  const size_t q = plane_layer_cell(G, T, sc, m, nc, ndens, xh_av, xhe_av, lls_grid, prev, cin_out, next, u, v);
+  const int face = G.fa * G.fb, f = u + G.fa * v;
+  for (int k = 0; k < NSED; k++) {
+    cell_flux[3 * q + k] = nf[k];
+    fnext[k * face + f] = nf[k];
+  }
+}
+
+// How a mesh cell (i, j, k) finds its face cell: f = i * fi + j * fj + k * fk, the coefficients from the plane's axis
+// (run_planes forms them) -- no division beyond the tile decode.
+struct PlaneFaceIndex {
+  int fi, fj, fk;
+};
+
+// k_plane_rates with the flux of the cell's own: PERCELL = false reads map[k][f] at the cell's face cell (normal
+// incidence), PERCELL = true the three doubles k_pflux_layer left at the cell (`flux`: 3 x face or 3 per cell).  The same
+// tile, wave shape and launch bounds.  A dark cell (plane_dark) leaves after the set-up the whole wave shares.
+template <bool HEAT, bool MULTI, bool PERCELL>
+__global__ void __launch_bounds__(BLOCK, MULTI ? (HEAT ? C2R_RATES_WAVES_HEAT_MULTI : 4) : (HEAT ? C2R_RATES_WAVES_HEAT : C2R_RATES_WAVES_ISO))
+k_pflux_rates(Grid g, double path, PlaneFaceIndex fx, int face, const double *__restrict__ flux, const double *__restrict__ ndens,
+              const double *__restrict__ xh_av, const double *__restrict__ xhe_av, const BandDataByRow *__restrict__ bdr, SedSet ss,
+              const double *__restrict__ cin, double *__restrict__ rates) {
+  const size_t nc = g.ncell;
+  __shared__ gm::LogEntry s_logtab[256];
+  s_logtab[threadIdx.x] = gm::make_log_entry((int)threadIdx.x);
+  __syncthreads();
+  gm::LogPins pins_ = {0.0, 0.0};
+  const gm::LogPins *pins = nullptr;
+  if (!HEAT) {
+    pins_ = gm::pin_log_constants();
+    pins = &pins_;
+  }
+  int i, j, k;
+  if (!plane_rates_lane(g, i, j, k)) return;
+  const size_t q = (size_t)i + (size_t)g.n1 * ((size_t)j + (size_t)g.n2 * (size_t)k);
+  double nf[NSED];
+  if (PERCELL) {
+    for (int s = 0; s < NSED; s++) nf[s] = flux[3 * q + s];
+  } else {
+    const int f = i * fx.fi + j * fx.fj + k * fx.fk;
+    for (int s = 0; s < NSED; s++) nf[s] = flux[s * face + f];
+  }
+  if (plane_dark(nf)) return;
+  plane_rates_cell<HEAT, MULTI>(q, nc, path, nf, ndens, xh_av, xhe_av, bdr, ss, cin, rates, &s_logtab[0], pins);
+}
+
+// The loss term of line f with the flux of its last cell (`flux`: 3 x face -- the map at normal incidence, the exit flux
+// of a tilted plane); 0.0 for a dark cell.
+template <bool MULTI>
+__device__ double pflux_exit_term(const PlaneGeom &G, const StepScalars &sc, double path, const BandData &bd, const SedSet &ss,
+                                  const double *__restrict__ cin, const double *__restrict__ exit_cols, const double *__restrict__ flux,
+                                  int f, int face) {
+  const double nf[NSED] = {flux[f], flux[face + f], flux[2 * face + f]};
+  if (plane_dark(nf)) return 0.0;
+  const size_t q = plane_cell(G, f, G.na - 1);
+  return plane_exit_term<MULTI>(bd, ss, cin[3 * q], exit_cols[f], cin[3 * q + 1], exit_cols[face + f], cin[3 * q + 2],
+                                exit_cols[2 * face + f], nf, sc.vol, path);
+}
+
+// k_plane_exit and k_face_plane_exit for a plane with a map: the same block sums, the same map update.
+template <bool MULTI>
+__global__ void __launch_bounds__(BLOCK)
+k_pflux_exit(PlaneGeom G, StepScalars sc, double path, const double *__restrict__ flux, const BandData *__restrict__ bd, SedSet ss,
+             const double *__restrict__ cin, const double *__restrict__ exit_cols, double *__restrict__ partial) {
+  __shared__ double sh[BLOCK / 64];
+  const int face = G.fa * G.fb;
+  const int f = (int)blockIdx.x * BLOCK + (int)threadIdx.x;
+  const double term = f < face ? pflux_exit_term<MULTI>(G, sc, path, *bd, ss, cin, exit_cols, flux, f, face) : 0.0;
+  const double bs = block_sum(term, sh);
+  if (threadIdx.x == 0) partial[blockIdx.x] = bs;
+}
+
+template <bool MULTI>
+__global__ void __launch_bounds__(BLOCK)
+k_face_pflux_exit(PlaneGeom G, StepScalars sc, double path, const double *__restrict__ flux, const BandData *__restrict__ bd, SedSet ss,
+                  const double *__restrict__ cin, const double *__restrict__ exit_cols, double *__restrict__ partial,
+                  double *__restrict__ map) {
+  __shared__ double sh[BLOCK / 64];
+  const int face = G.fa * G.fb;
+  const int f = (int)blockIdx.x * BLOCK + (int)threadIdx.x;
+  double term = 0.0;
+  if (f < face) {
+    term = pflux_exit_term<MULTI>(G, sc, path, *bd, ss, cin, exit_cols, flux, f, face);
     map[f] = map[f] + term;
   }
   const double bs = block_sum(term, sh);
@@ -1956,6 +2094,13 @@ struct c2r_ctx {
   bool plane_entry_set[PLANE_MAX] = {}; // entry columns were given (else zero)
   double plane_tilt[PLANE_MAX][2] = {}; // c2r_set_plane_tilt: tangents towards the two face axes ({0, 0}: normal incidence)
   double *d_plane_layer[2] = {};    // 3 x the largest face each: the outgoing columns of a tilted plane's layers, used alternately
+  // flux maps (c2r_set_plane_flux_map): made by the call that sets the first map of a plane, never inside a pass
+  double *d_plane_fmap[PLANE_MAX] = {}, *d_plane_fexit[PLANE_MAX] = {}; // 3 x face each: (SED 0, 1, 2) x face cells
+  bool plane_fmap_set[PLANE_MAX] = {};   // the plane has a map (it replaces normflux[])
+  bool plane_fmap_uses[PLANE_MAX][2] = {}; // some entry of SED 1 / SED 2 is non-zero (either: the three-SED routine)
+  bool plane_fexit_valid[PLANE_MAX] = {}; // the last pass that ran the plane ran it with a map: d_plane_fexit holds its exit flux
+  double *d_pflux_layer[2] = {};    // 3 x the largest face each: the flux of a tilted plane's layers, used alternately
+  double *d_pflux_cell = nullptr;   // 3 ncell: the flux of every cell of the tilted plane being run
   double *d_plane_partial = nullptr; // block sums of the exit loss
   double *d_plane_loss = nullptr, *h_plane_loss = nullptr; // PLANE_MAX each (h: pinned): the exit loss of the pass in flight
   double plane_loss[PLANE_MAX] = {}; // the term plane p added to photon_loss(1) in the last pass that ran it
@@ -2323,11 +2468,21 @@ static void free_plane_buffers(c2r_ctx *c) {
     c->d_plane_entry[p] = c->d_plane_exit[p] = nullptr;
     c->plane_entry_set[p] = false;
     c->plane_tilt[p][0] = c->plane_tilt[p][1] = 0.0;
+    if (c->d_plane_fmap[p]) (void)hipFree(c->d_plane_fmap[p]);
+    if (c->d_plane_fexit[p]) (void)hipFree(c->d_plane_fexit[p]);
+    c->d_plane_fmap[p] = c->d_plane_fexit[p] = nullptr;
+    c->plane_fmap_set[p] = c->plane_fmap_uses[p][0] = c->plane_fmap_uses[p][1] = c->plane_fexit_valid[p] = false;
   }
   for (double *&b : c->d_plane_layer) {
     if (b) (void)hipFree(b);
     b = nullptr;
   }
+  for (double *&b : c->d_pflux_layer) {
+    if (b) (void)hipFree(b);
+    b = nullptr;
+  }
+  if (c->d_pflux_cell) (void)hipFree(c->d_pflux_cell);
+  c->d_pflux_cell = nullptr;
   if (c->d_plane_cin) (void)hipFree(c->d_plane_cin);
   if (c->d_plane_partial) (void)hipFree(c->d_plane_partial);
   if (c->d_plane_loss) (void)hipFree(c->d_plane_loss);
@@ -4014,15 +4169,19 @@ static int run_planes(PassCtx &P, const std::vector<int> &planes) {
       return fail(c, "plane %d: with the cell sizes of this pass its tilt moves the beam %g and %g cells sideways per layer, more than 1 "
                   "(c2r_set_plane_tilt)", p + 1, tilt_of[p].a_f, tilt_of[p].a_g);
     if (!c->d_plane_layer[0] || !c->d_plane_layer[1]) return fail(c, "plane %d: tilted, but the layer buffers are missing", p + 1);
+    if (c->plane_fmap_set[p] && (!c->d_pflux_layer[0] || !c->d_pflux_layer[1] || !c->d_pflux_cell))
+      return fail(c, "plane %d: tilted with a flux map, but the flux buffers are missing", p + 1);
   }
   for (int p : planes) {
     const c2r_plane_source &pl = c->planes[p];
     PlaneDev pd;
     for (int s = 0; s < NSED; s++) pd.nf[s] = pl.normflux[s];
-    const bool multi = pd.nf[1] != 0.0 || pd.nf[2] != 0.0;
+    const bool mapped = c->plane_fmap_set[p]; // a flux map replaces normflux[] (c2r_set_plane_flux_map)
+    const bool uses[2] = {mapped ? c->plane_fmap_uses[p][0] : pd.nf[1] != 0.0, mapped ? c->plane_fmap_uses[p][1] : pd.nf[2] != 0.0};
+    const bool multi = uses[0] || uses[1];
     for (int k = 0; k < 2; k++) {
-      if (pd.nf[k + 1] != 0.0 && !c->have_sed[k]) return fail(c, "plane %d: flux of SED %d without c2r_set_sed_tables(%d)", p + 1, k + 1, k + 1);
-      if (pd.nf[k + 1] != 0.0 && !c->isothermal && !c->have_sed_heat[k])
+      if (uses[k] && !c->have_sed[k]) return fail(c, "plane %d: flux of SED %d without c2r_set_sed_tables(%d)", p + 1, k + 1, k + 1);
+      if (uses[k] && !c->isothermal && !c->have_sed_heat[k])
         return fail(c, "plane %d: non-isothermal run needs the heating tables of SED %d", p + 1, k + 1);
     }
     const PlaneGeom G = plane_geometry(g.n1, g.n2, g.n3, pl.axis, pl.from_high);
@@ -4034,7 +4193,23 @@ static int run_planes(PassCtx &P, const std::vector<int> &planes) {
     for (hipEvent_t &e : ev)
       if (c->timing && pool_event(c, &e)) return 1;
     if (c->timing) HIPCHK(c, hipEventRecord(ev[0], c->stream));
-    if (tilted) { // one launch per layer, in travel order; the last layer's outgoing columns are the exit columns
+    const double *exit_flux = nullptr; // 3 x face: the flux of the last cell of every line of a plane with a map
+    if (tilted && mapped) { // the layers with the flux carried along; the last layer's flux is the exit flux
+      const dim3 lgrid((unsigned)((G.fa + PLANE_LAYER_BX - 1) / PLANE_LAYER_BX), (unsigned)((G.fb + PLANE_LAYER_BY - 1) / PLANE_LAYER_BY));
+      const double *prev = c->plane_entry_set[p] ? c->d_plane_entry[p] : nullptr;
+      const double *fprev = c->d_plane_fmap[p];
+      for (int m = 0; m < G.na; m++) {
+        double *next = m == G.na - 1 ? c->d_plane_exit[p] : c->d_plane_layer[m & 1];
+        double *fnext = m == G.na - 1 ? c->d_plane_fexit[p] : c->d_pflux_layer[m & 1];
+        hipLaunchKernelGGL(k_pflux_layer, lgrid, dim3(PLANE_LAYER_BX, PLANE_LAYER_BY), 0, c->stream, G, T, P.sc, m, g.ncell, c->d_ndens,
+                           c->d_xh_av, c->d_xhe_av, c->lls_on_grid ? c->d_lls : nullptr, prev, c->d_plane_cin, next, fprev, c->d_pflux_cell,
+                           fnext);
+        prev = next;
+        fprev = fnext;
+      }
+      c->tm.sweep_launches += G.na;
+      exit_flux = c->d_plane_fexit[p];
+    } else if (tilted) { // one launch per layer, in travel order; the last layer's outgoing columns are the exit columns
       const dim3 lgrid((unsigned)((G.fa + PLANE_LAYER_BX - 1) / PLANE_LAYER_BX), (unsigned)((G.fb + PLANE_LAYER_BY - 1) / PLANE_LAYER_BY));
       const double *prev = c->plane_entry_set[p] ? c->d_plane_entry[p] : nullptr;
       for (int m = 0; m < G.na; m++) {
@@ -4049,15 +4224,49 @@ static int run_planes(PassCtx &P, const std::vector<int> &planes) {
                          c->lls_on_grid ? c->d_lls : nullptr, c->plane_entry_set[p] ? c->d_plane_entry[p] : nullptr, c->d_plane_cin,
                          c->d_plane_exit[p]);
       c->tm.sweep_launches++;
+      if (mapped) { // normal incidence: every cell of line f sees map[k][f], and so does the next slab
+        exit_flux = c->d_plane_fmap[p];
+        HIPCHK(c, hipMemcpyAsync(c->d_plane_fexit[p], c->d_plane_fmap[p], sizeof(double) * 3 * (size_t)face, hipMemcpyDeviceToDevice, c->stream));
+      }
     }
+    c->plane_fexit_valid[p] = mapped;
     if (c->timing) HIPCHK(c, hipEventRecord(ev[1], c->stream));
     auto go = [&](auto kernel) {
       hipLaunchKernelGGL(kernel, dim3(tiles), dim3(BLOCK), 0, c->stream, g, path, pd, c->d_ndens, c->d_xh_av, c->d_xhe_av, c->d_bands, ss,
                          c->d_plane_cin, c->d_rates);
     };
-    if (c->isothermal) multi ? go(k_plane_rates<false, true>) : go(k_plane_rates<false, false>);
+    auto go_map = [&](auto kernel) { // the flux of the cell's own: the map by face cell, or what the layers left per cell
+      const PlaneFaceIndex fx = {pl.axis == 0 ? 0 : 1, pl.axis == 0 ? 1 : (pl.axis == 1 ? 0 : g.n1), pl.axis == 2 ? 0 : (pl.axis == 0 ? g.n2 : g.n1)};
+      hipLaunchKernelGGL(kernel, dim3(tiles), dim3(BLOCK), 0, c->stream, g, path, fx, face, tilted ? c->d_pflux_cell : c->d_plane_fmap[p],
+                         c->d_ndens, c->d_xh_av, c->d_xhe_av, c->d_bands, ss, c->d_plane_cin, c->d_rates);
+    };
+    if (mapped) {
+      if (c->isothermal) {
+        if (tilted) multi ? go_map(k_pflux_rates<false, true, true>) : go_map(k_pflux_rates<false, false, true>);
+        else multi ? go_map(k_pflux_rates<false, true, false>) : go_map(k_pflux_rates<false, false, false>);
+      } else {
+        if (tilted) multi ? go_map(k_pflux_rates<true, true, true>) : go_map(k_pflux_rates<true, false, true>);
+        else multi ? go_map(k_pflux_rates<true, true, false>) : go_map(k_pflux_rates<true, false, false>);
+      }
+    } else if (c->isothermal) multi ? go(k_plane_rates<false, true>) : go(k_plane_rates<false, false>);
     else multi ? go(k_plane_rates<true, true>) : go(k_plane_rates<true, false>);
-    if (c->d_face_maps) { // escape maps: the same sum with every line's term kept, at the far face
+    if (mapped) {
+      if (c->d_face_maps) {
+        const FaceLayout L = face_layout(c);
+        double *map = c->d_face_maps + face_map_offset(L.n, L.open, 2 * pl.axis + (1 - pl.from_high));
+        if (multi)
+          hipLaunchKernelGGL(k_face_pflux_exit<true>, dim3(fblk), dim3(BLOCK), 0, c->stream, G, P.sc, path, exit_flux, c->d_bands, ss,
+                             c->d_plane_cin, c->d_plane_exit[p], c->d_plane_partial, map);
+        else
+          hipLaunchKernelGGL(k_face_pflux_exit<false>, dim3(fblk), dim3(BLOCK), 0, c->stream, G, P.sc, path, exit_flux, c->d_bands, ss,
+                             c->d_plane_cin, c->d_plane_exit[p], c->d_plane_partial, map);
+      } else if (multi)
+        hipLaunchKernelGGL(k_pflux_exit<true>, dim3(fblk), dim3(BLOCK), 0, c->stream, G, P.sc, path, exit_flux, c->d_bands, ss, c->d_plane_cin,
+                           c->d_plane_exit[p], c->d_plane_partial);
+      else
+        hipLaunchKernelGGL(k_pflux_exit<false>, dim3(fblk), dim3(BLOCK), 0, c->stream, G, P.sc, path, exit_flux, c->d_bands, ss, c->d_plane_cin,
+                           c->d_plane_exit[p], c->d_plane_partial);
+    } else if (c->d_face_maps) { // escape maps: the same sum with every line's term kept, at the far face
       const FaceLayout L = face_layout(c);
       double *map = c->d_face_maps + face_map_offset(L.n, L.open, 2 * pl.axis + (1 - pl.from_high));
       if (multi)
@@ -4974,6 +5183,19 @@ extern "C" int c2r_set_plane_entry_columns(c2r_ctx *c, int plane, const double *
   return for_replicas(c, [&](c2r_ctx *r) { return set_plane_entry_columns_one(r, plane, cols3); });
 }
 
+// The buffers only a tilted plane with a flux map needs -- two flux layers for the largest face of the list and the flux
+// of every cell -- made by whichever of c2r_set_plane_tilt and c2r_set_plane_flux_map completes the pair first.
+static int ensure_pflux_buffers(c2r_ctx *c) {
+  if (c->d_pflux_cell) return 0;
+  HIPCHK(c, hipSetDevice(c->device));
+  size_t face_max = 0;
+  for (int k = 0; k < c->nplane; k++) face_max = std::max(face_max, (size_t)plane_face_cells(c, c->planes[k].axis));
+  for (double *&b : c->d_pflux_layer)
+    if (!b) HIPCHK(c, hipMalloc(&b, sizeof(double) * 3 * face_max));
+  HIPCHK(c, hipMalloc(&c->d_pflux_cell, sizeof(double) * 3 * c->g.ncell));
+  return 0;
+}
+
 static int set_plane_tilt_one(c2r_ctx *c, int plane, const double *tilt) {
   if (!c) return 1;
   if (plane < 1 || plane > c->nplane) return fail(c, "c2r_set_plane_tilt: plane %d not in [1,%d]", plane, c->nplane);
@@ -4997,6 +5219,7 @@ static int set_plane_tilt_one(c2r_ctx *c, int plane, const double *tilt) {
       for (int k = 0; k < c->nplane; k++) face_max = std::max(face_max, (size_t)plane_face_cells(c, c->planes[k].axis));
       for (double *&b : c->d_plane_layer) HIPCHK(c, hipMalloc(&b, sizeof(double) * 3 * face_max));
     }
+    if (c->plane_fmap_set[p] && ensure_pflux_buffers(c)) return 1;
   }
   c->plane_tilt[p][0] = t[0];
   c->plane_tilt[p][1] = t[1];
@@ -5015,6 +5238,49 @@ extern "C" int c2r_get_plane_tilt(const c2r_ctx *c, int plane, double tilt[2]) {
   return 0;
 }
 
+static int set_plane_flux_map_one(c2r_ctx *c, int plane, const double *flux3) {
+  if (!c) return 1;
+  if (plane < 1 || plane > c->nplane) return fail(c, "c2r_set_plane_flux_map: plane %d not in [1,%d]", plane, c->nplane);
+  if (c->pass_open) return fail(c, "c2r_set_plane_flux_map: a pass opened by c2r_pass_sources_begin is still open");
+  const int p = plane - 1;
+  if (!flux3) { // the plane's uniform normflux again
+    c->plane_fmap_set[p] = c->plane_fmap_uses[p][0] = c->plane_fmap_uses[p][1] = false;
+    return 0;
+  }
+  const size_t face = (size_t)plane_face_cells(c, c->planes[p].axis);
+  bool uses[2] = {false, false};
+  for (size_t i = 0; i < 3 * face; i++) {
+    if (!(flux3[i] >= 0.0) || !std::isfinite(flux3[i]))
+      return fail(c, "c2r_set_plane_flux_map: plane %d: entry %zu of SED %d is %g (a flux is finite and not negative)", plane, i % face,
+                  (int)(i / face), flux3[i]);
+    if (i >= face && flux3[i] != 0.0) uses[i / face - 1] = true;
+  }
+  for (int k = 0; k < 2; k++)
+    if (uses[k] && !c->have_sed[k])
+      return fail(c, "c2r_set_plane_flux_map: plane %d: the map has a flux of SED %d, whose tables have not been set (c2r_set_sed_tables(%d))",
+                  plane, k + 1, k + 1);
+  HIPCHK(c, hipSetDevice(c->device));
+  if (!c->d_plane_fmap[p]) HIPCHK(c, hipMalloc(&c->d_plane_fmap[p], sizeof(double) * 3 * face));
+  if (!c->d_plane_fexit[p]) HIPCHK(c, hipMalloc(&c->d_plane_fexit[p], sizeof(double) * 3 * face));
+  if (plane_tilted(c->plane_tilt[p]) && ensure_pflux_buffers(c)) return 1;
+  c->plane_fmap_set[p] = false;
+  HIPCHK(c, hipMemcpyAsync(c->d_plane_fmap[p], flux3, sizeof(double) * 3 * face, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  c->plane_fmap_set[p] = true;
+  c->plane_fmap_uses[p][0] = uses[0];
+  c->plane_fmap_uses[p][1] = uses[1];
+  return 0;
+}
+
+extern "C" int c2r_set_plane_flux_map(c2r_ctx *c, int plane, const double *flux3) {
+  if (int e_ = set_plane_flux_map_one(c, plane, flux3)) return e_;
+  return for_replicas(c, [&](c2r_ctx *r) { return set_plane_flux_map_one(r, plane, flux3); });
+}
+
+extern "C" int c2r_get_plane_flux_map_set(const c2r_ctx *c, int plane) {
+  return c && plane >= 1 && plane <= c->nplane && c->plane_fmap_set[plane - 1] ? 1 : 0;
+}
+
 // the device of the context that ran plane p (0-based) last: the deal gives a plane to one device per pass
 static c2r_ctx *plane_owner(c2r_ctx *c, int p) {
   c2r_ctx *best = c;
@@ -5030,6 +5296,20 @@ extern "C" int c2r_download_plane_exit_columns(c2r_ctx *c, int plane, double *co
   HIPCHK(c, hipSetDevice(d->device));
   const size_t n3 = 3 * (size_t)plane_face_cells(d, d->planes[plane - 1].axis);
   HIPCHK(c, hipMemcpyAsync(cols3, d->d_plane_exit[plane - 1], sizeof(double) * n3, hipMemcpyDeviceToHost, d->stream));
+  HIPCHK(c, hipStreamSynchronize(d->stream));
+  return 0;
+}
+
+extern "C" int c2r_download_plane_exit_flux(c2r_ctx *c, int plane, double *flux3) {
+  if (!c) return 1;
+  if (plane < 1 || plane > c->nplane || !flux3) return fail(c, "c2r_download_plane_exit_flux: plane %d not in [1,%d], or null argument", plane, c->nplane);
+  if (c->pass_open) return fail(c, "c2r_download_plane_exit_flux: a pass opened by c2r_pass_sources_begin is still open");
+  c2r_ctx *d = plane_owner(c, plane - 1);
+  if (!d->plane_fexit_valid[plane - 1])
+    return fail(c, "c2r_download_plane_exit_flux: no pass has run plane %d with a flux map yet (c2r_set_plane_flux_map, then a pass)", plane);
+  HIPCHK(c, hipSetDevice(d->device));
+  const size_t n3 = 3 * (size_t)plane_face_cells(d, d->planes[plane - 1].axis);
+  HIPCHK(c, hipMemcpyAsync(flux3, d->d_plane_fexit[plane - 1], sizeof(double) * n3, hipMemcpyDeviceToHost, d->stream));
   HIPCHK(c, hipStreamSynchronize(d->stream));
   return 0;
 }

@@ -173,4 +173,26 @@ C2R_HD void plane_layer_in(const PlaneTilt &T, int fa, int fb, int u, int v, con
   c_HeII = plane_interp(T.s, c[2][0], c[2][1], c[2][2], c[2][3], sigma_HeII_at_ion_freq);
 }
 
+// Flux maps (c2r_set_plane_flux_map, include/c2ray_hip.h): the NormFlux of a plane as a field over its face, 3 x face
+// doubles, SED slowest, the face cells in the order of the entry columns.
+//
+// A dark cell -- all three fluxes == 0.0 -- adds nothing to any rate grid and its line's loss term is 0.0: it is skipped,
+// no per-cell function is evaluated.
+C2R_HD bool plane_dark(const double (&nf)[NSED]) { return nf[0] == 0.0 && nf[1] == 0.0 && nf[2] == 0.0; }
+
+// The flux of face cell (u, v) of a tilted plane's layer from the fluxes of the layer before (`fprev`: 3 x face, or the
+// map itself in front of the first layer): the corners c1 .. c4 of plane_layer_in with the geometric weights alone,
+// F = F1 s1 + F2 s2 + F3 s3 + F4 s4, every product rounded, the sums from the left.  No optical-depth factor: with it
+// the face total of a periodic face would not be conserved.  A corner outside an open side face carries flux 0.
+C2R_HD void plane_layer_flux(const PlaneTilt &T, int fa, int fb, int u, int v, const double *fprev, double (&nf)[NSED]) {
+  const int uu = plane_upstream(u, T.e_f, fa, T.wrap_f), vv = plane_upstream(v, T.e_g, fb, T.wrap_g);
+  const int face = fa * fb;
+  const int at[4] = {uu >= 0 && vv >= 0 ? uu + fa * vv : -1, vv >= 0 ? u + fa * vv : -1, uu >= 0 ? uu + fa * v : -1, u + fa * v};
+  for (int k = 0; k < NSED; k++) {
+    double F[4];
+    for (int i = 0; i < 4; i++) F[i] = at[i] >= 0 ? fprev[k * face + at[i]] : 0.0;
+    nf[k] = F[0] * T.s[0] + F[1] * T.s[1] + F[2] * T.s[2] + F[3] * T.s[3];
+  }
+}
+
 } // namespace c2r

@@ -523,6 +523,28 @@ class HipEngine:
         self._chk(self.lib.c2r_get_plane_loss(self.h, int(p), C.byref(loss)))
         return loss.value
 
+    def set_plane_flux_map(self, p, flux3=None):
+        """Flux map of plane p (1-based): 3 x face cells (black body, power law, quasar-like; the face cells in the order of
+        the entry columns), NormFlux per cm^2 at every face cell.  While set it replaces the plane's normflux.  None: the
+        uniform normflux again.  set_plane_sources drops every map."""
+        a = None
+        if flux3 is not None:
+            a = _f64(flux3).reshape(-1)
+            if a.size != 3 * self._face_cells(p):
+                raise ValueError(f"set_plane_flux_map: {a.size} values, expected 3 x {self._face_cells(p)}")
+        self._chk(self.lib.c2r_set_plane_flux_map(self.h, int(p), _dp(a)))
+
+    def plane_flux_map_set(self, p):
+        """True while plane p (1-based) has a flux map."""
+        return bool(self.lib.c2r_get_plane_flux_map_set(self.h, int(p)))
+
+    def plane_exit_flux(self, p):
+        """The flux the cells of the last layer of plane p saw in the last pass that ran it with a map (3 x face cells): the
+        flux map of the next slab downstream."""
+        out = np.empty(3 * self._face_cells(p))
+        self._chk(self.lib.c2r_download_plane_exit_flux(self.h, int(p), _dp(out)))
+        return out
+
     def set_plane_tilt(self, p, tilt=None):
         """Oblique incidence of plane p (1-based): `tilt` = the tangents of the beam's inclination towards the two face axes
         (the lower axis first), in physical lengths.  None or (0, 0): normal incidence again.  set_plane_sources resets

@@ -599,6 +599,28 @@ module c2ray_hip
        real(c_double), intent(out) :: tilt(2)
      end function c2r_get_plane_tilt
 
+     !> flux map of plane `plane`: 3 x face doubles, SED slowest, the face cells in the order of the entry columns; it
+     !> replaces the plane's normflux while set; a c_null_ptr removes it
+     integer(c_int) function c2r_set_plane_flux_map(ctx, plane, flux3) bind(C, name="c2r_set_plane_flux_map")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: ctx, flux3
+       integer(c_int), value :: plane
+     end function c2r_set_plane_flux_map
+
+     integer(c_int) function c2r_get_plane_flux_map_set(ctx, plane) bind(C, name="c2r_get_plane_flux_map_set")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: ctx
+       integer(c_int), value :: plane
+     end function c2r_get_plane_flux_map_set
+
+     !> the flux the cells of the last layer saw in the last pass that ran the plane with a map: the next slab's flux map
+     integer(c_int) function c2r_download_plane_exit_flux(ctx, plane, flux3) bind(C, name="c2r_download_plane_exit_flux")
+       import :: c_int, c_ptr, c_double
+       type(c_ptr), value :: ctx
+       integer(c_int), value :: plane
+       real(c_double), intent(out) :: flux3(*)
+     end function c2r_download_plane_exit_flux
+
      !> escape maps (include/c2ray_hip.h): the kept photon loss per cell of the open mesh face it leaves through;
      !> face = 2*axis + high, axis 0-based, high = 0 the face at index 1
      integer(c_int) function c2r_enable_face_loss(ctx, on) bind(C, name="c2r_enable_face_loss")

@@ -307,7 +307,7 @@ int c2r_get_boundaries_axes(const c2r_ctx *ctx, int out[3]);
 
 /* Plane-parallel sources: a plane wave that enters the mesh through an OPEN face and travels along one axis -- a slab lit
  * from outside, or slabs stacked along the line of sight that hand radiation to each other.  Axis-aligned incidence (a tilt:
- * c2r_set_plane_tilt below), one uniform flux per plane.  A plane is not a many-source approximation: every line of cells along the axis is a 1-D
+ * c2r_set_plane_tilt below), one uniform flux per plane (a flux per face cell: c2r_set_plane_flux_map below).  A plane is not a many-source approximation: every line of cells along the axis is a 1-D
  * problem of its own, without cinterp (the incoming columns of a cell are the outgoing columns of the cell before it)
  * and without 1/r^2 dilution; everything per cell is what a point source gets (csrc/c2ray_plane.hpp).
  *   axis       0, 1 or 2: the axis the photons travel along; it must be open (c2r_set_boundaries_axes)
@@ -390,6 +390,45 @@ int c2r_get_plane_loss(c2r_ctx *ctx, int plane, double *loss);
  * The first tilted plane allocates two buffers of 3 x face doubles; every layer is one kernel launch. */
 int c2r_set_plane_tilt(c2r_ctx *ctx, int plane, const double tilt[2]);
 int c2r_get_plane_tilt(const c2r_ctx *ctx, int plane, double tilt[2]);
+
+/* Flux maps: the flux of a plane as a field over its face instead of one number per SED -- a finite beam, a patchy
+ * background, or what the slab upstream let through.
+ * flux3: 3 x face doubles, SED slowest (black body, power law, quasar-like), the face cells in the order of
+ * c2r_set_plane_entry_columns.  While a map is set it REPLACES normflux[] of that plane: entry [k][f] is NormFlux per cm^2
+ * for SED k at face cell f -- per cm^2 of face at normal incidence, per cm^2 perpendicular to the beam for a tilted plane,
+ * as normflux is; S_star and its kin stay those of the point sources.  The map lives where the entry columns live, one
+ * layer in front of the first.  flux3 = NULL: the plane's uniform normflux again.
+ *   Normal incidence.  Every cell of line f uses nf[k] = map[k][f].  The plane takes the three-SED routine iff some entry
+ *     of SED 1 or 2 of the map is non-zero (scanned when the map is set); every cell then gets its own triple through that
+ *     routine, zeros included.
+ *   Tilted plane.  The flux travels with the beam by the geometric weights of the tilt, without the optical-depth factor
+ *     of the columns: for layer m and face cell (u, v), with the corners c1..c4 exactly as step 1 and 2 of the tilted
+ *     march pick them,
+ *        F[k] = F1[k]*s_1 + F2[k]*s_2 + F3[k]*s_3 + F4[k]*s_4,
+ *     every product rounded, the sums from the left; Fi is the flux of that corner in the layer before, for m = 0 the map
+ *     itself.  A corner outside an OPEN side face carries flux 0 (a map describes a finite beam: no flux enters through
+ *     the side of the mesh); a periodic face axis wraps, and the face total is then conserved up to rounding (exactly,
+ *     where the products are exact).  The cell (u, v) of layer m uses nf = F.
+ *   Dark cells.  A cell whose three fluxes are all == 0.0 adds nothing to any rate grid, and its line's loss term is 0.0:
+ *     it is skipped, no per-cell function is evaluated.  Everything else about a cell -- fog, columns, max_coldensh guard,
+ *     denominators, vol_ph = path, loss term photo_out*vol/path, the escape map of the far face -- is the existing plane's
+ *     cell with this nf.
+ *   The exit flux (c2r_download_plane_exit_flux) is the flux the cells of the LAST layer saw in the last pass that ran the
+ *     plane, in the map's layout: at normal incidence the map itself.  It is the flux map of the next slab downstream.
+ * Identities.  At normal incidence a map whose every entry equals normflux[k] gives the uniform plane's bits in every grid,
+ * exit column, loss and escape map.  For a tilted plane the same holds only to rounding: s_1 + s_2 + s_3 + s_4 is not
+ * exactly 1.  Two slabs stacked along the axis with the same tilt reproduce one mesh of the combined depth bit for bit
+ * when the upstream slab's exit columns AND its exit flux are handed downstream.
+ * Refused, each with an error text: a bad plane number; a negative or non-finite entry; a non-zero entry of SED 1 or 2
+ * without that SED's tables; a call between c2r_pass_sources_begin and c2r_pass_sources_end;
+ * c2r_download_plane_exit_flux before any pass ran the plane with a map.  c2r_set_plane_sources replaces the list and drops
+ * every map; c2r_set_boundaries* keep them, as they keep the tilts.  The calls act on every device of a multi-device
+ * context, and every route that runs a plane honours the map.  A plane without a map runs the kernels it ran before maps
+ * existed, with the same bits.  The first map of a plane allocates two buffers of 3 x face doubles; a plane with both a
+ * tilt and a map needs two more and 3 doubles per cell, allocated by whichever of the two calls comes second. */
+int c2r_set_plane_flux_map(c2r_ctx *ctx, int plane, const double *flux3);
+int c2r_get_plane_flux_map_set(const c2r_ctx *ctx, int plane);          /* 1 / 0 */
+int c2r_download_plane_exit_flux(c2r_ctx *ctx, int plane, double *flux3);
 
 /* Escape maps: WHERE the photons that photon_loss(1) counts left an open box -- the kept loss per cell of the open mesh
  * face it leaves through.  Off by default; with it off nothing is allocated, launched or waited for.
