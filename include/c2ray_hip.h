@@ -328,6 +328,10 @@ int c2r_get_boundaries_axes(const c2r_ctx *ctx, int out[3]);
  * per-device deal of a multi-device context, c2r_pass_allreduce_chemistry, c2r_iteration and c2r_evolve3d (whose
  * convergence criterion counts a plane as a source) give it to exactly one caller, and c2r_do_source(NumSrc + p) runs it.
  * The planes a caller owns are added before its point sources, in plane order.
+ * Several planes: any mix of plain, tilted and mapped planes may share a list, and two planes may enter through the SAME face
+ * (nothing refuses it): the rate grids and the far face's escape map receive each of them, in plane order, and every plane keeps
+ * its own exit columns, exit flux and c2r_get_plane_loss.  The planes of a pass run one after another on scratch they share,
+ * sized for the largest face of the list.  A tilt, a map and entry columns belong to the plane number they were set for.
  * c2r_set_plane_sources replaces the list (nplane = 0 removes it; at most 6) on every device of a multi-device context
  * and allocates what the planes need: 3 doubles per cell and two face buffers per plane.  It is refused for a plane
  * along a periodic axis, a bad axis, and between c2r_pass_sources_begin and c2r_pass_sources_end; c2r_set_boundaries*
@@ -346,7 +350,8 @@ int c2r_set_plane_entry_columns(c2r_ctx *ctx, int plane, const double *cols3);
 /* The outgoing columns of the last cell of every column, same layout, from the last pass that ran the plane: the entry
  * columns of the next slab downstream. */
 int c2r_download_plane_exit_columns(c2r_ctx *ctx, int plane, double *cols3);
-/* What the plane added to photon_loss(1) in the last pass that ran it. */
+/* What the plane added to photon_loss(1) in the last pass that ran it.  While no pass of this context has run the plane --
+ * before the first pass, or because the deal gives it to another caller -- the loss is 0 and the exit columns are 0. */
 int c2r_get_plane_loss(c2r_ctx *ctx, int plane, double *loss);
 
 /* Oblique incidence: a tilt per plane, by short characteristics.  tilt[0] and tilt[1] are the tangents, in physical
