@@ -604,6 +604,21 @@ C2R_HD double read_table(const double *col, const TauPos &p) {
   double a = e[0], b = e[1];
   return a + (b - a) * p.residual;
 }
+// The same two rows, fetched apart from their interpolation (the gathers-first order of band_rates), at a 32-bit BYTE
+// offset from the column base: the base is uniform over a wave, so the gather takes its scalar-base form (one 32-bit
+// shift per position, no 64-bit vector address arithmetic).  The offset stays within one column.
+struct TableRows {
+  double a, b; // rows ipos and ipos + 1
+};
+static_assert((size_t)NTAUP * sizeof(double) < ((size_t)1 << 32), "load_rows: a column is addressed by 32-bit byte offsets");
+C2R_HD TableRows load_rows(const double *col, const TauPos &p) {
+  const double *e = (const double *)((const char *)col + ((unsigned)p.ipos << 3));
+  TableRows r;
+  r.a = e[0];
+  r.b = e[1];
+  return r;
+}
+C2R_HD double interpolate_rows(const TableRows &r, const TauPos &p) { return r.a + (r.b - r.a) * p.residual; }
 
 // Heating tables as the rates kernels read them: INTERLEAVED by band.  The reference keeps one column of 0:NumTau
 // per (band, species) -- 1 + 2 x 26 + 3 x 20 = 113 columns (radiation_sizes.f90:23) -- and heat_lookuptable reads,
@@ -766,10 +781,28 @@ struct BandShared {
   TauPos pin, pout;
   double sc_HI, sc_HeI, sc_HeII;
 };
-template <bool HEAT, int CLS, class BD = BandData>
+// The photo_thick rows of one SED at both table positions of a band, requested ahead of everything that does not
+// need them (band_shared_gathers_first)
+struct BandRows {
+  TableRows in, out;
+};
+// ... and the place where they have to have arrived.  Without it the compiler sinks the second position and its
+// gather into the thick branch, behind the wait for the first gather: two waits in a row per band.  `under`: a
+// result of the arithmetic that is to run while the gathers are under way (the species split); as an operand of the
+// same statement it cannot be moved behind the wait.
+C2R_HD void band_gathers_arrive(const BandRows &R, double under) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  asm volatile("" ::"v"(R.in.a), "v"(R.in.b), "v"(R.out.a), "v"(R.out.b), "v"(under));
+#else
+  (void)R; (void)under;
+#endif
+}
+// PRE (gathers first, see band_rates): `R` holds the band's photo_thick rows, requested already; without it band_sed
+// reads them where it needs them, one wait per gather
+template <bool HEAT, int CLS, class BD = BandData, bool PRE = false>
 C2R_HD void band_sed(const BD &bd, const double *photo_thick, const double *photo_thin, const double *heat_thick,
                      const double *heat_thin, int b, const CellSrc &c, double NFlux, const BandShared &B, const Ricotti &ric,
-                     SedSums &o) {
+                     SedSums &o, const BandRows *R = nullptr) {
   const double sHI = B.sHI, sHeI = B.sHeI, sHeII = B.sHeII, dtau = B.dtau;
   const bool thick = B.thick, hthick = B.hthick;
   const TauPos pin = B.pin, pout = B.pout;
@@ -780,7 +813,21 @@ C2R_HD void band_sed(const BD &bd, const double *photo_thick, const double *phot
   {
     const double *tk = photo_thick + (size_t)b * NTAUP;
     double phi_in, phi_out, phi_all;
-    if (thick) {
+    if (PRE) {
+      band_gathers_arrive(*R, sc_HI);
+      const double t_in = interpolate_rows(R->in, pin);
+      phi_in = NFlux * t_in;
+      if (thick) {
+        const double t_out = interpolate_rows(R->out, pout);
+        phi_out = NFlux * t_out;
+        phi_all = phi_in - phi_out;
+      } else {
+        // the row at pout is not needed here: it is a valid one all the same (pout.ipos <= NumTau)
+        const double t_thin = read_table(photo_thin + (size_t)b * NTAUP, pin);
+        phi_all = NFlux * dtau * t_thin;
+        phi_out = phi_in - phi_all;
+      }
+    } else if (thick) {
       const double t_in = read_table(tk, pin), t_out = read_table(tk, pout);
       phi_in = NFlux * t_in;
       phi_out = NFlux * t_out;
@@ -919,8 +966,8 @@ C2R_HD void band_positions(const LT *logtab, const CellSrc &c, double tau_in, do
   B.dtau = dtau;
   B.thick = fabs(dtau) > tau_photo_limit;
   B.hthick = fabs(dtau) > tau_heat_limit;
-  // both positions always: an optically thin band (no use for pout) is rare, and one straight line for the
-  // two logs is worth more than skipping one of them now and then
+  // both positions always: an optically thin band (no use for pout) is rare.  The two logs are written as one straight
+  // line; compiled, the second position and its look-up sink into the thick branch of band_sed all the same
   tau_table_positions(tau_in, tau_out, logtab, B.pin, B.pout, c.pins);
   // species split of this band (scale_int2 / scale_int3)
   double sc_HI = 1.0, sc_HeI = 0.0, sc_HeII = 0.0;
@@ -940,6 +987,58 @@ C2R_HD void band_positions(const LT *logtab, const CellSrc &c, double tau_in, do
   }
   B.sc_HI = sc_HI; B.sc_HeI = sc_HeI; B.sc_HeII = sc_HeII;
 }
+// x is computed where this stands in the program, neither earlier nor later
+C2R_HD void pin_here(double &x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  asm volatile("" : "+v"(x));
+#else
+  (void)x;
+#endif
+}
+// band_positions in another order, for the kernel that can hold four table values over the species split (k_rates,
+// isothermal, one SED): the same operations on the same operands, and the band's two photo_thick gathers (R)
+// requested as soon as both positions exist, so that the split runs while they are under way and band_sed waits once.
+// What stands where decides the register count (93 for that kernel; 95-97 in any other order):
+//  - the difference first, before the logs: otherwise both depths stay in registers until the thick test wants it;
+//  - the plain division of the lanes outside recip_nr's range (rare, six temporaries wide) before the gathers are
+//    requested, recip_nr behind them;
+//  - each of the two reciprocals pinned inside its branch: once the gather no longer stands between them the compiler
+//    computes both for every lane and selects, eleven instructions more per band.
+template <int CLS, class LT>
+C2R_HD void band_positions_gathers_first(const LT *logtab, const CellSrc &c, double tau_in, double tau_out,
+                                         const double *photo_thick, int b, BandShared &B, BandRows &R) {
+  B.dtau = tau_out - tau_in;
+  pin_here(B.dtau);
+  tau_table_positions(tau_in, tau_out, logtab, B.pin, B.pout, c.pins);
+  // species split of this band (scale_int2 / scale_int3)
+  double tH = 0.0, tHe = 0.0, tHe2 = 0.0, den = 1.0, forscaleing; // set in one of the two branches below
+  if (CLS == 0) forscaleing = 1.0;
+  if (CLS >= 1) {
+    tH = B.sHI * c.cell_HI;
+    tHe = B.sHeI * c.cell_HeI;
+    den = tH + tHe;
+    if (CLS == 2) {
+      tHe2 = B.sHeII * c.cell_HeII;
+      den = den + tHe2;
+    }
+    if (!c.recip_safe) {
+      forscaleing = 1.0 / den;
+      pin_here(forscaleing);
+    }
+  }
+  const double *tk = photo_thick + (size_t)b * NTAUP;
+  R.in = load_rows(tk, B.pin);
+  R.out = load_rows(tk, B.pout);
+  if (CLS >= 1 && c.recip_safe) {
+    forscaleing = recip_nr(den);
+    pin_here(forscaleing);
+  }
+  B.thick = fabs(B.dtau) > tau_photo_limit;
+  B.hthick = fabs(B.dtau) > tau_heat_limit;
+  B.sc_HI = CLS >= 1 ? tH * forscaleing : 1.0;
+  B.sc_HeI = CLS >= 1 ? tHe * forscaleing : 0.0;
+  B.sc_HeII = CLS == 2 ? tHe2 * forscaleing : 0.0;
+}
 
 // One frequency band of photo_lookuptable (radiation_photoionrates.f90:331-464) + heat_lookuptable (:470-779) +
 // scale_int2/3 (:787-823).  CLS = 0: the band below the He I threshold (HI only), 1: bands NumBndin1+1 ..
@@ -949,7 +1048,9 @@ C2R_HD void band_positions(const LT *logtab, const CellSrc &c, double tau_in, do
 // `look_for_zero`: test whether the band is beyond the last non-zero table entry (band_tau_zero); returns
 // whether it was.  Within a class the optical depth falls from band to band, so once no lane of a wave has
 // found a band dead the caller stops asking (a missed skip costs time, never a bit).
-template <bool HEAT, int CLS, class LT, class BD = BandData>
+// GF (gathers first): band_positions_gathers_first instead of band_positions -- chosen per kernel; only the isothermal
+// one-SED k_rates asks for it (the heating and the three-SED kernels sit at 116-124 registers)
+template <bool HEAT, bool GF, int CLS, class LT, class BD = BandData>
 C2R_HD bool band_rates(const BD &bd, const double *photo_thick, const double *photo_thin, const double *heat_thick,
                        const double *heat_thin, const LT *logtab, const double *tau_zero, bool look_for_zero, int b,
                        const CellSrc &c, const Ricotti &ric, SedSums &o) {
@@ -962,8 +1063,14 @@ C2R_HD bool band_rates(const BD &bd, const double *photo_thick, const double *ph
     if (HEAT && CLS >= 1) o.df_ion_HI = o.df_ion_HeI = 0.0;
     return true;
   }
-  band_positions<CLS, LT>(logtab, c, tau_in, tau_out, B);
-  band_sed<HEAT, CLS>(bd, photo_thick, photo_thin, heat_thick, heat_thin, b, c, c.NFlux, B, ric, o);
+  if (GF) {
+    BandRows R;
+    band_positions_gathers_first<CLS, LT>(logtab, c, tau_in, tau_out, photo_thick, b, B, R);
+    band_sed<HEAT, CLS, BD, true>(bd, photo_thick, photo_thin, heat_thick, heat_thin, b, c, c.NFlux, B, ric, o, &R);
+  } else {
+    band_positions<CLS, LT>(logtab, c, tau_in, tau_out, B);
+    band_sed<HEAT, CLS>(bd, photo_thick, photo_thin, heat_thick, heat_thin, b, c, c.NFlux, B, ric, o);
+  }
   return false;
 }
 
@@ -1002,7 +1109,7 @@ struct SedAcc {
 // heat_lookuptable (:470-779), scale_int2/3 (:787-823) fused into one pass over the active bands
 // [blo, bhi) (0-based), in three stretches by band class; every sum runs in band order as in the reference.
 // HEAT selects the non-isothermal path.  `logtab`: see tau_table_position.
-template <bool HEAT, class LT, class BD = BandData>
+template <bool HEAT, bool GF, class LT, class BD = BandData>
 C2R_HD void sed_rates(const BD &bd, const double *photo_thick, const double *photo_thin,
                       const double *heat_thick, const double *heat_thin, int blo, int bhi, double cin_HI,
                       double cout_HI, double cin_HeI, double cout_HeI, double cin_HeII, double cout_HeII, double vol,
@@ -1027,19 +1134,19 @@ C2R_HD void sed_rates(const BD &bd, const double *photo_thick, const double *pho
   int b = blo;
   bool look = true;
   for (; b < e0; b++) {
-    const bool dead = band_rates<HEAT, 0, LT>(bd, photo_thick, photo_thin, heat_thick, heat_thin, logtab, tau_zero, look, b, c, ric, o);
+    const bool dead = band_rates<HEAT, GF, 0, LT>(bd, photo_thick, photo_thin, heat_thick, heat_thin, logtab, tau_zero, look, b, c, ric, o);
     C2R_COUNT_LANES(0, !dead);
     look = any_lane(dead);
   }
   look = true;
   for (; b < e1; b++) {
-    const bool dead = band_rates<HEAT, 1, LT>(bd, photo_thick, photo_thin, heat_thick, heat_thin, logtab, tau_zero, look, b, c, ric, o);
+    const bool dead = band_rates<HEAT, GF, 1, LT>(bd, photo_thick, photo_thin, heat_thick, heat_thin, logtab, tau_zero, look, b, c, ric, o);
     C2R_COUNT_LANES(0, !dead);
     look = any_lane(dead);
   }
   look = true;
   for (; b < bhi; b++) {
-    const bool dead = band_rates<HEAT, 2, LT>(bd, photo_thick, photo_thin, heat_thick, heat_thin, logtab, tau_zero, look, b, c, ric, o);
+    const bool dead = band_rates<HEAT, GF, 2, LT>(bd, photo_thick, photo_thin, heat_thick, heat_thin, logtab, tau_zero, look, b, c, ric, o);
     C2R_COUNT_LANES(0, !dead);
     look = any_lane(dead);
   }
@@ -1107,14 +1214,14 @@ C2R_HD void sed_rates_pair(const BD &bd, const double *const (&photo_thick)[2], 
 }
 
 // photoion_rates for a source with the black-body SED only
-template <bool HEAT, class LT = double, class BD = BandData>
+template <bool HEAT, class LT = double, class BD = BandData, bool GF = false>
 C2R_HD void photoion_rates(const BD &bd, const double *photo_thick, const double *photo_thin,
                            const double *heat_thick, const double *heat_thin, double cin_HI, double cout_HI,
                            double cin_HeI, double cout_HeI, double cin_HeII, double cout_HeII, double vol,
                            double NFlux, const Ricotti &ric, PhotoOut &o, const LT *logtab = C2R_LOGTAB_DEFAULT,
                            const gm::LogPins *pins = nullptr) {
   SedAcc a;
-  sed_rates<HEAT, LT>(bd, photo_thick, photo_thin, heat_thick, heat_thin, 0, bd.bb_upper, cin_HI, cout_HI, cin_HeI, cout_HeI,
+  sed_rates<HEAT, GF, LT>(bd, photo_thick, photo_thin, heat_thick, heat_thin, 0, bd.bb_upper, cin_HI, cout_HI, cin_HeI, cout_HeI,
                       cin_HeII, cout_HeII, vol, NFlux, ric, a, logtab, bd.tau_zero[0], pins);
   o.photo_HI = a.photo_HI;
   o.photo_HeI = a.photo_HeI;
@@ -1171,7 +1278,7 @@ C2R_HD void photoion_rates_multi(const BD &bd, const SedSet &ss, double cin_HI, 
     if (!act) continue;
     const double nf = s == 0 ? NFlux[0] : (s == 1 ? NFlux[1] : NFlux[2]);
     SedAcc a;
-    sed_rates<HEAT, LT>(bd, ss.photo_thick[s], ss.photo_thin[s], ss.heat_thick[s], ss.heat_thin[s], ss.lo[s], ss.hi[s], cin_HI,
+    sed_rates<HEAT, false, LT>(bd, ss.photo_thick[s], ss.photo_thin[s], ss.heat_thick[s], ss.heat_thin[s], ss.lo[s], ss.hi[s], cin_HI,
                         cout_HI, cin_HeI, cout_HeI, cin_HeII, cout_HeII, vol, nf, ric, a, logtab, bd.tau_zero[s], pins);
     o.photo_HI = o.photo_HI + a.photo_HI;
     o.photo_HeI = o.photo_HeI + a.photo_HeI;
