@@ -58,6 +58,11 @@ class PlaneSource(C.Structure):
     _fields_ = [("axis", C.c_int), ("from_high", C.c_int), ("normflux", C.c_double * 3)]
 
 
+class SourceBeam(C.Structure):
+    """c2r_source_beam (include/c2ray_hip.h)."""
+    _fields_ = [("kind", C.c_int), ("axis", C.c_double * 3), ("cos_half", C.c_double)]
+
+
 class SedSetup(C.Structure):
     """struct c2r_sed_setup (include/c2ray_hip.h)."""
     _fields_ = [("nfreq", C.c_int), ("sed", C.c_int), ("freq_min", _dp), ("delta_freq", _dp), ("xsec_index", _dp),
@@ -85,6 +90,8 @@ SYMBOLS = {
     "c2r_set_sources": (C.c_int, [C.c_void_p, C.c_int, _ip, _dp, C.c_double]),
     "c2r_set_sed_tables": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, _dp, _dp, C.c_int, C.c_int]),
     "c2r_set_sources_sed": (C.c_int, [C.c_void_p, C.c_int, _dp, C.c_double]),
+    "c2r_set_source_beams": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(SourceBeam)]),
+    "c2r_get_source_beam": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(SourceBeam)]),
     "c2r_build_tables": (C.c_int, [C.c_void_p, C.POINTER(SedSetup), C.c_int]),
     "c2r_download_tables": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, _dp, _dp]),
     "c2r_set_lls": (C.c_int, [C.c_void_p, C.c_int, C.c_double, _fp]),

@@ -41,6 +41,7 @@
 
 #include "../../include/c2ray_hip.h"
 #include "c2ray_device.hpp"
+#include "c2ray_beam.hpp"
 #include "c2ray_face.hpp"
 #include "c2ray_plane.hpp"
 #include "c2ray_shell.hpp"
@@ -77,7 +78,17 @@ struct SrcDev {
                        // all-periodic kernels never read them
   int wn[3];           // likewise: the wrap extent of each axis (axis_wrap_extent: the mesh extent if the axis is periodic
                        // while another is open, 0 if it is open)
+  int beam;            // the source's beam (c2r_set_source_beams; c2ray_beam.hpp): BEAM_NONE, BEAM_CONE or BEAM_BICONE ...
+  double bax, bay, baz; // ... its axis as given ...
+  double bK;           // ... and beam_K, cos^2 of the half opening angle times the axis's squared length (0 without a beam)
 };
+// Is the cell at offset (di, dj, dk) lit by source S?  Uniform branch on S.beam (a scalar register: the record is read through
+// the scalar cache), so a source without a beam costs a wave one scalar compare; the loss and per-cell kernels ask this
+// beside their in-box test.  (k_rates never asks: batches with a beamed source run k_rates_beam.)
+__device__ __forceinline__ bool source_lights(const SrcDev &S, double dr1, double dr2, double dr3, int di, int dj, int dk) {
+  if (S.beam == BEAM_NONE) return true;
+  return beam_lit(S.beam, S.bax, S.bay, S.baz, S.bK, dr1, dr2, dr3, di, dj, dk);
+}
 // the sub-box of the round in flight: the same for every active source of a batch (all are in the same round)
 struct Box {
   int lo[3], hi[3];
@@ -283,7 +294,8 @@ k_loss(Grid g, const SrcDev *__restrict__ src, const int *__restrict__ list, int
     const bool inside = di >= box.lo[0] && di <= box.hi[0] && dj >= box.lo[1] && dj <= box.hi[1] && dk >= box.lo[2] &&
                         dk <= box.hi[2];
     const bool boundary = on_counted_face<OPEN>(box, S, di, dj, dk, MOVABLE ? 1 : 0);
-    if (inside && boundary) {
+    // (an unlit cell of a beamed source loses nothing: its term is 0.0, as beyond max_coldensh)
+    if (inside && boundary && source_lights(S, sc.dr1, sc.dr2, sc.dr3, di, dj, dk)) {
       const size_t cz = S.cz;
       const size_t p = (OPEN ? (size_t)RS.off : (size_t)shell_offset(shell)) + (size_t)t;
       const global_double *cs = (const global_double *)S.cols;
@@ -653,7 +665,8 @@ k_loss_probe_rounds(Grid g, const SrcDev *__restrict__ src, const int *__restric
     const bool inside = di >= box.lo[0] && di <= box.hi[0] && dj >= box.lo[1] && dj <= box.hi[1] && dk >= box.lo[2] &&
                         dk <= box.hi[2];
     const bool boundary = on_counted_face<OPEN>(box, S, di, dj, dk, 1);
-    if (inside && boundary) {
+    // (unlit cells of a beamed source are left out: terms are only ever left out, so this stays a lower bound)
+    if (inside && boundary && source_lights(S, sc.dr1, sc.dr2, sc.dr3, di, dj, dk)) {
       const size_t cz = S.cz;
       const size_t p = (OPEN ? (size_t)RS.off : (size_t)shell_offset(shell)) + (size_t)t;
       const global_double *cs = (const global_double *)S.cols;
@@ -744,215 +757,29 @@ k_col_to_grid(Grid g, SrcDev S, const double *__restrict__ cs, double *__restric
 // the image within the mesh's reach along a periodic one (axis_offset); the final sub-box and the surface
 // test come from S.lo / S.hi as they always did.  Instantiations of their own: the periodic kernels have no issue slot
 // to spare and stay the code they were.
+// BEAM (beamed point sources, c2ray_beam.hpp): batches that hold at least one beamed source run k_rates_beam, a kernel of its
+// own name with the same arguments, launch shape and source order; batches without one launch the k_rates they always
+// launched.  The two share their text (c2ray_rates_body.inc).
+#define C2R_RATES_BOUNDS __launch_bounds__(BLOCK, MULTI ? (HEAT ? C2R_RATES_WAVES_HEAT_MULTI : 4) : (HEAT ? C2R_RATES_WAVES_HEAT : C2R_RATES_WAVES_ISO))
 template <bool HEAT, bool MULTI, bool OPEN = false>
-__global__ void __launch_bounds__(BLOCK, MULTI ? (HEAT ? C2R_RATES_WAVES_HEAT_MULTI : 4) : (HEAT ? C2R_RATES_WAVES_HEAT : C2R_RATES_WAVES_ISO))
+__global__ void C2R_RATES_BOUNDS
 k_rates(Grid g, const SrcDev *__restrict__ src, int nsrc, StepScalars sc, const double *__restrict__ ndens,
         const double *__restrict__ xh_av, const double *__restrict__ xhe_av,
         const BandDataByRow *__restrict__ bdr, SedSet ss, double *__restrict__ rates, const int *__restrict__ tiles,
         const int *__restrict__ tile_ptr, const int *__restrict__ tile_src, int tile_base, int fresh) {
-  const size_t nc = g.ncell;
-  // One block = a tile of 8 x 8 x 4 cells, one wave = a 4 x 4 x 4 cube of it.  Neighbouring cells see
-  // similar optical depths: the lanes of a cube mostly take the same branch of the bit-exact log (its
-  // near-1 path is 10 % of all arguments, so a wave of 64 unrelated cells nearly always runs both) and
-  // gather from few table lines -- 31.2 -> 26.9 ms per launch at 256^3 x 8 sources against 64
-  // consecutive i.  With sub-boxes much smaller than the mesh a cube also keeps ~(w/(w+3))^3 of its lanes
-  // busy for a box of width w instead of w/(w+63).  Loads are 16 segments of 32 B; the kernel is ALU-bound.
-  // `tiles`, when given, lists the tiles that intersect a sub-box of the batch (built on the host): the
-  // launch then holds only blocks with work, which keeps enough heavy waves resident per SIMD.  With it come
-  // `tile_ptr` / `tile_src`: for each listed tile the sources (positions in `src`, ascending = source order)
-  // whose sub-box reaches into it, so that a batch of hundreds of faint sources costs a cell only the sources
-  // near it.  Without lists every cell walks all nsrc sources of the batch (few sources, boxes that fill the mesh).
-  // the (invc, logc) table of the bit-exact log in LDS, with the log's power of two folded in (gm::LogEntry, 8 KB): two
-  // gathers per band iteration that no longer queue behind the photo-table gathers in the vector memory path
-  __shared__ gm::LogEntry s_logtab[256];
-  s_logtab[threadIdx.x] = gm::make_log_entry((int)threadIdx.x);
-  __syncthreads();
-  // the band data as uploaded (a BandDataByRow: the plain arrays and, behind them, the same numbers band by band); a kernel
-  // chooses its reading of them by the TYPE it hands down -- the base for the array form (an upcast, not a reinterpretation)
-  const BandData *const bd = bdr;
-  // two polynomial constants of the log held in vector registers for the whole kernel (gm::LogPins): -0.25 ms per
-  // launch in the isothermal kernel; the heating kernels, which have no registers to spare, lose 2.7 ms with them
-  gm::LogPins pins_ = {0.0, 0.0};
-  const gm::LogPins *pins = nullptr;
-  if (!HEAT) {
-    pins_ = gm::pin_log_constants();
-    pins = &pins_;
-  }
-  const int ti = (g.n1 + 7) >> 3, tj = (g.n2 + 7) >> 3;
-  // Workgroups are dealt to the 8 XCDs round-robin, and each XCD has its own L2.  A cube reads its columns as 32-byte
-  // rows of shell faces, so the other half of every cache line belongs to the neighbouring cube: give each XCD a
-  // contiguous run of C = 128 tiles (a slab of the mesh), so that the neighbour's request finds the line in the same L2.
-  int vb = (int)blockIdx.x;
-  {
-    constexpr int C = 128;
-    const int full = (int)(gridDim.x / (8 * C)) * (8 * C);
-    if (vb < full) {
-      const int r = vb >> 3, xcd = vb & 7;
-      vb = (r / C) * (8 * C) + xcd * C + (r % C);
-    }
-  }
-  const int tile = tiles ? tiles[tile_base + vb] : tile_base + vb;
-  const int bi = tile % ti, bj = (tile / ti) % tj, bk = tile / (ti * tj);
-  const int lane = threadIdx.x & 63;
-  const int w_ = threadIdx.x >> 6;
-  const int i = bi * 8 + (w_ & 1) * 4 + (lane & 3), j = bj * 8 + (w_ >> 1) * 4 + ((lane >> 2) & 3), k = bk * 4 + (lane >> 4);
-  if (i >= g.n1 || j >= g.n2 || k >= g.n3) return;
-  // The cell's own quantities are needed once per source, after its band loops: only what those divisions use stays
-  // in registers across the loops -- the three denominators h0 * nd * (1 - abu_he), ... (evaluated from the left, as
-  // evolve_point.F90:288-296 does per source), not the four factors, and not the cell number, which is formed again
-  // for the stores at the end.
-  double den_HI, den_HeI, den_HeII, h1;
-  double a_HI = 0.0, a_HeI = 0.0, a_HeII = 0.0, a_heat = 0.0;
-  {
-    const size_t q = (size_t)i + (size_t)g.n1 * ((size_t)j + (size_t)g.n2 * (size_t)k);
-    const double nd = ndens[q];
-    const double h0 = dmax(xh_av[q], epsilon);
-    h1 = dmax(xh_av[q + nc], epsilon);
-    const double he0 = dmax(xhe_av[q], epsilon), he1 = dmax(xhe_av[q + nc], epsilon);
-    den_HI = h0 * nd * (1.0 - abu_he);
-    den_HeI = he0 * nd * abu_he;
-    den_HeII = he1 * nd * abu_he;
-    // fresh: the first launch after set_rates_to_zero when the launch covers every cell -- the grids then need not
-    // be zeroed first (4 x 8 bytes per cell written and read again: 1.3 ms per iteration at 256^3); 0 + x == x
-    if (!fresh) {
-      a_HI = rates[q];
-      a_HeI = rates[q + nc];
-      a_HeII = rates[q + 2 * nc];
-      if (HEAT) a_heat = rates[q + 3 * nc];
-    }
-  }
-  // secondary-ionisation parameters of this cell, i_state = h_av(1) (evolve_point.F90:255): once per cell,
-  // not once per source
-  Ricotti ric = {};
-  if (HEAT) ric = ricotti_parameters(h1);
-  // The three-SED heating kernel parks the cell's denominators and running sums, which the band loops do not touch, in
-  // LDS, one column per lane, where the register allocation would otherwise spill them to scratch memory: it then fits
-  // four waves per SIMD without a private segment.  (Parking the secondary-ionisation parameters as well costs more
-  // than their registers: six LDS reads per heating band, 369 against 357 ms per pass on one box.)
-  constexpr bool PARK = HEAT && MULTI;
-  // the three denominators of the cell and its four running sums, touched once per source: [den_HI, den_HeI, den_HeII,
-  // a_HI, a_HeI, a_HeII, a_heat] x BLOCK (each lane reads back only what it wrote itself: no barrier)
-  __shared__ double s_den[PARK ? 7 * BLOCK : 1];
-  if (PARK) {
-    s_den[threadIdx.x] = den_HI;
-    s_den[BLOCK + threadIdx.x] = den_HeI;
-    s_den[2 * BLOCK + threadIdx.x] = den_HeII;
-    s_den[3 * BLOCK + threadIdx.x] = a_HI;
-    s_den[4 * BLOCK + threadIdx.x] = a_HeI;
-    s_den[5 * BLOCK + threadIdx.x] = a_HeII;
-    s_den[6 * BLOCK + threadIdx.x] = a_heat;
-  }
-  bool touched = false;
-  const int slot = tile_base + vb;
-  const int e0 = tile_ptr ? tile_ptr[slot] : 0, e1 = tile_ptr ? tile_ptr[slot + 1] : nsrc;
-  for (int e = e0; e < e1; e++) {
-    const SrcDev &S = src[tile_ptr ? tile_src[e] : e];
-    // unwrapped offset rtpos - srcpos in [-mesh/2, mesh - mesh/2 - 1]
-    int di = i + 1 - S.i0, dj = j + 1 - S.j0, dk = k + 1 - S.k0;
-    if constexpr (!OPEN) {
-      di = wrap0(di + g.l1, g.n1) - g.l1;
-      dj = wrap0(dj + g.l2, g.n2) - g.l2;
-      dk = wrap0(dk + g.l3, g.n3) - g.l3;
-    } else { // per axis: wrapped where the axis is periodic (S.wn is uniform over the block), as it is where it is open
-      di = axis_offset(i, S.i0, S.wn[0]);
-      dj = axis_offset(j, S.j0, S.wn[1]);
-      dk = axis_offset(k, S.k0, S.wn[2]);
-    }
-    // Cells outside the source's last sub-box were never traced (evolve_source.F90:136-144): no
-    // contribution.  (The reference's own marker is coldensh_out == 0, evolve_point.F90:120; every cell
-    // of the box is traced exactly once, so "inside the box" is the same set and needs no zeroing.)
-    const bool outside = di < S.lo[0] || di > S.hi[0] || dj < S.lo[1] || dj > S.hi[1] || dk < S.lo[2] || dk > S.hi[2];
-    C2R_COUNT_LANES(3, !outside);
-    if (outside) continue;
-    touched = true;
-    const size_t cz = S.cz;
-    const size_t p = OPEN ? reach_position(S.rl, S.rr, di, dj, dk) : shell_position(di, dj, dk);
-    global_double *cs = (global_double *)S.cols;
-    const double cout_HI = cs[col_out(p, 0, cz)];
-    const double cin_HI = cs[col_in(p, 0, cz)], cin_HeI = cs[col_in(p, 1, cz)], cin_HeII = cs[col_in(p, 2, cz)];
-    const double cout_HeI = cs[col_out(p, 1, cz)], cout_HeII = cs[col_out(p, 2, cz)];
-    double vol_ph;
-    if (di == 0 && dj == 0 && dk == 0) {
-      vol_ph = sc.cellvol;
-    } else {
-      const double path = sc_path(di, dj, dk) * sc.dr1;
-      const double xs = sc.dr1 * (double)di, ys = sc.dr2 * (double)dj, zs = sc.dr3 * (double)dk;
-      const double dist2 = xs * xs + ys * ys + zs * zs;
-      vol_ph = 4.0 * pi * dist2 * path;
-    }
-    // photoion_rates and the sums of this cell; with_loss: also return photo_out, which the kernel otherwise never
-    // forms (one addition per band, registers that stay alive through the band loop, scalar registers short
-    // enough already: 4 % of the launch when every wave pays it) -- two copies of the code, chosen per wave below
-    auto rates_of_source = [&](auto with_loss) -> double {
-      double photo_out = 0.0;
-      if (cin_HI < max_coldensh) {
-        PhotoOut o;
-        if (MULTI) {
-          const double nf[NSED] = {S.nflux, S.nflux_sed[0], S.nflux_sed[1]};
-          if constexpr (HEAT) // this kernel reads cross sections and factors band by band (BandDataByRow)
-            photoion_rates_multi<HEAT>(*bdr, ss, cin_HI, cout_HI, cin_HeI, cout_HeI, cin_HeII, cout_HeII,
-                                       vol_ph, nf, ric, o, &s_logtab[0], pins);
-          else
-            photoion_rates_multi<HEAT>(*bd, ss, cin_HI, cout_HI, cin_HeI, cout_HeI, cin_HeII, cout_HeII, vol_ph, nf, ric, o, &s_logtab[0], pins);
-        } else {
-          // gathers first (band_positions_gathers_first) where the registers allow it: the isothermal kernel
-          photoion_rates<HEAT, gm::LogEntry, BandData, !HEAT>(*bd, ss.photo_thick[0], ss.photo_thin[0], ss.heat_thick[0], ss.heat_thin[0], cin_HI, cout_HI,
-                                                                   cin_HeI, cout_HeI, cin_HeII, cout_HeII, vol_ph, S.nflux, ric, o, &s_logtab[0], pins);
-        }
-        if (PARK) { // (volatile: read here, not hoisted back into registers)
-          volatile __attribute__((address_space(3))) double *dn = (volatile __attribute__((address_space(3))) double *)&s_den[threadIdx.x];
-          dn[3 * BLOCK] = dn[3 * BLOCK] + o.photo_HI / dn[0];
-          dn[4 * BLOCK] = dn[4 * BLOCK] + o.photo_HeI / dn[BLOCK];
-          dn[5 * BLOCK] = dn[5 * BLOCK] + o.photo_HeII / dn[2 * BLOCK];
-          dn[6 * BLOCK] = dn[6 * BLOCK] + o.heat;
-        } else {
-          a_HI = a_HI + o.photo_HI / den_HI;
-          a_HeI = a_HeI + o.photo_HeI / den_HeI;
-          a_HeII = a_HeII + o.photo_HeII / den_HeII;
-          if (HEAT) a_heat = a_heat + o.heat;
-        }
-        if (decltype(with_loss)::value) photo_out = o.photo_out;
-      } else {
-        // rates are zero: x + 0.0 == x
-      }
-      return photo_out;
-    };
-    // evolve_point.F90:310-315: a cell on the surface of the (final) sub-box loses photo_out * vol / vol_ph photons
-    // through it.  For a source whose last round ended for geometric reasons (SrcDev::loss_lo >= 0) that loss is
-    // the one that is kept: leave it in the cell's N_in(HI) slot, which nobody reads any more, for k_loss_stored.
-    // Only the shells of the final round count; the others were done -- and counted, for a loss that is not kept
-    // -- in earlier rounds.
-    // (Isothermal kernels only: the heating kernels, three times the code and short of registers as they are, lose
-    // 10 % of their launch to the second copy -- 34.0 against 31.2 ms -- where the isothermal one gains; heating runs
-    // evaluate the kept loss with k_loss beside the rates launch, as rounds 1 and 2 did.)
-    bool surface = false;
-    if (!HEAT && S.loss_lo >= 0) { // uniform
-      const int ia = di < 0 ? -di : di, ja = dj < 0 ? -dj : dj, ka = dk < 0 ? -dk : dk;
-      const int shell = ia > ja ? (ia > ka ? ia : ka) : (ja > ka ? ja : ka);
-      surface = (di == S.lo[0] || dj == S.lo[1] || dk == S.lo[2] || di == S.hi[0] || dj == S.hi[1] || dk == S.hi[2]) &&
-                shell >= S.loss_lo;
-    }
-    if (!HEAT && __any(surface ? 1 : 0)) {
-      const double photo_out = rates_of_source(std::true_type{});
-      if (surface) cs[col_in(p, 0, cz)] = photo_out * sc.vol / vol_ph;
-    } else {
-      (void)rates_of_source(std::false_type{});
-    }
-  }
-  if (touched || fresh) {
-    const size_t q = (size_t)i + (size_t)g.n1 * ((size_t)j + (size_t)g.n2 * (size_t)k);
-    if (PARK) {
-      a_HI = s_den[3 * BLOCK + threadIdx.x];
-      a_HeI = s_den[4 * BLOCK + threadIdx.x];
-      a_HeII = s_den[5 * BLOCK + threadIdx.x];
-      a_heat = s_den[6 * BLOCK + threadIdx.x];
-    }
-    rates[q] = a_HI;
-    rates[q + nc] = a_HeI;
-    rates[q + 2 * nc] = a_HeII;
-    if (HEAT) rates[q + 3 * nc] = a_heat;
-  }
+  constexpr bool BEAM = false;
+#include "c2ray_rates_body.inc"
 }
+template <bool HEAT, bool MULTI, bool OPEN = false>
+__global__ void C2R_RATES_BOUNDS
+k_rates_beam(Grid g, const SrcDev *__restrict__ src, int nsrc, StepScalars sc, const double *__restrict__ ndens,
+             const double *__restrict__ xh_av, const double *__restrict__ xhe_av,
+             const BandDataByRow *__restrict__ bdr, SedSet ss, double *__restrict__ rates, const int *__restrict__ tiles,
+             const int *__restrict__ tile_ptr, const int *__restrict__ tile_src, int tile_base, int fresh) {
+  constexpr bool BEAM = true;
+#include "c2ray_rates_body.inc"
+}
+#undef C2R_RATES_BOUNDS
 
 // ---------------------------------------------------------------------------------------------
 // evolve0D_global + do_chemistry (files_for_3D/evolve_point.F90:325-440, :444-646), one cell per lane.
@@ -1439,7 +1266,8 @@ k_evolve0d(SweepArgs A, SrcDev S, int di, int dj, int dk, const BandData *__rest
     vol_ph = 4.0 * pi * dist2 * path;
   }
   double photo_out = 0.0;
-  if (cin_HI < max_coldensh) {
+  // (the columns above are the cell's whatever the beam: an unlit cell adds no rates and loses nothing)
+  if (cin_HI < max_coldensh && source_lights(S, A.sc.dr1, A.sc.dr2, A.sc.dr3, di, dj, dk)) {
     Ricotti ric = {};
     if (HEAT) ric = ricotti_parameters(h1);
     PhotoOut o;
@@ -1762,6 +1590,7 @@ k_face_loss(FaceLayout L, const SrcDev *__restrict__ src, int nsrc, StepScalars 
     const bool outside = o[0] < S.lo[0] || o[0] > S.hi[0] || o[1] < S.lo[1] || o[1] > S.hi[1] || o[2] < S.lo[2] || o[2] > S.hi[2];
     if (outside) continue;
     if (face_of_cell(L.n, L.open, m, o, dr) != face) continue;
+    if (!source_lights(S, sc.dr1, sc.dr2, sc.dr3, o[0], o[1], o[2])) continue; // the term of an unlit cell is 0.0: acc + 0.0 == acc
     const size_t cz = S.cz;
     const size_t p = reach_position(S.rl, S.rr, o[0], o[1], o[2]);
     const global_double *cs = (const global_double *)S.cols;
@@ -1982,6 +1811,9 @@ struct c2r_ctx {
   bool have_sed[2] = {false, false}, have_sed_heat[2] = {false, false}, have_sed_limits[2] = {false, false};
   std::vector<double> normflux_sed[2];
   double s_star_sed[2] = {0, 0};
+  // c2r_set_source_beams: one record per source as it was given, and beam_K of each (empty: no source is beamed)
+  std::vector<c2r_source_beam> beams;
+  std::vector<double> beam_k;
 
   double *d_xh = nullptr, *d_xhe = nullptr, *d_xh_av = nullptr, *d_xhe_av = nullptr, *d_xh_int = nullptr,
          *d_xhe_int = nullptr;
@@ -2798,6 +2630,8 @@ static int set_sources_one(c2r_ctx *c, int nsrc, const int *srcpos, const double
   c->s_star = s_star;
   c->normflux_sed[0].clear();
   c->normflux_sed[1].clear();
+  c->beams.clear();
+  c->beam_k.clear();
   return 0;
 }
 
@@ -2838,6 +2672,49 @@ static int set_sources_sed_one(c2r_ctx *c, int sed, const double *normflux, doub
   c->normflux_sed[k].assign(normflux, normflux + c->nsrc);
   c->s_star_sed[k] = s_star;
   return 0;
+}
+
+// c2r_set_source_beams on one device: everything is checked before anything is kept
+static int set_source_beams_one(c2r_ctx *c, int nsrc, const c2r_source_beam *beams) {
+  if (!c) return 1;
+  if (c->pass_open) return fail(c, "c2r_set_source_beams: a pass opened by c2r_pass_sources_begin is still open");
+  if (nsrc != c->nsrc) return fail(c, "c2r_set_source_beams: nsrc = %d, but c2r_set_sources gave %d sources", nsrc, c->nsrc);
+  if (!beams) {
+    c->beams.clear();
+    c->beam_k.clear();
+    return 0;
+  }
+  std::vector<double> k((size_t)nsrc, 0.0);
+  for (int s = 0; s < nsrc; s++) {
+    const c2r_source_beam &b = beams[s];
+    if (b.kind < BEAM_NONE || b.kind > BEAM_BICONE)
+      return fail(c, "c2r_set_source_beams: source %d: kind = %d, expected 0 (none), 1 (cone) or 2 (bicone)", s + 1, b.kind);
+    if (b.kind == BEAM_NONE) continue;
+    if (!std::isfinite(b.axis[0]) || !std::isfinite(b.axis[1]) || !std::isfinite(b.axis[2]))
+      return fail(c, "c2r_set_source_beams: source %d: axis (%g, %g, %g) is not finite", s + 1, b.axis[0], b.axis[1], b.axis[2]);
+    const double a2 = (b.axis[0] * b.axis[0] + b.axis[1] * b.axis[1]) + b.axis[2] * b.axis[2];
+    if (!std::isnormal(a2))
+      return fail(c, "c2r_set_source_beams: source %d: the squared length %g of axis (%g, %g, %g) is zero or not a normal finite number",
+                  s + 1, a2, b.axis[0], b.axis[1], b.axis[2]);
+    if (!std::isfinite(b.cos_half) || b.cos_half < 0.0 || b.cos_half > 1.0)
+      return fail(c, "c2r_set_source_beams: source %d: cos_half = %g is not in [0, 1]", s + 1, b.cos_half);
+    k[(size_t)s] = beam_K(b.cos_half, b.axis[0], b.axis[1], b.axis[2]);
+  }
+  c->beams.assign(beams, beams + nsrc);
+  c->beam_k.swap(k);
+  return 0;
+}
+
+// the beam of source ns (1-based) in its device record
+static void source_beam(const c2r_ctx *c, int ns, SrcDev &S) {
+  S.beam = BEAM_NONE;
+  S.bax = S.bay = S.baz = S.bK = 0.0;
+  if (c->beams.empty()) return;
+  const c2r_source_beam &b = c->beams[(size_t)ns - 1];
+  if (b.kind == BEAM_NONE) return;
+  S.beam = b.kind;
+  S.bax = b.axis[0]; S.bay = b.axis[1]; S.baz = b.axis[2];
+  S.bK = c->beam_k[(size_t)ns - 1];
 }
 
 // The per-frequency vectors of k_build_tables, with the host versions of the bit-exact exp / pow:
@@ -3369,6 +3246,7 @@ struct Batch {
   size_t settled = 0, launched = 0; // recs[0, settled): while-test applied; recs[settled, launched): probes in flight
   bool sweep_started = false;       // ev[0] goes in front of the first shell launch, behind the uploads of records and lists
   int ntiles = 0;                   // tiles in the rates launch's list h_tiles[set] (0: none, every tile of the mesh)
+  bool beamed = false;              // some source of the batch has a beam: its rates launch is k_rates_beam
 };
 
 // Queue the probes of the batch's rounds recs[launched ..) (lower bounds of their boundary losses, k_loss_probe_rounds) on
@@ -3490,6 +3368,7 @@ static int place_batch(const PassCtx &P, const std::vector<int> &mine, Batch &B)
   const int set = B.set;
   SrcDev *hs = c->h_src[set];
   B.run.assign((size_t)B.nb, SrcRun());
+  B.beamed = false;
   for (bool released = false;;) {
     c->seg_cur[set] = 0;
     c->seg_used[set] = 0;
@@ -3553,6 +3432,8 @@ static int place_batch(const PassCtx &P, const std::vector<int> &mine, Batch &B)
     source_wrap(c, S.wn);
     S.nflux = c->normflux[r.ns - 1];
     for (int k = 0; k < 2; k++) S.nflux_sed[k] = c->normflux_sed[k].empty() ? 0.0 : c->normflux_sed[k][r.ns - 1];
+    source_beam(c, r.ns, S);
+    B.beamed = B.beamed || S.beam != BEAM_NONE;
   }
   // coldensh_out = 0 for every new source (evolve_source.F90:94-95) serves two purposes in the
   // reference: the "already done" marker (replaced here by the shell order: every cell is visited
@@ -4037,7 +3918,15 @@ static int launch_rates(const PassCtx &P, Batch &B, bool last_batch) {
                          c->d_bands, P.ss, c->d_rates, lists ? c->d_tiles[B.set] : nullptr, lists ? c->d_tptr[B.set] : nullptr,
                          lists ? c->d_tsrc[B.set] : nullptr, base, fresh);
     };
-    if (cnt > 0 && c->periodic) {
+    if (cnt > 0 && B.beamed) { // some source of the batch has a beam: the kernel that asks (c2r_set_source_beams)
+      if (c->periodic) {
+        if (c->isothermal) P.multi ? go(k_rates_beam<false, true>) : go(k_rates_beam<false, false>);
+        else P.multi ? go(k_rates_beam<true, true>) : go(k_rates_beam<true, false>);
+      } else {
+        if (c->isothermal) P.multi ? go(k_rates_beam<false, true, true>) : go(k_rates_beam<false, false, true>);
+        else P.multi ? go(k_rates_beam<true, true, true>) : go(k_rates_beam<true, false, true>);
+      }
+    } else if (cnt > 0 && c->periodic) {
       if (c->isothermal) P.multi ? go(k_rates<false, true>) : go(k_rates<false, false>);
       else P.multi ? go(k_rates<true, true>) : go(k_rates<true, false>);
     } else if (cnt > 0) {
@@ -4650,6 +4539,7 @@ extern "C" int c2r_evolve0d(c2r_ctx *c, const int rtpos[3], int ns, int niter, i
   S.loss_lo = -1;
   for (int d = 0; d < 3; d++) { S.rl[d] = R.l[d]; S.rr[d] = R.r[d]; }
   source_wrap(c, S.wn);
+  source_beam(c, ns, S);
   double *dl = on_surface ? c->d_point_loss : nullptr;
   if (!c->isothermal) c->phiheat_dirty = true;
 #define C2R_LAUNCH_POINT(H, M) \
@@ -5403,6 +5293,18 @@ extern "C" int c2r_set_sed_tables(c2r_ctx *c, int sed, const double *photo_thick
 extern "C" int c2r_set_sources_sed(c2r_ctx *c, int sed, const double *normflux, double s_star) {
   if (int e_ = set_sources_sed_one(c, sed, normflux, s_star)) return e_;
   return for_replicas(c, [&](c2r_ctx *r) { return set_sources_sed_one(r, sed, normflux, s_star); });
+}
+
+extern "C" int c2r_set_source_beams(c2r_ctx *c, int nsrc, const c2r_source_beam *beams) {
+  if (int e_ = set_source_beams_one(c, nsrc, beams)) return e_;
+  return for_replicas(c, [&](c2r_ctx *r) { return set_source_beams_one(r, nsrc, beams); });
+}
+
+extern "C" int c2r_get_source_beam(const c2r_ctx *c, int ns, c2r_source_beam *out) {
+  if (!c || !out || ns < 1 || ns > c->nsrc) return 1;
+  if (c->beams.empty()) *out = c2r_source_beam{};
+  else *out = c->beams[(size_t)ns - 1];
+  return 0;
 }
 
 extern "C" int c2r_build_tables(c2r_ctx *c, const c2r_sed_setup *S, int with_heat) {

@@ -369,6 +369,31 @@ class HipEngine:
                 assert f.size == nf.size
                 self._chk(self.lib.c2r_set_sources_sed(self.h, idx, _dp(f), float(star)))
 
+    def set_source_beams(self, beams=None):
+        """c2r_set_source_beams: one beam per point source, in source order -- None (no beam), a dict or a tuple
+        (kind, axis, cos_half) with kind 0 / "none", 1 / "cone" or 2 / "bicone", axis three numbers (any length), cos_half the
+        cosine of the half opening angle.  beams=None: no source is beamed.  set_sources clears the beams."""
+        if beams is None:
+            self._chk(self.lib.c2r_set_source_beams(self.h, int(self.nsrc), None))
+            return
+        kinds = {"none": 0, "cone": 1, "bicone": 2}
+        beams = list(beams)
+        arr = (_lib.SourceBeam * max(len(beams), 1))()
+        for rec, b in zip(arr, beams):
+            if b is None:
+                continue
+            kind, axis, cos_half = (b["kind"], b["axis"], b["cos_half"]) if isinstance(b, dict) else b
+            rec.kind = kinds[kind] if isinstance(kind, str) else int(kind)
+            rec.axis[:] = [float(a) for a in axis]
+            rec.cos_half = float(cos_half)
+        self._chk(self.lib.c2r_set_source_beams(self.h, len(beams), arr))
+
+    def source_beam(self, ns):
+        """c2r_get_source_beam for source `ns` (1-based) as a dict: kind (0 none, 1 cone, 2 bicone), axis, cos_half."""
+        b = _lib.SourceBeam()
+        self._chk(self.lib.c2r_get_source_beam(self.h, int(ns), C.byref(b)))
+        return {"kind": int(b.kind), "axis": [float(a) for a in b.axis], "cos_half": float(b.cos_half)}
+
     def upload_state(self, mat: Material):
         xh, xhe = _f64(mat.xh).reshape(-1), _f64(mat.xhe).reshape(-1)
         assert xh.size == 2 * self.ncell and xhe.size == 3 * self.ncell

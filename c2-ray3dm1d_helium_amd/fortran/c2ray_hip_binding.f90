@@ -62,6 +62,13 @@ module c2ray_hip
      real(c_double) :: normflux(3)
   end type c2r_plane_source
 
+  !> c2r_source_beam of include/c2ray_hip.h: the emission cone (kind 1) or bicone (kind 2) of one point source; kind 0: none
+  type, bind(C) :: c2r_source_beam
+     integer(c_int) :: kind
+     real(c_double) :: axis(3)
+     real(c_double) :: cos_half
+  end type c2r_source_beam
+
   !> c2r_sed_setup of include/c2ray_hip.h: what spec_integration starts from for one SED
   type, bind(C) :: c2r_sed_setup
      integer(c_int) :: nfreq, sed
@@ -177,6 +184,22 @@ module c2ray_hip
        real(c_double), intent(in) :: normflux(*)
        real(c_double), value :: s_star
      end function c2r_set_sources_sed
+
+     !> beams: c_loc of NumSrc records of type(c2r_source_beam), or c_null_ptr: no source is beamed
+     integer(c_int) function c2r_set_source_beams(ctx, nsrc, beams) bind(C, name="c2r_set_source_beams")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: ctx
+       integer(c_int), value :: nsrc
+       type(c_ptr), value :: beams
+     end function c2r_set_source_beams
+
+     !> the beam of source ns (1-based) as it was set
+     integer(c_int) function c2r_get_source_beam(ctx, ns, beam) bind(C, name="c2r_get_source_beam")
+       import :: c_int, c_ptr, c2r_source_beam
+       type(c_ptr), value :: ctx
+       integer(c_int), value :: ns
+       type(c2r_source_beam), intent(out) :: beam
+     end function c2r_get_source_beam
 
      integer(c_int) function c2r_build_tables(ctx, setup, with_heat) bind(C, name="c2r_build_tables")
        import :: c_int, c_ptr, c2r_sed_setup

@@ -124,6 +124,54 @@ int c2r_set_sed_tables(c2r_ctx *ctx, int sed, const double *photo_thick, const d
                        const double *heat_thick, const double *heat_thin, int lower, int upper);
 int c2r_set_sources_sed(c2r_ctx *ctx, int sed, const double *normflux, double s_star);
 
+/* Beamed point sources: an emission cone or bicone per source -- a quasar that lights a cone, not a sphere.  The reference
+ * has nothing of the kind; a source at infinity gets its direction from c2r_set_plane_tilt, a source inside the box here.
+ *   kind      0 none (the source radiates isotropically, as every source of the reference), 1 cone, 2 bicone
+ *   axis      the beam's axis in the physical directions x, y, z; it need not be normalised
+ *   cos_half  the cosine of the half opening angle, 0 <= cos_half <= 1
+ * The rule (csrc/c2ray_beam.hpp).  When the beams are set the host forms one double per source,
+ *     K = (cos_half*cos_half) * ((a_x*a_x + a_y*a_y) + a_z*a_z).
+ * For a cell at offset (di, dj, dk) from the source -- the offset exactly as the kernel in question already forms it: the
+ * image within the reach on a periodic axis, the plain difference on an open one -- and the dr of the pass, every product
+ * and sum rounded as written and evaluated from the left:
+ *     xs = dr1*(double)di    ys = dr2*(double)dj    zs = dr3*(double)dk
+ *     dot = (xs*a_x + ys*a_y) + zs*a_z
+ *     d2  = (xs*xs + ys*ys) + zs*zs
+ *     cone:    lit  iff  dot >= 0.0  &&  dot*dot >= K*d2
+ *     bicone:  lit  iff  dot*dot >= K*d2
+ * No square root and no division: a cell exactly on the cone is lit, and so is the source's own cell (0 >= 0).
+ * An UNLIT cell behaves, for that source only, exactly like a cell with N_in(HI) >= max_coldensh: it adds nothing to phih,
+ * phihe or phiheat, and its loss term photo_out*vol/vol_ph is 0.0 in the loss that decides whether the sub-box grows, in the
+ * loss that is kept, in photon_loss(1) and in the escape maps.  A LIT cell gets the bits it gets without a beam.
+ * What a beam does not do.  NormFlux stays the isotropic-equivalent flux: nothing is rescaled to conserve photons.  The
+ * threshold 1e-10 * total_source_flux of the sub-box loop is unchanged (a beam can only end the loop earlier).  Columns are
+ * swept as before, over the whole box, lit or not; sum_nbox counts rounds as before.  Planes are untouched.
+ * Identities.
+ *   Beams off: with no beams set, or every kind == 0, every grid, loss, map and sum_nbox has the bits it had before beams
+ *     existed, from the same kernel launches.
+ *   Full bicone: a bicone with cos_half = 0 lights every cell; the results are the unbeamed bits, through the beamed kernels.
+ *   One beamed source, from zeroed grids: every rate grid equals the unbeamed source's grid where the cell is lit and +0.0
+ *     elsewhere, provided both runs trace the same rounds.
+ *   Several sources: grid = grid + where(lit_s, term_s, 0.0), folded in source order.
+ * c2r_set_source_beams gives all NumSrc sources their beams at once (nsrc must equal the NumSrc of c2r_set_sources); beams =
+ * NULL: no source is beamed.  c2r_set_sources clears the beams, as it clears the extra SEDs; c2r_set_boundaries* keep them.
+ * The beams act on every device of a multi-device context, and every route that traces a point source honours them:
+ * c2r_pass_sources and its slab-wise form, c2r_do_source, c2r_pass_allreduce_chemistry, c2r_iteration, c2r_evolve3d,
+ * c2r_evolve0d (the loss of an unlit surface cell is 0.0) and the escape maps.
+ * Refused, each with an error text: a call between c2r_pass_sources_begin and c2r_pass_sources_end; nsrc != NumSrc; a kind
+ * outside 0..2; a non-finite axis component; an axis whose squared length is zero or not a normal finite double; a cos_half
+ * outside [0, 1] or not finite.  (axis and cos_half of a source with kind == 0 mean nothing and are not looked at: a
+ * zeroed record is "no beam".)  A refused call changes nothing.
+ * c2r_get_source_beam returns the beam of source ns (1-based) as it was set; kind 0, axis {0, 0, 0}, cos_half 0 while none
+ * is set. */
+typedef struct {
+  int kind;
+  double axis[3];
+  double cos_half;
+} c2r_source_beam;
+int c2r_set_source_beams(c2r_ctx *ctx, int nsrc, const c2r_source_beam *beams);
+int c2r_get_source_beam(const c2r_ctx *ctx, int ns, c2r_source_beam *out);
+
 /* material:xh, xhe, temperature_grid (temperature may be NULL when isothermal) */
 int c2r_upload_state(c2r_ctx *ctx, const double *xh, const double *xhe, const float *temperature);
 int c2r_download_state(c2r_ctx *ctx, double *xh, double *xhe, float *temperature);
