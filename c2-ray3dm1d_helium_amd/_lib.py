@@ -92,6 +92,8 @@ SYMBOLS = {
     "c2r_set_sources_sed": (C.c_int, [C.c_void_p, C.c_int, _dp, C.c_double]),
     "c2r_set_source_beams": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(SourceBeam)]),
     "c2r_get_source_beam": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(SourceBeam)]),
+    "c2r_set_source_horizons": (C.c_int, [C.c_void_p, C.c_int, _dp]),
+    "c2r_get_source_horizon": (C.c_int, [C.c_void_p, C.c_int, _dp]),
     "c2r_build_tables": (C.c_int, [C.c_void_p, C.POINTER(SedSetup), C.c_int]),
     "c2r_download_tables": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, _dp, _dp]),
     "c2r_set_lls": (C.c_int, [C.c_void_p, C.c_int, C.c_double, _fp]),

@@ -42,6 +42,7 @@
 #include "../../include/c2ray_hip.h"
 #include "c2ray_device.hpp"
 #include "c2ray_beam.hpp"
+#include "c2ray_horizon.hpp"
 #include "c2ray_face.hpp"
 #include "c2ray_plane.hpp"
 #include "c2ray_shell.hpp"
@@ -78,16 +79,19 @@ struct SrcDev {
                        // all-periodic kernels never read them
   int wn[3];           // likewise: the wrap extent of each axis (axis_wrap_extent: the mesh extent if the axis is periodic
                        // while another is open, 0 if it is open)
-  int beam;            // the source's beam (c2r_set_source_beams; c2ray_beam.hpp): BEAM_NONE, BEAM_CONE or BEAM_BICONE ...
-  double bax, bay, baz; // ... its axis as given ...
-  double bK;           // ... and beam_K, cos^2 of the half opening angle times the axis's squared length (0 without a beam)
+  int cut;             // what cuts the source's light short (c2ray_horizon.hpp): its beam's kind (c2r_set_source_beams;
+                       // c2ray_beam.hpp: BEAM_NONE, BEAM_CONE or BEAM_BICONE) | CUT_HORIZON where it has a finite horizon
+                       // (c2r_set_source_horizons); CUT_NONE: neither ...
+  double bax, bay, baz; // ... the beam's axis as given ...
+  double bK;           // ... beam_K, cos^2 of the half opening angle times the axis's squared length (0 without a beam) ...
+  double hR2;          // ... and horizon_R2, the squared radius of the horizon (+infinity without one)
 };
-// Is the cell at offset (di, dj, dk) lit by source S?  Uniform branch on S.beam (a scalar register: the record is read through
-// the scalar cache), so a source without a beam costs a wave one scalar compare; the loss and per-cell kernels ask this
-// beside their in-box test.  (k_rates never asks: batches with a beamed source run k_rates_beam.)
+// Is the cell at offset (di, dj, dk) lit by source S?  Uniform branch on S.cut (a scalar register: the record is read through
+// the scalar cache), so a source with neither beam nor horizon costs a wave one scalar compare; the loss and per-cell kernels
+// ask this beside their in-box test.  (k_rates never asks: batches with such a source run k_rates_beam.)
 __device__ __forceinline__ bool source_lights(const SrcDev &S, double dr1, double dr2, double dr3, int di, int dj, int dk) {
-  if (S.beam == BEAM_NONE) return true;
-  return beam_lit(S.beam, S.bax, S.bay, S.baz, S.bK, dr1, dr2, dr3, di, dj, dk);
+  if (S.cut == CUT_NONE) return true;
+  return cut_lit(S.cut, S.bax, S.bay, S.baz, S.bK, S.hR2, dr1, dr2, dr3, di, dj, dk);
 }
 // the sub-box of the round in flight: the same for every active source of a batch (all are in the same round)
 struct Box {
@@ -1778,7 +1782,7 @@ struct c2r_ctx {
   c2r_comm_timing ctm{};
   hipStream_t stream = nullptr;
   Grid g{};
-  std::string err;
+  mutable std::string err; // (mutable: a getter on a const context says why it refused)
 
   double *d_photo_thick = nullptr, *d_photo_thin = nullptr, *d_heat_thick = nullptr, *d_heat_thin = nullptr;
   // the heating tables as the kernels read them, interleaved by band (c2ray_device.hpp heat_interleave): [sed][thick, thin];
@@ -1814,6 +1818,9 @@ struct c2r_ctx {
   // c2r_set_source_beams: one record per source as it was given, and beam_K of each (empty: no source is beamed)
   std::vector<c2r_source_beam> beams;
   std::vector<double> beam_k;
+  // c2r_set_source_horizons: one radius per source as it was given, and horizon_R2 of each (empty: no source has a horizon)
+  std::vector<double> horizons;
+  std::vector<double> horizon_r2;
 
   double *d_xh = nullptr, *d_xhe = nullptr, *d_xh_av = nullptr, *d_xhe_av = nullptr, *d_xh_int = nullptr,
          *d_xhe_int = nullptr;
@@ -2632,6 +2639,8 @@ static int set_sources_one(c2r_ctx *c, int nsrc, const int *srcpos, const double
   c->normflux_sed[1].clear();
   c->beams.clear();
   c->beam_k.clear();
+  c->horizons.clear();
+  c->horizon_r2.clear();
   return 0;
 }
 
@@ -2705,16 +2714,45 @@ static int set_source_beams_one(c2r_ctx *c, int nsrc, const c2r_source_beam *bea
   return 0;
 }
 
-// the beam of source ns (1-based) in its device record
-static void source_beam(const c2r_ctx *c, int ns, SrcDev &S) {
-  S.beam = BEAM_NONE;
+// c2r_set_source_horizons on one device: everything is checked before anything is kept
+static int set_source_horizons_one(c2r_ctx *c, int nsrc, const double *radius) {
+  if (!c) return 1;
+  if (c->pass_open) return fail(c, "c2r_set_source_horizons: a pass opened by c2r_pass_sources_begin is still open");
+  if (nsrc != c->nsrc) return fail(c, "c2r_set_source_horizons: nsrc = %d, but c2r_set_sources gave %d sources", nsrc, c->nsrc);
+  if (!radius) {
+    c->horizons.clear();
+    c->horizon_r2.clear();
+    return 0;
+  }
+  std::vector<double> r2((size_t)nsrc);
+  for (int s = 0; s < nsrc; s++) {
+    if (!(radius[s] >= 0.0)) // (a NaN fails every comparison)
+      return fail(c, "c2r_set_source_horizons: source %d: radius = %g is negative or not a number", s + 1, radius[s]);
+    r2[(size_t)s] = horizon_R2(radius[s]);
+  }
+  c->horizons.assign(radius, radius + nsrc);
+  c->horizon_r2.swap(r2);
+  return 0;
+}
+
+// the beam and the horizon of source ns (1-based) in its device record
+static void source_cut(const c2r_ctx *c, int ns, SrcDev &S) {
+  S.cut = CUT_NONE;
   S.bax = S.bay = S.baz = S.bK = 0.0;
-  if (c->beams.empty()) return;
-  const c2r_source_beam &b = c->beams[(size_t)ns - 1];
-  if (b.kind == BEAM_NONE) return;
-  S.beam = b.kind;
-  S.bax = b.axis[0]; S.bay = b.axis[1]; S.baz = b.axis[2];
-  S.bK = c->beam_k[(size_t)ns - 1];
+  S.hR2 = INFINITY;
+  if (!c->beams.empty()) {
+    const c2r_source_beam &b = c->beams[(size_t)ns - 1];
+    if (b.kind != BEAM_NONE) {
+      S.cut = b.kind;
+      S.bax = b.axis[0]; S.bay = b.axis[1]; S.baz = b.axis[2];
+      S.bK = c->beam_k[(size_t)ns - 1];
+    }
+  }
+  // (+infinity as given: no horizon.  A finite radius whose square overflows keeps its flag: every cell is within, asked)
+  if (!c->horizons.empty() && std::isfinite(c->horizons[(size_t)ns - 1])) {
+    S.cut |= CUT_HORIZON;
+    S.hR2 = c->horizon_r2[(size_t)ns - 1];
+  }
 }
 
 // The per-frequency vectors of k_build_tables, with the host versions of the bit-exact exp / pow:
@@ -3246,7 +3284,7 @@ struct Batch {
   size_t settled = 0, launched = 0; // recs[0, settled): while-test applied; recs[settled, launched): probes in flight
   bool sweep_started = false;       // ev[0] goes in front of the first shell launch, behind the uploads of records and lists
   int ntiles = 0;                   // tiles in the rates launch's list h_tiles[set] (0: none, every tile of the mesh)
-  bool beamed = false;              // some source of the batch has a beam: its rates launch is k_rates_beam
+  bool beamed = false;              // some source of the batch has a beam or a finite horizon: its rates launch is k_rates_beam
 };
 
 // Queue the probes of the batch's rounds recs[launched ..) (lower bounds of their boundary losses, k_loss_probe_rounds) on
@@ -3432,8 +3470,8 @@ static int place_batch(const PassCtx &P, const std::vector<int> &mine, Batch &B)
     source_wrap(c, S.wn);
     S.nflux = c->normflux[r.ns - 1];
     for (int k = 0; k < 2; k++) S.nflux_sed[k] = c->normflux_sed[k].empty() ? 0.0 : c->normflux_sed[k][r.ns - 1];
-    source_beam(c, r.ns, S);
-    B.beamed = B.beamed || S.beam != BEAM_NONE;
+    source_cut(c, r.ns, S);
+    B.beamed = B.beamed || S.cut != CUT_NONE;
   }
   // coldensh_out = 0 for every new source (evolve_source.F90:94-95) serves two purposes in the
   // reference: the "already done" marker (replaced here by the shell order: every cell is visited
@@ -3918,7 +3956,7 @@ static int launch_rates(const PassCtx &P, Batch &B, bool last_batch) {
                          c->d_bands, P.ss, c->d_rates, lists ? c->d_tiles[B.set] : nullptr, lists ? c->d_tptr[B.set] : nullptr,
                          lists ? c->d_tsrc[B.set] : nullptr, base, fresh);
     };
-    if (cnt > 0 && B.beamed) { // some source of the batch has a beam: the kernel that asks (c2r_set_source_beams)
+    if (cnt > 0 && B.beamed) { // some source of the batch has a beam or a horizon: the kernel that asks (c2r_set_source_beams, _horizons)
       if (c->periodic) {
         if (c->isothermal) P.multi ? go(k_rates_beam<false, true>) : go(k_rates_beam<false, false>);
         else P.multi ? go(k_rates_beam<true, true>) : go(k_rates_beam<true, false>);
@@ -4539,7 +4577,7 @@ extern "C" int c2r_evolve0d(c2r_ctx *c, const int rtpos[3], int ns, int niter, i
   S.loss_lo = -1;
   for (int d = 0; d < 3; d++) { S.rl[d] = R.l[d]; S.rr[d] = R.r[d]; }
   source_wrap(c, S.wn);
-  source_beam(c, ns, S);
+  source_cut(c, ns, S);
   double *dl = on_surface ? c->d_point_loss : nullptr;
   if (!c->isothermal) c->phiheat_dirty = true;
 #define C2R_LAUNCH_POINT(H, M) \
@@ -5304,6 +5342,21 @@ extern "C" int c2r_get_source_beam(const c2r_ctx *c, int ns, c2r_source_beam *ou
   if (!c || !out || ns < 1 || ns > c->nsrc) return 1;
   if (c->beams.empty()) *out = c2r_source_beam{};
   else *out = c->beams[(size_t)ns - 1];
+  return 0;
+}
+
+extern "C" int c2r_set_source_horizons(c2r_ctx *c, int nsrc, const double *radius) {
+  if (int e_ = set_source_horizons_one(c, nsrc, radius)) return e_;
+  return for_replicas(c, [&](c2r_ctx *r) { return set_source_horizons_one(r, nsrc, radius); });
+}
+
+extern "C" int c2r_get_source_horizon(const c2r_ctx *c, int ns, double *radius) {
+  if (!c || !radius) return 1;
+  if (ns < 1 || ns > c->nsrc) {
+    c->err = "c2r_get_source_horizon: source " + std::to_string(ns) + " not in [1," + std::to_string(c->nsrc) + "]";
+    return 1;
+  }
+  *radius = c->horizons.empty() ? (double)INFINITY : c->horizons[(size_t)ns - 1];
   return 0;
 }
 

@@ -116,13 +116,13 @@
     const bool outside = di < S.lo[0] || di > S.hi[0] || dj < S.lo[1] || dj > S.hi[1] || dk < S.lo[2] || dk > S.hi[2];
     C2R_COUNT_LANES(3, !outside);
     if (outside) continue;
-    // A beamed source (S.beam: uniform over the block, a source without a beam takes the path it always took): the
-    // predicate joins the in-box test, before any column is loaded, and nothing of it outlives this statement -- an unlit
+    // A source with a beam or a horizon (S.cut: uniform over the block, a source with neither takes the path it always took):
+    // the predicate (both, with d2 formed once: cut_lit, c2ray_horizon.hpp) joins the in-box test, before any column is loaded, and nothing of it outlives this statement -- an unlit
     // cell is a cell the source does not reach.  One thing remains to do for it: where the rates launch leaves the terms
     // of the kept loss behind (S.loss_lo >= 0), an unlit cell of the counted surface leaves its term, 0.0, in the N_in(HI)
     // slot that k_loss_stored will read.
     if constexpr (BEAM) { // (k_rates_beam only)
-      if (S.beam != BEAM_NONE && !beam_lit(S.beam, S.bax, S.bay, S.baz, S.bK, sc.dr1, sc.dr2, sc.dr3, di, dj, dk)) {
+      if (S.cut != CUT_NONE && !cut_lit(S.cut, S.bax, S.bay, S.baz, S.bK, S.hR2, sc.dr1, sc.dr2, sc.dr3, di, dj, dk)) {
         if (!HEAT && S.loss_lo >= 0) {
           const int ia = di < 0 ? -di : di, ja = dj < 0 ? -dj : dj, ka = dk < 0 ? -dk : dk;
           const int shell = ia > ja ? (ia > ka ? ia : ka) : (ja > ka ? ja : ka);

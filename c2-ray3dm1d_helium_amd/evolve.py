@@ -394,6 +394,22 @@ class HipEngine:
         self._chk(self.lib.c2r_get_source_beam(self.h, int(ns), C.byref(b)))
         return {"kind": int(b.kind), "axis": [float(a) for a in b.axis], "cos_half": float(b.cos_half)}
 
+    def set_source_horizons(self, radii=None):
+        """c2r_set_source_horizons: one photon horizon per point source, in source order -- a maximum ray length in the length
+        unit of dr (a physical length: a pass uses its own dr); None or inf: that source has none.  radii=None: no source has
+        a horizon.  set_sources clears the horizons."""
+        if radii is None:
+            self._chk(self.lib.c2r_set_source_horizons(self.h, int(self.nsrc), None))
+            return
+        arr = np.array([np.inf if r is None else float(r) for r in radii], dtype=np.float64)
+        self._chk(self.lib.c2r_set_source_horizons(self.h, int(arr.size), _dp(arr) if arr.size else None))
+
+    def get_source_horizon(self, ns):
+        """c2r_get_source_horizon for source `ns` (1-based): its radius, inf while it has none."""
+        r = C.c_double(0.0)
+        self._chk(self.lib.c2r_get_source_horizon(self.h, int(ns), C.byref(r)))
+        return float(r.value)
+
     def upload_state(self, mat: Material):
         xh, xhe = _f64(mat.xh).reshape(-1), _f64(mat.xhe).reshape(-1)
         assert xh.size == 2 * self.ncell and xhe.size == 3 * self.ncell

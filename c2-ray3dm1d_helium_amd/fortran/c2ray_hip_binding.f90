@@ -201,6 +201,23 @@ module c2ray_hip
        type(c2r_source_beam), intent(out) :: beam
      end function c2r_get_source_beam
 
+     !> photon horizons: radius(NumSrc), a maximum ray length per source in the length unit of dr (ieee +infinity: none), or
+     !> c_null_ptr: no source has a horizon
+     integer(c_int) function c2r_set_source_horizons(ctx, nsrc, radius) bind(C, name="c2r_set_source_horizons")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: ctx
+       integer(c_int), value :: nsrc
+       type(c_ptr), value :: radius
+     end function c2r_set_source_horizons
+
+     !> the horizon of source ns (1-based) as it was set; +infinity while it has none
+     integer(c_int) function c2r_get_source_horizon(ctx, ns, radius) bind(C, name="c2r_get_source_horizon")
+       import :: c_int, c_ptr, c_double
+       type(c_ptr), value :: ctx
+       integer(c_int), value :: ns
+       real(c_double), intent(out) :: radius
+     end function c2r_get_source_horizon
+
      integer(c_int) function c2r_build_tables(ctx, setup, with_heat) bind(C, name="c2r_build_tables")
        import :: c_int, c_ptr, c2r_sed_setup
        type(c_ptr), value :: ctx

@@ -172,6 +172,47 @@ typedef struct {
 int c2r_set_source_beams(c2r_ctx *ctx, int nsrc, const c2r_source_beam *beams);
 int c2r_get_source_beam(const c2r_ctx *ctx, int ns, c2r_source_beam *out);
 
+/* Photon horizons: a maximum ray length per point source -- a mean free path set by unresolved absorbers, or the causal front
+ * c*(t - t_on) of a source that has just switched on.  The reference's only cap is max_subbox, a compile-time cube in cells.
+ *   radius    one double per source, in the length unit of dr: a PHYSICAL length, so a pass uses the dr of that pass (a host
+ *             that wants a comoving horizon rescales it as it rescales dr); finite and >= 0, or +infinity: no horizon
+ * The rule (csrc/c2ray_horizon.hpp).  When the horizons are set the host forms one double per source, R2 = radius*radius.
+ * For a cell at offset (di, dj, dk) from the source -- the offset exactly as the kernel in question already forms it, as for
+ * a beam -- and the dr of the pass, every product and sum rounded as written and evaluated from the left (the beam's own xs,
+ * ys, zs, d2):
+ *     xs = dr1*(double)di    ys = dr2*(double)dj    zs = dr3*(double)dk
+ *     d2 = (xs*xs + ys*ys) + zs*zs
+ *     within  iff  d2 <= R2
+ * No square root and no division: a cell exactly on the sphere is within, and so is the source's own cell (0 <= R2); radius =
+ * 0 lights the own cell only; a radius so large that R2 overflows to +infinity lights everything.
+ * A cell that is NOT within is UNLIT for that source, in exactly the sense of c2r_set_source_beams: it adds nothing to phih,
+ * phihe or phiheat, and its loss term photo_out*vol/vol_ph is 0.0 in the loss that decides whether the sub-box grows, in the
+ * loss that is kept, in photon_loss(1) and in the escape maps.  A LIT cell gets the bits it gets without a horizon.  A source
+ * with a beam and a horizon lights a cell iff both predicates hold.
+ * What a horizon does not do.  Columns are swept as before, over the whole box (a cell within the sphere only interpolates
+ * from cells nearer the source, which are within it too).  The threshold 1e-10 * total_source_flux of the sub-box loop and
+ * the counting of sum_nbox are unchanged: the loop ends at the first sub-box that contains the sphere, because the deciding
+ * loss becomes 0.0.  Reaches, column blocks and tile lists are untouched.  Planes are untouched.
+ * THERE IS NO HORIZON LOSS: photons cut off at the sphere appear in no loss and no map (the weights vol/vol_ph tile the
+ * surface of a cube, not of a sphere).  With a horizon set, photon_loss no longer closes the photon budget.
+ * Identities.
+ *   Horizons off: with none set, or every radius +infinity, every grid, loss, map and sum_nbox has the bits it had before
+ *     horizons existed, from the same kernel launches.
+ *   Infinite R2: a finite radius whose square overflows (1e200) lights every cell; the results are the unhorizoned bits,
+ *     through the beamed kernels.
+ * c2r_set_source_horizons gives all NumSrc sources their horizons at once (nsrc must equal the NumSrc of c2r_set_sources);
+ * radius = NULL: no source has a horizon.  c2r_set_sources clears the horizons, as it clears beams and extra SEDs;
+ * c2r_set_boundaries* and c2r_set_source_beams keep them.  The horizons act on every device of a multi-device context, and
+ * every route that traces a point source honours them: c2r_pass_sources and its slab-wise form, c2r_do_source,
+ * c2r_pass_allreduce_chemistry, c2r_iteration, c2r_evolve3d, c2r_evolve0d (the loss of an unlit surface cell is 0.0) and the
+ * escape maps.
+ * Refused, each with an error text: a call between c2r_pass_sources_begin and c2r_pass_sources_end; nsrc != NumSrc; a NaN or
+ * negative radius.  A refused call changes nothing.
+ * c2r_get_source_horizon returns the radius of source ns (1-based) as it was set, +infinity while none is set; an ns outside
+ * 1..NumSrc is refused with an error text. */
+int c2r_set_source_horizons(c2r_ctx *ctx, int nsrc, const double *radius);
+int c2r_get_source_horizon(const c2r_ctx *ctx, int ns, double *radius);
+
 /* material:xh, xhe, temperature_grid (temperature may be NULL when isothermal) */
 int c2r_upload_state(c2r_ctx *ctx, const double *xh, const double *xhe, const float *temperature);
 int c2r_download_state(c2r_ctx *ctx, double *xh, double *xhe, float *temperature);
