@@ -147,6 +147,10 @@ SYMBOLS = {
     "c2r_get_face_loss_enabled": (C.c_int, [C.c_void_p]),
     "c2r_download_face_loss": (C.c_int, [C.c_void_p, C.c_int, _dp]),
     "c2r_get_face_loss": (C.c_int, [C.c_void_p, _dp]),
+    "c2r_enable_horizon_loss": (C.c_int, [C.c_void_p, C.c_int]),
+    "c2r_get_horizon_loss_enabled": (C.c_int, [C.c_void_p]),
+    "c2r_get_horizon_loss": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp]),
+    "c2r_download_horizon_rim": (C.c_int, [C.c_void_p, _ip, _ip, _dp, C.c_longlong]),
     "c2r_evolve0d_global": (C.c_int, [C.c_void_p, C.c_double, _ip, _ip]),
     "c2r_evolve0d": (C.c_int, [C.c_void_p, _ip, C.c_int, C.c_int, C.c_int, _dp]),
     "c2r_fraction_minima": (C.c_int, [C.c_void_p, C.c_int, _dp]),

@@ -21,6 +21,8 @@
 //                                  over its face (c2r_set_plane_flux_map); a plane without a map never runs them
 //   escape maps    k_face_loss, k_face_plane_exit   the kept loss of an open box per cell of the mesh face it leaves through
 //                                  (c2r_enable_face_loss): a gather, one lane per face cell, the sources in source order
+//   horizon loss   k_horizon_rim   what crosses the photon horizon of each source that has one (c2r_enable_horizon_loss): one
+//                                  lane per column of the six sheets around the source, k_loss_finish adds the block sums
 //
 // Compile: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fPIC -shared
 #include <hip/hip_runtime.h>
@@ -44,6 +46,7 @@
 #include "c2ray_beam.hpp"
 #include "c2ray_horizon.hpp"
 #include "c2ray_face.hpp"
+#include "c2ray_rim.hpp"
 #include "c2ray_plane.hpp"
 #include "c2ray_shell.hpp"
 
@@ -1623,6 +1626,56 @@ k_face_loss(FaceLayout L, const SrcDev *__restrict__ src, int nsrc, StepScalars 
   if (touched) *slot = acc;
 }
 
+// Horizon loss (c2r_enable_horizon_loss; the rule is c2ray_rim.hpp): what crosses the photon horizon
+// of the sources of a batch that have one (`list`: their places in the batch, one block row each).
+// Lane <-> column: lane t = blockIdx.x * 256 + threadIdx.x of a row is entry t of that source's six sheets (rim_decode: the
+// sheet, then the two transverse offsets from the extents of the source's final box, the lower axis fastest); it finds k*
+// with the exact predicate, gathers the six columns of the column's cell at its shell position and forms po * w.
+// The sum is order-fixed -- the block adds its 256 terms in block_sum's tree, k_loss_finish adds the block sums of a row in
+// order, which is face_sum (c2ray_face.hpp) of the T terms -- so a source's loss has the same bits on every run and for every
+// batch size; no float atomics.  The last row of the launch also stores its terms (c2r_download_horizon_rim).
+// It runs on the sweep stream where k_face_loss runs: after the batch's last shell, the final boxes in the records, before
+// the rates launch; it reads interior cells only, whose N_in(HI) slots the rates launch never overwrites.
+// Cost: about 6 (2R+1)^2 lanes per source against k_rates' (2R+1)^3 cells -- 3/R of its cell.source pairs, each a
+// photo-out band loop without the rates.  Most lanes of a sheet whose columns cross the sphere are busy (pi/4 of them for a
+// sphere that fills its box); a wave sits on one sheet, and consecutive lanes read neighbouring cells of a shell face.
+template <bool MULTI, bool OPEN>
+__global__ void __launch_bounds__(BLOCK)
+k_horizon_rim(const SrcDev *__restrict__ src, const int *__restrict__ list, StepScalars sc, const BandData *__restrict__ bd, SedSet ss,
+              double *__restrict__ partial, int pitch, double *__restrict__ terms) {
+  __shared__ double sh[BLOCK / 64];
+  const SrcDev &S = src[list[blockIdx.y]];
+  const long long t = (long long)blockIdx.x * BLOCK + (long long)threadIdx.x;
+  double term = 0.0;
+  int fc, oa, ob;
+  if (rim_decode(S.lo, S.hi, t, fc, oa, ob)) {
+    int k, o0, o1, o2;
+    double w;
+    if (rim_column(S.cut, S.bax, S.bay, S.baz, S.bK, S.hR2, sc.dr1, sc.dr2, sc.dr3, S.lo, S.hi, fc, oa, ob, k, o0, o1, o2, w)) {
+      const size_t cz = S.cz;
+      const size_t p = OPEN ? reach_position(S.rl, S.rr, o0, o1, o2) : shell_position(o0, o1, o2);
+      if (p < cz) { // (an interior cell of the final box: the block holds its shell)
+        const global_double *cs = (const global_double *)S.cols;
+        const double cin_HI = cs[col_in(p, 0, cz)], cin_HeI = cs[col_in(p, 1, cz)], cin_HeII = cs[col_in(p, 2, cz)];
+        const double cout_HI = cs[col_out(p, 0, cz)], cout_HeI = cs[col_out(p, 1, cz)], cout_HeII = cs[col_out(p, 2, cz)];
+        if (cin_HI < max_coldensh) {
+          double po;
+          if (MULTI) {
+            const double nf[NSED] = {S.nflux, S.nflux_sed[0], S.nflux_sed[1]};
+            po = photo_out_multi(*bd, ss, cin_HI, cout_HI, cin_HeI, cout_HeI, cin_HeII, cout_HeII, nf);
+          } else {
+            po = photo_out_only(*bd, ss.photo_thick[0], ss.photo_thin[0], cin_HI, cout_HI, cin_HeI, cout_HeI, cin_HeII, cout_HeII, S.nflux);
+          }
+          term = po * w;
+        }
+      }
+    }
+    if (blockIdx.y == gridDim.y - 1) terms[t] = term;
+  }
+  const double bs = block_sum(term, sh);
+  if (threadIdx.x == 0) partial[(size_t)blockIdx.y * pitch + blockIdx.x] = bs;
+}
+
 // k_plane_exit with the per-line term kept: the same terms, the same block sums, and map = map + term at the line's
 // face cell of the plane's far face (`map`: that face's map; a plane's face cells are the map's, in its order).
 template <bool MULTI>
@@ -1879,6 +1932,8 @@ struct c2r_ctx {
     std::vector<double> loss;
     std::vector<int> slot; // -1: `loss` holds the value
     std::vector<int> nbox;
+    std::vector<int> rim_ns;      // horizon loss: the batch's horizoned sources (1-based), entry j's sum is h_rim[set][j] ...
+    std::vector<double> rim_loss; // ... until it is resolved into this
   };
   std::vector<BatchTail> tails;
   double *h_tail = nullptr;       // pinned: photon_loss(1:47), sum_nbox on their way to the reduction buffer
@@ -1952,6 +2007,19 @@ struct c2r_ctx {
   bool face_on = false;
   double *d_face_maps = nullptr;    // null while the feature is off or no axis is open
   size_t face_total = 0;            // doubles in it
+
+  // horizon loss (c2r_enable_horizon_loss; the rule is c2ray_rim.hpp): everything below is made by c2r_enable_horizon_loss
+  // except the block sums, which grow with the batches; nothing exists while the feature is off
+  bool rim_on = false;
+  std::vector<double> horizon_loss; // per source, the lifetime of photon_loss (a source without a finite horizon stays 0.0)
+  double *d_rim_terms = nullptr;    // the terms of the horizoned source swept last: 2*(n1*n2 + n0*n2 + n0*n1) doubles
+  size_t rim_terms_cap = 0;
+  double *d_rim_partial[2] = {nullptr, nullptr}; // per ping-pong set: block sums, a row per horizoned source of the batch ...
+  size_t rim_partial_cap[2] = {0, 0};
+  double *d_rim_acc[2] = {nullptr, nullptr}, *h_rim[2] = {nullptr, nullptr}; // ... and their sums (h: pinned), BATCH_MAX each
+  int *d_rim_list[2] = {nullptr, nullptr}, *h_rim_list[2] = {nullptr, nullptr}; // the batch's horizoned sources, BATCH_MAX each
+  int rim_last_ns = 0, rim_last_ext[3] = {0, 0, 0}; // whose terms d_rim_terms holds, and the extents of its final box
+  long long rim_last_stamp = 0;     // ... and the pass that wrote them (as trace_stamp)
 
   // second stream for the rates kernels: the (latency-bound) column sweep of batch n+1 runs beside
   // the (ALU-bound) rates kernel of batch n; two scratch sets ping-pong between them
@@ -2300,6 +2368,23 @@ static int alloc_face_maps(c2r_ctx *c) {
   return 0;
 }
 
+// the buffers of the horizon loss of one device (c2r_enable_horizon_loss, c2r_destroy)
+static void free_horizon_loss(c2r_ctx *c) {
+  if (c->d_rim_terms) (void)hipFree(c->d_rim_terms);
+  c->d_rim_terms = nullptr;
+  c->rim_terms_cap = 0;
+  for (int k = 0; k < 2; k++) {
+    if (c->d_rim_partial[k]) (void)hipFree(c->d_rim_partial[k]);
+    if (c->d_rim_acc[k]) (void)hipFree(c->d_rim_acc[k]);
+    if (c->h_rim[k]) (void)hipHostFree(c->h_rim[k]);
+    if (c->d_rim_list[k]) (void)hipFree(c->d_rim_list[k]);
+    if (c->h_rim_list[k]) (void)hipHostFree(c->h_rim_list[k]);
+    c->d_rim_partial[k] = c->d_rim_acc[k] = c->h_rim[k] = nullptr;
+    c->d_rim_list[k] = c->h_rim_list[k] = nullptr;
+    c->rim_partial_cap[k] = 0;
+  }
+}
+
 // the device and pinned buffers of the plane sources (c2r_set_plane_sources makes them, removal and c2r_destroy free them)
 static void free_plane_buffers(c2r_ctx *c) {
   for (int p = 0; p < PLANE_MAX; p++) {
@@ -2385,6 +2470,7 @@ extern "C" void c2r_destroy(c2r_ctx *c) {
   }
   free_plane_buffers(c);
   free_face_maps(c);
+  free_horizon_loss(c);
   if (c->h_conv) (void)hipHostFree(c->h_conv);
   if (c->h_stat) (void)hipHostFree(c->h_stat);
   if (c->h_iter) (void)hipHostFree(c->h_iter);
@@ -2594,6 +2680,14 @@ static int set_step_one(c2r_ctx *c, const double *ndens, const double dr[3], dou
   return 0;
 }
 
+// horizon loss (c2r_enable_horizon_loss): other sources, other horizons or other boundaries -- the values start at 0.0 again,
+// one per source of the list in force, and the terms of the source swept last are nobody's
+static void forget_horizon_loss(c2r_ctx *c) {
+  if (c->rim_on) c->horizon_loss.assign((size_t)c->nsrc, 0.0);
+  c->rim_last_ns = 0;
+  c->rim_last_stamp = 0;
+}
+
 static int set_sources_one(c2r_ctx *c, int nsrc, const int *srcpos, const double *normflux, double s_star) {
   if (!c) return 1;
   if (nsrc < 0 || (nsrc > 0 && (!srcpos || !normflux))) return fail(c, "c2r_set_sources: bad arguments");
@@ -2641,6 +2735,7 @@ static int set_sources_one(c2r_ctx *c, int nsrc, const int *srcpos, const double
   c->beam_k.clear();
   c->horizons.clear();
   c->horizon_r2.clear();
+  forget_horizon_loss(c);
   return 0;
 }
 
@@ -2722,6 +2817,7 @@ static int set_source_horizons_one(c2r_ctx *c, int nsrc, const double *radius) {
   if (!radius) {
     c->horizons.clear();
     c->horizon_r2.clear();
+    forget_horizon_loss(c);
     return 0;
   }
   std::vector<double> r2((size_t)nsrc);
@@ -2732,6 +2828,7 @@ static int set_source_horizons_one(c2r_ctx *c, int nsrc, const double *radius) {
   }
   c->horizons.assign(radius, radius + nsrc);
   c->horizon_r2.swap(r2);
+  forget_horizon_loss(c);
   return 0;
 }
 
@@ -3124,6 +3221,7 @@ static int set_rates_to_zero_one(c2r_ctx *c) {
   c->rates_zero_pending = true;
   std::memset(c->photon_loss, 0, sizeof c->photon_loss);
   c->sum_nbox = 0;
+  std::fill(c->horizon_loss.begin(), c->horizon_loss.end(), 0.0); // (c2r_enable_horizon_loss)
   // the escape maps follow photon_loss (on the sweep stream, which every kernel that adds to them runs on)
   if (c->d_face_maps) HIPCHK(c, zero_device(c->d_face_maps, sizeof(double) * c->face_total, c->stream));
   return 0;
@@ -3285,6 +3383,7 @@ struct Batch {
   bool sweep_started = false;       // ev[0] goes in front of the first shell launch, behind the uploads of records and lists
   int ntiles = 0;                   // tiles in the rates launch's list h_tiles[set] (0: none, every tile of the mesh)
   bool beamed = false;              // some source of the batch has a beam or a finite horizon: its rates launch is k_rates_beam
+  std::vector<int> rim_ns;          // horizon loss: the sources (1-based) whose sums queue_horizon_rim has queued, in row order
 };
 
 // Queue the probes of the batch's rounds recs[launched ..) (lower bounds of their boundary losses, k_loss_probe_rounds) on
@@ -3372,6 +3471,7 @@ static void resolve_tails(c2r_ctx *c, int set) {
     if (bt.resolved || bt.set != set) continue;
     for (size_t b = 0; b < bt.loss.size(); b++)
       if (bt.slot[b] >= 0) bt.loss[b] = c->h_final[set][bt.slot[b]];
+    for (size_t j = 0; j < bt.rim_ns.size(); j++) bt.rim_loss[j] = c->h_rim[set][j];
     bt.resolved = true;
   }
 }
@@ -3756,6 +3856,51 @@ static int queue_face_loss(const PassCtx &P, const Batch &B) {
   return 0;
 }
 
+// The horizon loss of a batch whose SrcDev records, final boxes included, are on their way to the device on the sweep
+// stream: one launch with a block row per horizoned source that traced anything, one that adds each row's block sums, and
+// the copy of the sums to the host, where resolve_tails finds them once the set's rates launch is through (it waits for
+// this stream).  The last row's terms stay in d_rim_terms (c2r_download_horizon_rim).
+static int queue_horizon_rim(const PassCtx &P, Batch &B) {
+  c2r_ctx *c = P.c;
+  const int set = B.set;
+  int *hl = c->h_rim_list[set];
+  int nh = 0;
+  long long most = 0;
+  for (int b = 0; b < B.nb; b++) {
+    const SrcDev &S = c->h_src[set][b];
+    if (!(S.cut & CUT_HORIZON) || B.run[b].nbox == 0) continue;
+    const long long T = rim_total(rim_extent(S.lo[0], S.hi[0]), rim_extent(S.lo[1], S.hi[1]), rim_extent(S.lo[2], S.hi[2]));
+    if (T > (long long)c->rim_terms_cap)
+      return fail(c, "internal: the %lld sheet columns of source %d do not fit the %zu of the mesh", T, B.run[b].ns, c->rim_terms_cap);
+    most = std::max(most, T);
+    hl[nh++] = b;
+    B.rim_ns.push_back(B.run[b].ns);
+  }
+  if (nh == 0) return 0;
+  const int nblk = (int)((most + BLOCK - 1) / BLOCK);
+  const size_t need = (size_t)nblk * (size_t)nh;
+  if (c->rim_partial_cap[set] < need) {
+    HIPCHK(c, hipStreamSynchronize(c->stream)); // an earlier batch's launches may still use the old buffer
+    if (ensure_pair<double>(c, &c->d_rim_partial[set], (double **)nullptr, &c->rim_partial_cap[set], need)) return 1;
+  }
+  HIPCHK(c, hipMemcpyAsync(c->d_rim_list[set], hl, sizeof(int) * nh, hipMemcpyHostToDevice, c->stream));
+  auto go = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, dim3((unsigned)nblk, (unsigned)nh), dim3(BLOCK), 0, c->stream, c->d_src[set], c->d_rim_list[set], P.sc,
+                       c->d_bands, P.ss, c->d_rim_partial[set], nblk, c->d_rim_terms);
+  };
+  if (c->periodic) P.multi ? go(k_horizon_rim<true, false>) : go(k_horizon_rim<false, false>);
+  else P.multi ? go(k_horizon_rim<true, true>) : go(k_horizon_rim<false, true>);
+  hipLaunchKernelGGL(k_loss_finish, dim3(nh), dim3(BLOCK), 0, c->stream, c->d_rim_partial[set], nblk, nblk, c->d_rim_acc[set]);
+  HIPCHK(c, hipGetLastError());
+  c->tm.sweep_launches += 2;
+  HIPCHK(c, hipMemcpyAsync(c->h_rim[set], c->d_rim_acc[set], sizeof(double) * nh, hipMemcpyDeviceToHost, c->stream));
+  const SrcDev &L = c->h_src[set][hl[nh - 1]];
+  c->rim_last_ns = B.rim_ns.back();
+  for (int d = 0; d < 3; d++) c->rim_last_ext[d] = rim_extent(L.lo[d], L.hi[d]);
+  c->rim_last_stamp = P.stamp;
+  return 0;
+}
+
 // Final sub-boxes for the rates launch, what the next pass learns from this one (prev_nbox, prev_grow), the upload of the
 // SrcDev entries; then the rates stream takes the batch over.
 static int close_boxes(PassCtx &P, Batch &B) {
@@ -3796,20 +3941,26 @@ static int close_boxes(PassCtx &P, Batch &B) {
   // Escape maps: the batch's terms, here -- the final boxes are known, the batch will not start over, and the N_in(HI)
   // slots still hold columns (the rates launch, which waits for the event below, overwrites them where SrcDev::loss_lo
   // asks it to).  The records go up first, and the kernel counts into the sweep's span.
+  // Horizon loss: likewise, for the sources of the batch that have a finite horizon and traced anything.
+  B.rim_ns.clear();
+  bool rim = false;
+  if (c->rim_on)
+    for (int b = 0; b < B.nb && !rim; b++) rim = (c->h_src[B.set][b].cut & CUT_HORIZON) && B.run[b].nbox > 0;
   const bool maps = c->d_face_maps != nullptr;
-  if (maps) {
+  if (maps || rim) {
     if (c->timing && !B.sweep_started) {
       HIPCHK(c, hipEventRecord(B.ev[0], c->stream));
       B.sweep_started = true;
     }
     HIPCHK(c, hipMemcpyAsync(c->d_src[B.set], c->h_src[B.set], sizeof(SrcDev) * B.nb, hipMemcpyHostToDevice, c->stream));
-    if (queue_face_loss(P, B)) return 1;
+    if (maps && queue_face_loss(P, B)) return 1;
+    if (rim && queue_horizon_rim(P, B)) return 1;
   }
   if (c->timing) { // the sweep's span: from the first shell launch to the last, record uploads on either side left out
     if (!B.sweep_started) HIPCHK(c, hipEventRecord(B.ev[0], c->stream));
     HIPCHK(c, hipEventRecord(B.ev[1], c->stream));
   }
-  if (!maps) HIPCHK(c, hipMemcpyAsync(c->d_src[B.set], c->h_src[B.set], sizeof(SrcDev) * B.nb, hipMemcpyHostToDevice, c->stream));
+  if (!maps && !rim) HIPCHK(c, hipMemcpyAsync(c->d_src[B.set], c->h_src[B.set], sizeof(SrcDev) * B.nb, hipMemcpyHostToDevice, c->stream));
   if (!P.transposed_seen) {
     // small boxes only: nobody needed the copies, but whatever follows this sweep (the global pass rewrites the
     // state) has to come after the kernel that reads it
@@ -4050,7 +4201,9 @@ static int queue_kept_losses(const PassCtx &P, Batch &B) {
     B.list_used += (size_t)nf;
   }
   if (nslot > 0) HIPCHK(c, hipMemcpyAsync(c->h_final[set], c->d_final_acc[set], sizeof(double) * nslot, hipMemcpyDeviceToHost, c->stream2));
-  bt.resolved = nslot == 0;
+  bt.rim_ns = B.rim_ns; // (c2r_enable_horizon_loss: their sums are on their way to h_rim[set] on the sweep stream)
+  bt.rim_loss.assign(bt.rim_ns.size(), 0.0);
+  bt.resolved = nslot == 0 && bt.rim_ns.empty();
   c->tails.push_back(std::move(bt));
   return 0;
 }
@@ -4263,6 +4416,7 @@ static int pass_list(c2r_ctx *c, const std::vector<int> &dealt, int nslab = 0) {
   // this list; entries still here belong to a pass that ended in an error and must not be added to this one
   c->tails.clear();
   if (c->prev_nbox.size() != (size_t)c->nsrc) c->prev_nbox.assign((size_t)c->nsrc, 0);
+  if (c->rim_on && c->horizon_loss.size() != (size_t)c->nsrc) c->horizon_loss.assign((size_t)c->nsrc, 0.0);
   if (c->trace.size() != (size_t)c->nsrc) {
     c->trace.assign((size_t)c->nsrc, c2r_source_trace{});
     c->trace_stamp.assign((size_t)c->nsrc, 0);
@@ -4362,6 +4516,11 @@ static int pass_finish(c2r_ctx *c) {
     for (size_t b = 0; b < bt.loss.size(); b++) {
       c->photon_loss[0] = c->photon_loss[0] + bt.loss[b];
       c->sum_nbox += bt.nbox[b];
+    }
+  for (const c2r_ctx::BatchTail &bt : c->tails) // horizon loss: loss[ns] = loss[ns] + (this pass's sum)
+    for (size_t j = 0; j < bt.rim_ns.size(); j++) {
+      double &hl = c->horizon_loss[(size_t)bt.rim_ns[j] - 1];
+      hl = hl + bt.rim_loss[j];
     }
   c->tails.clear();
   // tail of the reduction buffer: photon_loss(1:47), sum_nbox
@@ -5323,6 +5482,94 @@ extern "C" int c2r_get_face_loss(c2r_ctx *c, double out6[6]) {
   return 0;
 }
 
+// ---------------------------------------------------------------------------------------------
+// horizon loss
+static int enable_horizon_loss_one(c2r_ctx *c, int on) {
+  if (!c) return 1;
+  if (c->pass_open) return fail(c, "c2r_enable_horizon_loss: a pass opened by c2r_pass_sources_begin is still open (close it with c2r_pass_sources_end first)");
+  HIPCHK(c, hipSetDevice(c->device));
+  if (!on) {
+    if (c->rim_on) HIPCHK(c, hipStreamSynchronize(c->stream)); // nothing queued may still write the buffers
+    free_horizon_loss(c);
+    c->rim_on = false;
+    c->horizon_loss.clear();
+    c->rim_last_ns = 0;
+    c->rim_last_stamp = 0;
+    return 0;
+  }
+  if (c->rim_on) return 0;
+  const size_t n0 = (size_t)c->g.n1, n1 = (size_t)c->g.n2, n2 = (size_t)c->g.n3;
+  auto allocate = [&]() -> int {
+    c->rim_terms_cap = 2 * (n1 * n2 + n0 * n2 + n0 * n1);
+    HIPCHK(c, hipMalloc(&c->d_rim_terms, sizeof(double) * c->rim_terms_cap));
+    for (int k = 0; k < 2; k++) {
+      HIPCHK(c, hipMalloc(&c->d_rim_acc[k], sizeof(double) * BATCH_MAX));
+      HIPCHK(c, hipHostMalloc(&c->h_rim[k], sizeof(double) * BATCH_MAX));
+      HIPCHK(c, hipMalloc(&c->d_rim_list[k], sizeof(int) * BATCH_MAX));
+      HIPCHK(c, hipHostMalloc(&c->h_rim_list[k], sizeof(int) * BATCH_MAX));
+    }
+    return 0;
+  };
+  if (allocate()) {
+    free_horizon_loss(c); // (an allocation failed half way: nothing stays behind; the feature was off and stays off)
+    return 1;
+  }
+  c->rim_on = true;
+  forget_horizon_loss(c);
+  return 0;
+}
+
+extern "C" int c2r_enable_horizon_loss(c2r_ctx *c, int on) {
+  if (int e_ = enable_horizon_loss_one(c, on)) return e_; // (a refused call changes nothing)
+  return for_replicas(c, [&](c2r_ctx *r) { return enable_horizon_loss_one(r, on); });
+}
+
+extern "C" int c2r_get_horizon_loss_enabled(const c2r_ctx *c) { return c && c->rim_on ? 1 : 0; }
+
+// per source: the devices of the context added in device order (a source is swept by one device of a deal, the others hold 0.0)
+extern "C" int c2r_get_horizon_loss(c2r_ctx *c, int nsrc, double *per_source, double *total) {
+  if (!c) return 1;
+  if (!c->rim_on) return fail(c, "c2r_get_horizon_loss: the horizon loss is off (c2r_enable_horizon_loss)");
+  if (nsrc != c->nsrc) return fail(c, "c2r_get_horizon_loss: nsrc = %d, but c2r_set_sources gave %d sources", nsrc, c->nsrc);
+  if (c->pass_open) return fail(c, "c2r_get_horizon_loss: a pass opened by c2r_pass_sources_begin is still open");
+  double sum = 0.0;
+  for (int s = 0; s < nsrc; s++) {
+    double v = (size_t)s < c->horizon_loss.size() ? c->horizon_loss[(size_t)s] : 0.0;
+    for (const c2r_ctx *r : c->replicas)
+      if ((size_t)s < r->horizon_loss.size()) v = v + r->horizon_loss[(size_t)s];
+    if (per_source) per_source[s] = v;
+    sum = sum + v;
+  }
+  if (total) *total = sum;
+  return 0;
+}
+
+extern "C" int c2r_download_horizon_rim(c2r_ctx *c, int *ns, int extent[3], double *terms, long long capacity) {
+  if (!c) return 1;
+  if (!ns || !extent || !terms) return fail(c, "c2r_download_horizon_rim: null argument");
+  if (!c->rim_on) return fail(c, "c2r_download_horizon_rim: the horizon loss is off (c2r_enable_horizon_loss)");
+  if (c->pass_open) return fail(c, "c2r_download_horizon_rim: a pass opened by c2r_pass_sources_begin is still open");
+  // the context itself or, of a multi-device context, the device that swept a horizoned source last
+  c2r_ctx *from = nullptr;
+  long long stamp = 0;
+  auto look = [&](c2r_ctx *r) {
+    if (r->rim_last_ns > 0 && r->rim_last_stamp > stamp) { stamp = r->rim_last_stamp; from = r; }
+  };
+  look(c);
+  for (c2r_ctx *r : c->replicas) look(r);
+  if (!from) return fail(c, "c2r_download_horizon_rim: no source with a finite horizon has been swept yet");
+  const long long T = rim_total(from->rim_last_ext[0], from->rim_last_ext[1], from->rim_last_ext[2]);
+  *ns = from->rim_last_ns;
+  for (int d = 0; d < 3; d++) extent[d] = from->rim_last_ext[d];
+  if (capacity < T)
+    return fail(c, "c2r_download_horizon_rim: capacity = %lld, but source %d has T = %lld terms (extents %d x %d x %d)", capacity, *ns, T,
+                extent[0], extent[1], extent[2]);
+  HIPCHK(c, hipSetDevice(from->device));
+  HIPCHK(c, hipMemcpyAsync(terms, from->d_rim_terms, sizeof(double) * (size_t)T, hipMemcpyDeviceToHost, from->stream));
+  HIPCHK(c, hipStreamSynchronize(from->stream));
+  return 0;
+}
+
 extern "C" int c2r_set_sed_tables(c2r_ctx *c, int sed, const double *photo_thick, const double *photo_thin, const double *heat_thick, const double *heat_thin, int lower, int upper) {
   if (int e_ = set_sed_tables_one(c, sed, photo_thick, photo_thin, heat_thick, heat_thin, lower, upper)) return e_;
   return for_replicas(c, [&](c2r_ctx *r) { return set_sed_tables_one(r, sed, photo_thick, photo_thin, heat_thick, heat_thin, lower, upper); });
@@ -5447,6 +5694,7 @@ static int set_boundaries_one(c2r_ctx *c, const int periodic[3]) {
   c->trace_stamp.clear();
   c->last_src = 0;
   c->last_cols = nullptr;
+  forget_horizon_loss(c);
   return 0;
 }
 

@@ -26,8 +26,11 @@
 // total_source_flux of the sub-box loop and the way sum_nbox counts rounds are what they were: the loop ends at the first
 // sub-box that contains the sphere because the deciding loss becomes 0.0.  Reaches, column blocks and tile lists are
 // untouched (an unlit lane leaves the source loop before any column load).  Planes are untouched.
-// THERE IS NO HORIZON LOSS.  Photons cut off at the sphere appear in no loss and no map: the solid-angle weights vol/vol_ph
-// tile the surface of a cube, not of a sphere.  With a horizon set, photon_loss no longer closes the photon budget.
+// THERE IS NO HORIZON LOSS unless c2r_enable_horizon_loss.  Photons cut off at the sphere appear in no loss and no map, and
+// with a horizon set photon_loss alone does not close the photon budget.  The horizon loss does (c2ray_rim.hpp): the cells
+// within the horizon are a closed staircase whose boundary is made of cell faces, and a weight per exposed face at the face
+// centre -- w = ((dr_a*dr_b)*fd) / ((4.0*pi)*(f2*sqrt(f2))), f2 = (xa*xa + xb*xb) + fd*fd, fd = dr_d*((double)k* + 0.5), 1/6
+// for the faces of the source's own cell -- tiles the sphere; a source's loss is the fixed-order sum of po * w over its faces.
 //
 // Identities.
 //   Horizons off.  With no horizons set, or every radius +infinity, every grid, loss, map and sum_nbox has the bits, and the

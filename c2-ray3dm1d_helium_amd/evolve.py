@@ -627,6 +627,34 @@ class HipEngine:
         self._chk(self.lib.c2r_get_face_loss(self.h, _dp(out)))
         return out
 
+    # -- horizon loss (c2r_enable_horizon_loss; include/c2ray_hip.h has the rule) -------------------------------
+    def enable_horizon_loss(self, on=True):
+        """Keep, per point source, what crosses its photon horizon (off by default)."""
+        self._chk(self.lib.c2r_enable_horizon_loss(self.h, int(on)))
+
+    @property
+    def horizon_loss_enabled(self):
+        return bool(self.lib.c2r_get_horizon_loss_enabled(self.h))
+
+    def horizon_loss(self):
+        """(per_source, total) since the last set_rates_to_zero: one double per point source (0.0 without a finite horizon)
+        and their sum in source order."""
+        per = np.zeros(int(self.nsrc))
+        tot = C.c_double(0.0)
+        self._chk(self.lib.c2r_get_horizon_loss(self.h, int(self.nsrc), _dp(per) if per.size else None, C.byref(tot)))
+        return per, tot.value
+
+    def horizon_rim(self):
+        """The diagnostic of c2r_download_horizon_rim: (ns, extent, terms) of the point source with a finite horizon that was
+        swept last -- its 1-based number, the extents of its final box and the T = 2*(E1*E2 + E0*E2 + E0*E1) terms, the six
+        sheets one behind the other."""
+        ns, ext = C.c_int(0), (C.c_int * 3)()
+        cap = 2 * (self.mesh[1] * self.mesh[2] + self.mesh[0] * self.mesh[2] + self.mesh[0] * self.mesh[1])
+        out = np.zeros(cap)
+        self._chk(self.lib.c2r_download_horizon_rim(self.h, C.byref(ns), ext, _dp(out), cap))
+        e = [int(x) for x in ext]
+        return ns.value, e, out[:2 * (e[1] * e[2] + e[0] * e[2] + e[0] * e[1])].copy()
+
     def enable_timing(self, on=True):
         self._chk(self.lib.c2r_enable_timing(self.h, int(on)))
 

@@ -688,6 +688,37 @@ module c2ray_hip
        real(c_double), intent(out) :: out6(6)
      end function c2r_get_face_loss
 
+     !> horizon loss (include/c2ray_hip.h): what crosses each source's photon horizon, per source; off by default
+     integer(c_int) function c2r_enable_horizon_loss(ctx, on) bind(C, name="c2r_enable_horizon_loss")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: ctx
+       integer(c_int), value :: on
+     end function c2r_enable_horizon_loss
+
+     integer(c_int) function c2r_get_horizon_loss_enabled(ctx) bind(C, name="c2r_get_horizon_loss_enabled")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: ctx
+     end function c2r_get_horizon_loss_enabled
+
+     !> per_source(nsrc), nsrc = NumSrc; total: their sum in source order
+     integer(c_int) function c2r_get_horizon_loss(ctx, nsrc, per_source, total) bind(C, name="c2r_get_horizon_loss")
+       import :: c_int, c_ptr, c_double
+       type(c_ptr), value :: ctx
+       integer(c_int), value :: nsrc
+       real(c_double), intent(out) :: per_source(*)
+       real(c_double), intent(out) :: total
+     end function c2r_get_horizon_loss
+
+     !> diagnostic: the T = 2*(E1*E2 + E0*E2 + E0*E1) terms of the horizoned source swept last, its number and extents
+     integer(c_int) function c2r_download_horizon_rim(ctx, ns, extent, terms, capacity) bind(C, name="c2r_download_horizon_rim")
+       import :: c_int, c_ptr, c_double, c_long_long
+       type(c_ptr), value :: ctx
+       integer(c_int), intent(out) :: ns
+       integer(c_int), intent(out) :: extent(3)
+       real(c_double), intent(out) :: terms(*)
+       integer(c_long_long), value :: capacity
+     end function c2r_download_horizon_rim
+
      integer(c_int) function c2r_enable_timing(ctx, on) bind(C, name="c2r_enable_timing")
        import :: c_int, c_ptr
        type(c_ptr), value :: ctx

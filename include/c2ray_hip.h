@@ -193,8 +193,8 @@ int c2r_get_source_beam(const c2r_ctx *ctx, int ns, c2r_source_beam *out);
  * from cells nearer the source, which are within it too).  The threshold 1e-10 * total_source_flux of the sub-box loop and
  * the counting of sum_nbox are unchanged: the loop ends at the first sub-box that contains the sphere, because the deciding
  * loss becomes 0.0.  Reaches, column blocks and tile lists are untouched.  Planes are untouched.
- * THERE IS NO HORIZON LOSS: photons cut off at the sphere appear in no loss and no map (the weights vol/vol_ph tile the
- * surface of a cube, not of a sphere).  With a horizon set, photon_loss no longer closes the photon budget.
+ * THERE IS NO HORIZON LOSS unless c2r_enable_horizon_loss (below): photons cut off at the sphere appear in no loss and no
+ * map, and with a horizon set photon_loss alone does not close the photon budget; the horizon loss does.
  * Identities.
  *   Horizons off: with none set, or every radius +infinity, every grid, loss, map and sum_nbox has the bits it had before
  *     horizons existed, from the same kernel launches.
@@ -212,6 +212,52 @@ int c2r_get_source_beam(const c2r_ctx *ctx, int ns, c2r_source_beam *out);
  * 1..NumSrc is refused with an error text. */
 int c2r_set_source_horizons(c2r_ctx *ctx, int nsrc, const double *radius);
 int c2r_get_source_horizon(const c2r_ctx *ctx, int ns, double *radius);
+
+/* Horizon loss: what crosses each source's photon horizon, per source.  The rule (csrc/c2ray_rim.hpp).  The cells within a
+ * horizon are a closed staircase around the source whose boundary is made of cell faces; the solid angles of those faces add up
+ * to 4 pi, so a weight per exposed face, taken at the face centre, tiles the sphere: summed over a box that contains the
+ * sphere the weights give 1 to within 6.3e-4 at a radius of 5 cells and 4e-6 at 16.
+ * For one point source with a finite horizon: R2, the dr of the pass and the final sub-box lo[3]..hi[3] (offsets).
+ *   Sheets.  Six sheets, fc = 2*d + (s > 0 ? 1 : 0) for axis d and sign s = -1, +1 (the face numbering of the escape maps).
+ *     Sheet fc has one entry per pair of transverse offsets (oa, ob), the two other axes a < b, a fastest, over the box's
+ *     extents E_a = hi_a - lo_a + 1 and E_b: entry (oa - lo_a) + E_a*(ob - lo_b).  The six sheets lie one behind the other in
+ *     face order, T = 2*(E1*E2 + E0*E2 + E0*E1) entries.
+ *   The face of a sheet column.  Along the column cells have o_d = s*k, k = 0, 1, ...; the predicate above is monotone in k.
+ *     If the k = 0 cell is not within, the column has no face.  Otherwise k* is the largest k whose cell is within and inside
+ *     the box, and the column has a face iff that cell is not on the surface of the final box on any axis (lo_e < o_e < hi_e
+ *     for all e: surface cells give their term to the kept loss), the cell at k* + 1 is not within, and the cell is lit (a
+ *     beam-unlit cell has no face).  The two sheets of an axis both see the k = 0 cell; each owns its own face of it.
+ *   Weight: the solid angle over 4 pi of that face at its centre, every product and sum rounded as written and evaluated from
+ *     the left, no contraction (pi: the float-rounded constant of the kept loss):
+ *         xa = dr_a*(double)oa     xb = dr_b*(double)ob     fd = dr_d*((double)k* + 0.5)
+ *         f2 = (xa*xa + xb*xb) + fd*fd
+ *         w  = ((dr_a*dr_b)*fd) / ((4.0*pi)*(f2*sqrt(f2)))
+ *     The source's own cell (oa = ob = 0, k* = 0) takes w = 1.0/6.0 instead.
+ *   Term: po * w, po the photo_out of the cell from its six stored columns, formed as the escape maps form it (0.0 where
+ *     N_in(HI) >= max_coldensh); a column without a face has the term +0.0.
+ *   The horizon loss of a source in a pass: its T terms added in the fixed order of c2r_get_face_loss (blocks of 256 by a
+ *     tree, then the block sums in order).  No float atomics: the same bits on every run and for every c2r_set_batch.
+ * Off by default; while it is off nothing is allocated, launched or waited for.  The values live as photon_loss lives:
+ * c2r_set_rates_to_zero clears them, every pass that sweeps source ns does loss[ns] = loss[ns] + (that pass's sum), a source
+ * without a finite horizon stays 0.0.  c2r_set_sources, c2r_set_source_horizons and a change of boundary mode zero them.
+ * Routes that honour it: c2r_pass_sources and its slab-wise form (complete after c2r_pass_sources_end), c2r_do_source,
+ * c2r_pass_allreduce_chemistry, c2r_iteration and c2r_evolve3d (the last iteration's pass).  c2r_evolve0d and planes do not
+ * know it.  It is NOT part of the reduction buffer: c2r_rates_count and its layout are unchanged; a multi-device context
+ * answers per source from the device that swept it (the devices' values added in device order), across processes a rank
+ * reports its own sources and 0.0 for the others.  It changes no bit of any rate grid, photon_loss, escape map, sum_nbox,
+ * sub-box decision or existing launch.
+ * c2r_get_horizon_loss: per_source (may be NULL) takes nsrc doubles, nsrc must equal NumSrc; *total (may be NULL) their sum in
+ * source order, added on the host.
+ * c2r_download_horizon_rim (a diagnostic, like c2r_download_columns): the T terms of the point source with a finite horizon
+ * that was swept last, its number *ns (1-based) and the extents extent[3] of its final box.  With capacity < T the call is
+ * refused, its error text names T, and *ns and extent[] are set all the same (T follows from them).
+ * Refused, each with an error text: enabling or disabling between c2r_pass_sources_begin and _end; nsrc != NumSrc; either
+ * getter while the feature is off or while a slab-wise pass is open; a download before any horizoned source was swept; a
+ * capacity < T. */
+int c2r_enable_horizon_loss(c2r_ctx *ctx, int on);
+int c2r_get_horizon_loss_enabled(const c2r_ctx *ctx);
+int c2r_get_horizon_loss(c2r_ctx *ctx, int nsrc, double *per_source, double *total);
+int c2r_download_horizon_rim(c2r_ctx *ctx, int *ns, int extent[3], double *terms, long long capacity);
 
 /* material:xh, xhe, temperature_grid (temperature may be NULL when isothermal) */
 int c2r_upload_state(c2r_ctx *ctx, const double *xh, const double *xhe, const float *temperature);
