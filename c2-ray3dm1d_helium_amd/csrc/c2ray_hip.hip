@@ -14,12 +14,9 @@
 //   chemistry      k_chemistry     evolve0D_global / do_chemistry / doric / thermal per cell
 //   statistics     k_state_sums, k_total_rates, k_stat_finish   the grid sums of photonstatistics.f90
 //   tables         k_build_tables  spec_integration: the photo-ionisation / heating tables of one SED
-//   plane sources  k_plane_columns, k_plane_rates, k_plane_exit   a plane wave entering through an open mesh face: the 1-D
-//                                  march of every line of cells along the axis, its rates, what leaves through the far face
-//                  k_plane_layer   one layer of the march of a tilted plane (c2r_set_plane_tilt), one launch per layer
-//                  k_pflux_layer, k_pflux_rates, k_pflux_exit, k_face_pflux_exit   the same for a plane whose flux is a map
-//                                  over its face (c2r_set_plane_flux_map); a plane without a map never runs them
-//   escape maps    k_face_loss, k_face_plane_exit   the kept loss of an open box per cell of the mesh face it leaves through
+//   plane sources  k_plane_columns, k_plane_layer, k_plane_rates, k_plane_exit   a plane wave entering through an open mesh
+//                                  face (c2ray_planes.inc): the march along the axis, its rates, what leaves through the far face
+//   escape maps    k_face_loss     the kept loss of an open box per cell of the mesh face it leaves through
 //                                  (c2r_enable_face_loss): a gather, one lane per face cell, the sources in source order
 //   horizon loss   k_horizon_rim   what crosses the photon horizon of each source that has one (c2r_enable_horizon_loss): one
 //                                  lane per column of the six sheets around the source, k_loss_finish adds the block sums
@@ -1390,177 +1387,6 @@ __global__ void __launch_bounds__(BLOCK) k_divide_by(double *__restrict__ a, siz
 }
 
 // ---------------------------------------------------------------------------------------------
-// Plane-parallel sources (c2r_set_plane_sources; the per-cell rule is c2ray_plane.hpp): a plane
-// wave enters through an open face and travels along one axis, every line of cells a 1-D problem of its own.  Three
-// kernels per plane and pass, all on the sweep stream: the columns (a march, one lane per line), the rates (no
-// dependencies, one lane per cell) and what leaves through the far face.  A tilted plane (c2r_set_plane_tilt) replaces the
-// first by one launch of k_plane_layer per layer; the other two are the same kernels with the tilted path.
-struct PlaneDev {
-  double nf[NSED]; // NormFlux per cm^2 of face: black body, power law, quasar-like
-};
-
-// The march: lane f owns column f of the face and walks the mesh[axis] cells behind it in travel order, handing each
-// cell's outgoing columns to the next as its incoming ones.  Writes the incoming columns of every cell (LLS fog applied),
-// 3 doubles per cell in mesh order, and the outgoing columns of the last cell (species slowest).  Memory-bound and cheap
-// next to the rates: 32 bytes read and 24 written per cell.  Along axis 0 the lanes of a wave are n1 doubles apart, but
-// 16 consecutive steps of a lane stay within one 128-byte line of each grid, so the lines are fetched once.
-__global__ void __launch_bounds__(BLOCK)
-k_plane_columns(PlaneGeom G, StepScalars sc, double path, size_t nc, const double *__restrict__ ndens, const double *__restrict__ xh_av,
-                const double *__restrict__ xhe_av, const float *__restrict__ lls_grid, const double *__restrict__ entry,
-                double *__restrict__ cin_out, double *__restrict__ exit_cols) {
-  const int face = G.fa * G.fb;
-  const int f = (int)blockIdx.x * BLOCK + (int)threadIdx.x;
-  if (f >= face) return;
-  double c_HI = 0.0, c_HeI = 0.0, c_HeII = 0.0;
-  if (entry) { c_HI = entry[f]; c_HeI = entry[face + f]; c_HeII = entry[2 * face + f]; }
-  long long q = (long long)plane_cell(G, f, 0);
-  const long long step = G.from_high ? -(long long)G.sa : (long long)G.sa;
-  for (int m = 0; m < G.na; m++, q += step) {
-    const double lls = sc.use_lls ? (lls_grid ? (double)lls_grid[q] : sc.coldensh_lls) : 0.0;
-    double o_HI, o_HeI, o_HeII;
-    plane_cell_columns(ndens[q], xh_av[q], xhe_av[q], xhe_av[q + (long long)nc], path, sc.dr1, sc.use_lls, lls, c_HI, c_HeI, c_HeII,
-                       o_HI, o_HeI, o_HeII);
-    cin_out[3 * q] = c_HI; // (with the fog: what the rates and the exit loss see)
-    cin_out[3 * q + 1] = c_HeI;
-    cin_out[3 * q + 2] = c_HeII;
-    c_HI = o_HI; c_HeI = o_HeI; c_HeII = o_HeII;
-  }
-  exit_cols[f] = c_HI;
-  exit_cols[face + f] = c_HeI;
-  exit_cols[2 * face + f] = c_HeII;
-}
-
-// One layer of the march of a tilted plane (c2r_set_plane_tilt, PlaneTilt): lane (u, v) owns face cell (u, v) of layer m
-// (travel order), interpolates its incoming columns from four cells of the layer before (`prev`: that layer's outgoing
-// columns, 3 x face, or the entry columns, or null = zero) and writes the fogged incoming columns into the cell's place of
-// cin_out and the outgoing ones into `next`.  The layers depend on each other as the shells of a point source do, and are
-// ordered the same way: one launch per layer on the sweep stream.  prev and next are different
-// buffers: every lane of the launch reads only what earlier launches wrote.
-// A block is 64 x 4 face cells, a wave one row of 64 along f: its 12 loads of prev are unit-stride (shifted by at most one
-// cell, and by whole rows), u and v come from the block and thread indices (no division), the wrap is a compare and an
-// add.  The loads of the mesh grids are unit-stride for axis 1 and 2 and n1 doubles apart for axis 0, where 16
-// consecutive layers share each 128-byte line.
-constexpr int PLANE_LAYER_BX = 64, PLANE_LAYER_BY = 4;
-// The columns of face cell (u, v) of layer m, what k_plane_layer and k_pflux_layer have in common: N_in from the layer
-// before, the fog, N_out; cin_out at the cell, `next` at the face cell.  Returns the cell.
-__device__ __forceinline__ size_t plane_layer_cell(const PlaneGeom &G, const PlaneTilt &T, const StepScalars &sc, int m, size_t nc,
-                                                   const double *__restrict__ ndens, const double *__restrict__ xh_av,
-                                                   const double *__restrict__ xhe_av, const float *__restrict__ lls_grid,
-                                                   const double *__restrict__ prev, double *__restrict__ cin_out,
-                                                   double *__restrict__ next, int u, int v) {
-  const int face = G.fa * G.fb, f = u + G.fa * v;
-  const int along = G.from_high ? G.na - 1 - m : m;
-  const size_t q = (size_t)u * G.sf + (size_t)v * G.sg + (size_t)along * G.sa;
-  double c_HI, c_HeI, c_HeII;
-  plane_layer_in(T, G.fa, G.fb, u, v, prev, c_HI, c_HeI, c_HeII);
-  const double lls = sc.use_lls ? (lls_grid ? (double)lls_grid[q] : sc.coldensh_lls) : 0.0;
-  double o_HI, o_HeI, o_HeII;
-  plane_cell_columns(ndens[q], xh_av[q], xhe_av[q], xhe_av[q + nc], T.path, sc.dr1, sc.use_lls, lls, c_HI, c_HeI, c_HeII, o_HI, o_HeI,
-                     o_HeII);
-  cin_out[3 * q] = c_HI;
-  cin_out[3 * q + 1] = c_HeI;
-  cin_out[3 * q + 2] = c_HeII;
-  next[f] = o_HI;
-  next[face + f] = o_HeI;
-  next[2 * face + f] = o_HeII;
-  return q;
-}
-
-__global__ void __launch_bounds__(PLANE_LAYER_BX * PLANE_LAYER_BY)
-k_plane_layer(PlaneGeom G, PlaneTilt T, StepScalars sc, int m, size_t nc, const double *__restrict__ ndens,
-              const double *__restrict__ xh_av, const double *__restrict__ xhe_av, const float *__restrict__ lls_grid,
-              const double *__restrict__ prev, double *__restrict__ cin_out, double *__restrict__ next) {
-  const int u = (int)blockIdx.x * PLANE_LAYER_BX + (int)threadIdx.x, v = (int)blockIdx.y * PLANE_LAYER_BY + (int)threadIdx.y;
-  if (u >= G.fa || v >= G.fb) return;
-  plane_layer_cell(G, T, sc, m, nc, ndens, xh_av, xhe_av, lls_grid, prev, cin_out, next, u, v);
-}
-
-// The rates of every cell from one plane, added to the rate grids: k_rates' shape -- a block is a tile of 8 x 8 x 4
-// cells, a wave a 4 x 4 x 4 cube of it (neighbours see similar optical depths and take the same branches), the log's
-// table in LDS -- with one source whose columns come in mesh order and whose vol_ph is dr[axis].  One lane per cell and
-// not per line: the rates are some thousands of fp64 instructions per cell, and N^2 lanes would leave the device idle.
-// The outgoing columns are formed again from the incoming ones (plane_cell_out, the expression the march used).
-// What k_plane_rates and k_pflux_rates have in common.  The tile decode: the cell (i, j, k) of this lane, false outside the
-// mesh ...
-__device__ __forceinline__ bool plane_rates_lane(const Grid &g, int &i, int &j, int &k) {
-  const int ti = (g.n1 + 7) >> 3, tj = (g.n2 + 7) >> 3;
-  const int tile = (int)blockIdx.x;
-  const int bi = tile % ti, bj = (tile / ti) % tj, bk = tile / (ti * tj);
-  const int lane = threadIdx.x & 63;
-  const int w_ = threadIdx.x >> 6;
-  i = bi * 8 + (w_ & 1) * 4 + (lane & 3), j = bj * 8 + (w_ >> 1) * 4 + ((lane >> 2) & 3), k = bk * 4 + (lane >> 4);
-  return i < g.n1 && j < g.n2 && k < g.n3;
-}
-// ... and the rates of cell q from the flux nf, added to the rate grids.
-template <bool HEAT, bool MULTI>
-__device__ __forceinline__ void plane_rates_cell(size_t q, size_t nc, double path, const double (&nf)[NSED], const double *__restrict__ ndens,
-                                                 const double *__restrict__ xh_av, const double *__restrict__ xhe_av,
-                                                 const BandDataByRow *__restrict__ bdr, const SedSet &ss, const double *__restrict__ cin,
-                                                 double *__restrict__ rates, const gm::LogEntry *logtab, const gm::LogPins *pins) {
-  const BandData *const bd = bdr;
-  double u_HI, u_HeI, u_HeII;
-  plane_cell_state(ndens[q], xh_av[q], xhe_av[q], xhe_av[q + nc], u_HI, u_HeI, u_HeII);
-  const double cin_HI = cin[3 * q], cin_HeI = cin[3 * q + 1], cin_HeII = cin[3 * q + 2];
-  double cout_HI, cout_HeI, cout_HeII;
-  plane_cell_out(cin_HI, cin_HeI, cin_HeII, u_HI, u_HeI, u_HeII, path, cout_HI, cout_HeI, cout_HeII);
-  const double h_av1 = HEAT ? xh_av[q + nc] : 0.0;
-  double add[4];
-  bool lit;
-  if constexpr (HEAT && MULTI) // cross sections and factors band by band, as k_rates' three-SED heating kernel reads them
-    lit = plane_cell_rates<HEAT, MULTI>(*bdr, ss, cin_HI, cout_HI, cin_HeI, cout_HeI, cin_HeII, cout_HeII, path, nf, h_av1, u_HI, u_HeI,
-                                        u_HeII, add, logtab, pins);
-  else
-    lit = plane_cell_rates<HEAT, MULTI>(*bd, ss, cin_HI, cout_HI, cin_HeI, cout_HeI, cin_HeII, cout_HeII, path, nf, h_av1, u_HI, u_HeI,
-                                        u_HeII, add, logtab, pins);
-  if (!lit) return; // beyond max_coldensh: nothing is added
-  rates[q] = rates[q] + add[0];
-  rates[q + nc] = rates[q + nc] + add[1];
-  rates[q + 2 * nc] = rates[q + 2 * nc] + add[2];
-  if (HEAT) rates[q + 3 * nc] = rates[q + 3 * nc] + add[3];
-}
-
-template <bool HEAT, bool MULTI>
-__global__ void __launch_bounds__(BLOCK, MULTI ? (HEAT ? C2R_RATES_WAVES_HEAT_MULTI : 4) : (HEAT ? C2R_RATES_WAVES_HEAT : C2R_RATES_WAVES_ISO))
-k_plane_rates(Grid g, double path, PlaneDev pl, const double *__restrict__ ndens, const double *__restrict__ xh_av,
-              const double *__restrict__ xhe_av, const BandDataByRow *__restrict__ bdr, SedSet ss, const double *__restrict__ cin,
-              double *__restrict__ rates) {
-  const size_t nc = g.ncell;
-  __shared__ gm::LogEntry s_logtab[256];
-  s_logtab[threadIdx.x] = gm::make_log_entry((int)threadIdx.x);
-  __syncthreads();
-  gm::LogPins pins_ = {0.0, 0.0};
-  const gm::LogPins *pins = nullptr;
-  if (!HEAT) {
-    pins_ = gm::pin_log_constants();
-    pins = &pins_;
-  }
-  int i, j, k;
-  if (!plane_rates_lane(g, i, j, k)) return;
-  const size_t q = (size_t)i + (size_t)g.n1 * ((size_t)j + (size_t)g.n2 * (size_t)k);
-  plane_rates_cell<HEAT, MULTI>(q, nc, path, pl.nf, ndens, xh_av, xhe_av, bdr, ss, cin, rates, &s_logtab[0], pins);
-}
-
-// What the plane loses through the far face: lane f evaluates photo_out of the last cell of column f
-// (plane_exit_term), the block adds its 256 terms in block_sum's fixed tree; k_loss_finish then adds the block sums in
-// order.  No float atomics: the same bits every time.
-template <bool MULTI>
-__global__ void __launch_bounds__(BLOCK)
-k_plane_exit(PlaneGeom G, StepScalars sc, double path, PlaneDev pl, const BandData *__restrict__ bd, SedSet ss,
-             const double *__restrict__ cin, const double *__restrict__ exit_cols, double *__restrict__ partial) {
-  __shared__ double sh[BLOCK / 64];
-  const int face = G.fa * G.fb;
-  const int f = (int)blockIdx.x * BLOCK + (int)threadIdx.x;
-  double term = 0.0;
-  if (f < face) {
-    const size_t q = plane_cell(G, f, G.na - 1);
-    term = plane_exit_term<MULTI>(*bd, ss, cin[3 * q], exit_cols[f], cin[3 * q + 1], exit_cols[face + f], cin[3 * q + 2],
-                                  exit_cols[2 * face + f], pl.nf, sc.vol, path);
-  }
-  const double bs = block_sum(term, sh);
-  if (threadIdx.x == 0) partial[blockIdx.x] = bs;
-}
-
-// ---------------------------------------------------------------------------------------------
 // Escape maps (c2r_enable_face_loss; the rule is c2ray_face.hpp): the terms of the kept loss of an
 // open box, photo_out * vol / vol_ph of the cells on open mesh faces, kept per face cell instead of summed.
 struct FaceLayout {
@@ -1674,137 +1500,6 @@ k_horizon_rim(const SrcDev *__restrict__ src, const int *__restrict__ list, Step
   }
   const double bs = block_sum(term, sh);
   if (threadIdx.x == 0) partial[(size_t)blockIdx.y * pitch + blockIdx.x] = bs;
-}
-
-// k_plane_exit with the per-line term kept: the same terms, the same block sums, and map = map + term at the line's
-// face cell of the plane's far face (`map`: that face's map; a plane's face cells are the map's, in its order).
-template <bool MULTI>
-__global__ void __launch_bounds__(BLOCK)
-k_face_plane_exit(PlaneGeom G, StepScalars sc, double path, PlaneDev pl, const BandData *__restrict__ bd, SedSet ss,
-                 const double *__restrict__ cin, const double *__restrict__ exit_cols, double *__restrict__ partial,
-                 double *__restrict__ map) {
-  __shared__ double sh[BLOCK / 64];
-  const int face = G.fa * G.fb;
-  const int f = (int)blockIdx.x * BLOCK + (int)threadIdx.x;
-  double term = 0.0;
-  if (f < face) {
-    const size_t q = plane_cell(G, f, G.na - 1);
-    term = plane_exit_term<MULTI>(*bd, ss, cin[3 * q], exit_cols[f], cin[3 * q + 1], exit_cols[face + f], cin[3 * q + 2],
-                                  exit_cols[2 * face + f], pl.nf, sc.vol, path);
-    map[f] = map[f] + term;
-  }
-  const double bs = block_sum(term, sh);
-  if (threadIdx.x == 0) partial[blockIdx.x] = bs;
-}
-
-// ---------------------------------------------------------------------------------------------
-// Flux maps (c2r_set_plane_flux_map; the rule is c2ray_plane.hpp): the NormFlux of a plane as a
-// field over its face.  Only a plane with a map runs the kernels below; every other plane runs the ones above, as before.
-// A plane at normal incidence keeps k_plane_columns (the columns do not know the flux) and every cell of line f reads
-// map[k][f]; a tilted plane carries the flux from layer to layer with the geometric weights (plane_layer_flux) next to
-// the columns, and the rates read the flux of their own cell.
-
-// k_plane_layer with the three fluxes carried along: 12 more loads of the layer before (`fprev`: 3 x face; the map in
-// front of the first layer), the same shifted unit-stride rows as the loads of the columns, one store of 3 doubles at the
-// cell (cell_flux, 3 per cell like cin_out) and one into the next flux layer (`fnext`; the last layer's is the exit flux).
-// All three SEDs are carried whether the plane uses them or not: the loads are issued together with those of the
-// columns, and a test per SED would save none of the latency.
-__global__ void __launch_bounds__(PLANE_LAYER_BX * PLANE_LAYER_BY)
-k_pflux_layer(PlaneGeom G, PlaneTilt T, StepScalars sc, int m, size_t nc, const double *__restrict__ ndens,
-              const double *__restrict__ xh_av, const double *__restrict__ xhe_av, const float *__restrict__ lls_grid,
-              const double *__restrict__ prev, double *__restrict__ cin_out, double *__restrict__ next,
-              const double *__restrict__ fprev, double *__restrict__ cell_flux, double *__restrict__ fnext) {
-  const int u = (int)blockIdx.x * PLANE_LAYER_BX + (int)threadIdx.x, v = (int)blockIdx.y * PLANE_LAYER_BY + (int)threadIdx.y;
-  if (u >= G.fa || v >= G.fb) return;
-  double nf[NSED];
-  plane_layer_flux(T, G.fa, G.fb, u, v, fprev, nf);
-  const size_t q = plane_layer_cell(G, T, sc, m, nc, ndens, xh_av, xhe_av, lls_grid, prev, cin_out, next, u, v);
-  const int face = G.fa * G.fb, f = u + G.fa * v;
-  for (int k = 0; k < NSED; k++) {
-    cell_flux[3 * q + k] = nf[k];
-    fnext[k * face + f] = nf[k];
-  }
-}
-
-// How a mesh cell (i, j, k) finds its face cell: f = i * fi + j * fj + k * fk, the coefficients from the plane's axis
-// (run_planes forms them) -- no division beyond the tile decode.
-struct PlaneFaceIndex {
-  int fi, fj, fk;
-};
-
-// k_plane_rates with the flux of the cell's own: PERCELL = false reads map[k][f] at the cell's face cell (normal
-// incidence), PERCELL = true the three doubles k_pflux_layer left at the cell (`flux`: 3 x face or 3 per cell).  The same
-// tile, wave shape and launch bounds.  A dark cell (plane_dark) leaves after the set-up the whole wave shares.
-template <bool HEAT, bool MULTI, bool PERCELL>
-__global__ void __launch_bounds__(BLOCK, MULTI ? (HEAT ? C2R_RATES_WAVES_HEAT_MULTI : 4) : (HEAT ? C2R_RATES_WAVES_HEAT : C2R_RATES_WAVES_ISO))
-k_pflux_rates(Grid g, double path, PlaneFaceIndex fx, int face, const double *__restrict__ flux, const double *__restrict__ ndens,
-              const double *__restrict__ xh_av, const double *__restrict__ xhe_av, const BandDataByRow *__restrict__ bdr, SedSet ss,
-              const double *__restrict__ cin, double *__restrict__ rates) {
-  const size_t nc = g.ncell;
-  __shared__ gm::LogEntry s_logtab[256];
-  s_logtab[threadIdx.x] = gm::make_log_entry((int)threadIdx.x);
-  __syncthreads();
-  gm::LogPins pins_ = {0.0, 0.0};
-  const gm::LogPins *pins = nullptr;
-  if (!HEAT) {
-    pins_ = gm::pin_log_constants();
-    pins = &pins_;
-  }
-  int i, j, k;
-  if (!plane_rates_lane(g, i, j, k)) return;
-  const size_t q = (size_t)i + (size_t)g.n1 * ((size_t)j + (size_t)g.n2 * (size_t)k);
-  double nf[NSED];
-  if (PERCELL) {
-    for (int s = 0; s < NSED; s++) nf[s] = flux[3 * q + s];
-  } else {
-    const int f = i * fx.fi + j * fx.fj + k * fx.fk;
-    for (int s = 0; s < NSED; s++) nf[s] = flux[s * face + f];
-  }
-  if (plane_dark(nf)) return;
-  plane_rates_cell<HEAT, MULTI>(q, nc, path, nf, ndens, xh_av, xhe_av, bdr, ss, cin, rates, &s_logtab[0], pins);
-}
-
-// The loss term of line f with the flux of its last cell (`flux`: 3 x face -- the map at normal incidence, the exit flux
-// of a tilted plane); 0.0 for a dark cell.
-template <bool MULTI>
-__device__ double pflux_exit_term(const PlaneGeom &G, const StepScalars &sc, double path, const BandData &bd, const SedSet &ss,
-                                  const double *__restrict__ cin, const double *__restrict__ exit_cols, const double *__restrict__ flux,
-                                  int f, int face) {
-  const double nf[NSED] = {flux[f], flux[face + f], flux[2 * face + f]};
-  if (plane_dark(nf)) return 0.0;
-  const size_t q = plane_cell(G, f, G.na - 1);
-  return plane_exit_term<MULTI>(bd, ss, cin[3 * q], exit_cols[f], cin[3 * q + 1], exit_cols[face + f], cin[3 * q + 2],
-                                exit_cols[2 * face + f], nf, sc.vol, path);
-}
-
-// k_plane_exit and k_face_plane_exit for a plane with a map: the same block sums, the same map update.
-template <bool MULTI>
-__global__ void __launch_bounds__(BLOCK)
-k_pflux_exit(PlaneGeom G, StepScalars sc, double path, const double *__restrict__ flux, const BandData *__restrict__ bd, SedSet ss,
-             const double *__restrict__ cin, const double *__restrict__ exit_cols, double *__restrict__ partial) {
-  __shared__ double sh[BLOCK / 64];
-  const int face = G.fa * G.fb;
-  const int f = (int)blockIdx.x * BLOCK + (int)threadIdx.x;
-  const double term = f < face ? pflux_exit_term<MULTI>(G, sc, path, *bd, ss, cin, exit_cols, flux, f, face) : 0.0;
-  const double bs = block_sum(term, sh);
-  if (threadIdx.x == 0) partial[blockIdx.x] = bs;
-}
-
-template <bool MULTI>
-__global__ void __launch_bounds__(BLOCK)
-k_face_pflux_exit(PlaneGeom G, StepScalars sc, double path, const double *__restrict__ flux, const BandData *__restrict__ bd, SedSet ss,
-                  const double *__restrict__ cin, const double *__restrict__ exit_cols, double *__restrict__ partial,
-                  double *__restrict__ map) {
-  __shared__ double sh[BLOCK / 64];
-  const int face = G.fa * G.fb;
-  const int f = (int)blockIdx.x * BLOCK + (int)threadIdx.x;
-  double term = 0.0;
-  if (f < face) {
-    term = pflux_exit_term<MULTI>(G, sc, path, *bd, ss, cin, exit_cols, flux, f, face);
-    map[f] = map[f] + term;
-  }
-  const double bs = block_sum(term, sh);
-  if (threadIdx.x == 0) partial[blockIdx.x] = bs;
 }
 
 } // namespace
@@ -1982,24 +1677,29 @@ struct c2r_ctx {
 
   // plane-parallel sources (c2r_set_plane_sources): plane p (1-based) is "source nsrc + p" of every deal.  The buffers are
   // made by c2r_set_plane_sources and live until the planes are removed: never allocated inside a pass.
+  // What one plane owns; removing the planes frees the buffers and makes every record a Plane{} again (free_plane_buffers).
+  struct Plane {
+    c2r_plane_source src = {};
+    double tilt[2] = {0.0, 0.0};      // c2r_set_plane_tilt: tangents towards the two face axes ({0, 0}: normal incidence)
+    double *d_entry = nullptr, *d_exit = nullptr; // 3 x face each: (HI, HeI, HeII) x face cells
+    bool entry_set = false;           // entry columns were given (else zero)
+    // flux maps (c2r_set_plane_flux_map): made by the call that sets the first map of the plane, never inside a pass
+    double *d_fmap = nullptr, *d_fexit = nullptr; // 3 x face each: (SED 0, 1, 2) x face cells
+    bool fmap_set = false;            // the plane has a map (it replaces normflux[])
+    bool fmap_uses[2] = {false, false}; // some entry of SED 1 / SED 2 is non-zero (either: the three-SED routine)
+    bool fexit_valid = false;         // the last pass that ran the plane ran it with a map: d_fexit holds its exit flux
+    double loss = 0.0;                // the term the plane added to photon_loss(1) in the last pass that ran it
+    long long stamp = 0;              // ... and which pass that was (as trace_stamp)
+  };
   int nplane = 0;
-  c2r_plane_source planes[PLANE_MAX] = {};
-  double *d_plane_cin = nullptr;    // 3 ncell: the incoming columns of every cell, of the plane being run (planes run one after another)
-  double *d_plane_entry[PLANE_MAX] = {}, *d_plane_exit[PLANE_MAX] = {}; // 3 x face each: (HI, HeI, HeII) x face cells
-  bool plane_entry_set[PLANE_MAX] = {}; // entry columns were given (else zero)
-  double plane_tilt[PLANE_MAX][2] = {}; // c2r_set_plane_tilt: tangents towards the two face axes ({0, 0}: normal incidence)
+  Plane plane[PLANE_MAX];
+  // shared by the planes, which run one after another
+  double *d_plane_cin = nullptr;    // 3 ncell: the incoming columns of every cell, of the plane being run
   double *d_plane_layer[2] = {};    // 3 x the largest face each: the outgoing columns of a tilted plane's layers, used alternately
-  // flux maps (c2r_set_plane_flux_map): made by the call that sets the first map of a plane, never inside a pass
-  double *d_plane_fmap[PLANE_MAX] = {}, *d_plane_fexit[PLANE_MAX] = {}; // 3 x face each: (SED 0, 1, 2) x face cells
-  bool plane_fmap_set[PLANE_MAX] = {};   // the plane has a map (it replaces normflux[])
-  bool plane_fmap_uses[PLANE_MAX][2] = {}; // some entry of SED 1 / SED 2 is non-zero (either: the three-SED routine)
-  bool plane_fexit_valid[PLANE_MAX] = {}; // the last pass that ran the plane ran it with a map: d_plane_fexit holds its exit flux
   double *d_pflux_layer[2] = {};    // 3 x the largest face each: the flux of a tilted plane's layers, used alternately
   double *d_pflux_cell = nullptr;   // 3 ncell: the flux of every cell of the tilted plane being run
   double *d_plane_partial = nullptr; // block sums of the exit loss
   double *d_plane_loss = nullptr, *h_plane_loss = nullptr; // PLANE_MAX each (h: pinned): the exit loss of the pass in flight
-  double plane_loss[PLANE_MAX] = {}; // the term plane p added to photon_loss(1) in the last pass that ran it
-  long long plane_stamp[PLANE_MAX] = {}; // ... and which pass that was (as trace_stamp)
   std::vector<int> pass_planes;     // planes (0-based) of the pass in flight, in order
 
   // escape maps (c2r_enable_face_loss): the maps of the open faces one behind the other, in face order (face_map_offset,
@@ -2106,6 +1806,14 @@ static int for_replicas(c2r_ctx *c, F f) {
       return e;
     }
   return 0;
+}
+
+// A run-time flag as a compile-time one: f gets std::true_type or std::false_type, whose ::value picks a kernel's template
+// argument.  Nested for two or three flags.
+template <class F>
+static void with_flag(bool flag, F f) {
+  if (flag) f(std::true_type{});
+  else f(std::false_type{});
 }
 
 extern "C" const char *c2r_last_error(const c2r_ctx *c) { return c ? c->err.c_str() : "null context"; }
@@ -2385,35 +2093,7 @@ static void free_horizon_loss(c2r_ctx *c) {
   }
 }
 
-// the device and pinned buffers of the plane sources (c2r_set_plane_sources makes them, removal and c2r_destroy free them)
-static void free_plane_buffers(c2r_ctx *c) {
-  for (int p = 0; p < PLANE_MAX; p++) {
-    if (c->d_plane_entry[p]) (void)hipFree(c->d_plane_entry[p]);
-    if (c->d_plane_exit[p]) (void)hipFree(c->d_plane_exit[p]);
-    c->d_plane_entry[p] = c->d_plane_exit[p] = nullptr;
-    c->plane_entry_set[p] = false;
-    c->plane_tilt[p][0] = c->plane_tilt[p][1] = 0.0;
-    if (c->d_plane_fmap[p]) (void)hipFree(c->d_plane_fmap[p]);
-    if (c->d_plane_fexit[p]) (void)hipFree(c->d_plane_fexit[p]);
-    c->d_plane_fmap[p] = c->d_plane_fexit[p] = nullptr;
-    c->plane_fmap_set[p] = c->plane_fmap_uses[p][0] = c->plane_fmap_uses[p][1] = c->plane_fexit_valid[p] = false;
-  }
-  for (double *&b : c->d_plane_layer) {
-    if (b) (void)hipFree(b);
-    b = nullptr;
-  }
-  for (double *&b : c->d_pflux_layer) {
-    if (b) (void)hipFree(b);
-    b = nullptr;
-  }
-  if (c->d_pflux_cell) (void)hipFree(c->d_pflux_cell);
-  c->d_pflux_cell = nullptr;
-  if (c->d_plane_cin) (void)hipFree(c->d_plane_cin);
-  if (c->d_plane_partial) (void)hipFree(c->d_plane_partial);
-  if (c->d_plane_loss) (void)hipFree(c->d_plane_loss);
-  if (c->h_plane_loss) (void)hipHostFree(c->h_plane_loss);
-  c->d_plane_cin = c->d_plane_partial = c->d_plane_loss = c->h_plane_loss = nullptr;
-}
+static void free_plane_buffers(c2r_ctx *c); // c2ray_planes.inc
 
 extern "C" void c2r_destroy(c2r_ctx *c) {
   if (!c) return;
@@ -3847,10 +3527,10 @@ static int queue_face_loss(const PassCtx &P, const Batch &B) {
   for (int d = 0; d < 3; d++)
     if (L.open[d]) most = std::max(most, face_cells(L.n, d));
   const dim3 grid((unsigned)((most + BLOCK - 1) / BLOCK), 6);
-  if (P.multi)
-    hipLaunchKernelGGL(k_face_loss<true>, grid, dim3(BLOCK), 0, c->stream, L, c->d_src[B.set], B.nb, P.sc, c->d_bands, P.ss, c->d_face_maps);
-  else
-    hipLaunchKernelGGL(k_face_loss<false>, grid, dim3(BLOCK), 0, c->stream, L, c->d_src[B.set], B.nb, P.sc, c->d_bands, P.ss, c->d_face_maps);
+  with_flag(P.multi, [&](auto multi) {
+    hipLaunchKernelGGL(k_face_loss<decltype(multi)::value>, grid, dim3(BLOCK), 0, c->stream, L, c->d_src[B.set], B.nb, P.sc, c->d_bands, P.ss,
+                       c->d_face_maps);
+  });
   HIPCHK(c, hipGetLastError());
   c->tm.sweep_launches++;
   return 0;
@@ -3884,12 +3564,11 @@ static int queue_horizon_rim(const PassCtx &P, Batch &B) {
     if (ensure_pair<double>(c, &c->d_rim_partial[set], (double **)nullptr, &c->rim_partial_cap[set], need)) return 1;
   }
   HIPCHK(c, hipMemcpyAsync(c->d_rim_list[set], hl, sizeof(int) * nh, hipMemcpyHostToDevice, c->stream));
-  auto go = [&](auto kernel) {
+  with_flag(P.multi, [&](auto multi) { with_flag(!c->periodic, [&](auto open) {
+    const auto kernel = k_horizon_rim<decltype(multi)::value, decltype(open)::value>;
     hipLaunchKernelGGL(kernel, dim3((unsigned)nblk, (unsigned)nh), dim3(BLOCK), 0, c->stream, c->d_src[set], c->d_rim_list[set], P.sc,
                        c->d_bands, P.ss, c->d_rim_partial[set], nblk, c->d_rim_terms);
-  };
-  if (c->periodic) P.multi ? go(k_horizon_rim<true, false>) : go(k_horizon_rim<false, false>);
-  else P.multi ? go(k_horizon_rim<true, true>) : go(k_horizon_rim<false, true>);
+  }); });
   hipLaunchKernelGGL(k_loss_finish, dim3(nh), dim3(BLOCK), 0, c->stream, c->d_rim_partial[set], nblk, nblk, c->d_rim_acc[set]);
   HIPCHK(c, hipGetLastError());
   c->tm.sweep_launches += 2;
@@ -4107,21 +3786,13 @@ static int launch_rates(const PassCtx &P, Batch &B, bool last_batch) {
                          c->d_bands, P.ss, c->d_rates, lists ? c->d_tiles[B.set] : nullptr, lists ? c->d_tptr[B.set] : nullptr,
                          lists ? c->d_tsrc[B.set] : nullptr, base, fresh);
     };
-    if (cnt > 0 && B.beamed) { // some source of the batch has a beam or a horizon: the kernel that asks (c2r_set_source_beams, _horizons)
-      if (c->periodic) {
-        if (c->isothermal) P.multi ? go(k_rates_beam<false, true>) : go(k_rates_beam<false, false>);
-        else P.multi ? go(k_rates_beam<true, true>) : go(k_rates_beam<true, false>);
-      } else {
-        if (c->isothermal) P.multi ? go(k_rates_beam<false, true, true>) : go(k_rates_beam<false, false, true>);
-        else P.multi ? go(k_rates_beam<true, true, true>) : go(k_rates_beam<true, false, true>);
-      }
-    } else if (cnt > 0 && c->periodic) {
-      if (c->isothermal) P.multi ? go(k_rates<false, true>) : go(k_rates<false, false>);
-      else P.multi ? go(k_rates<true, true>) : go(k_rates<true, false>);
-    } else if (cnt > 0) {
-      if (c->isothermal) P.multi ? go(k_rates<false, true, true>) : go(k_rates<false, false, true>);
-      else P.multi ? go(k_rates<true, true, true>) : go(k_rates<true, false, true>);
-    }
+    if (cnt > 0)
+      with_flag(!c->isothermal, [&](auto heat) { with_flag(P.multi, [&](auto multi) { with_flag(!c->periodic, [&](auto open) {
+        constexpr bool H = decltype(heat)::value, M = decltype(multi)::value, O = decltype(open)::value;
+        // some source of the batch has a beam or a horizon: the kernel that asks (c2r_set_source_beams, _horizons)
+        if (B.beamed) go(k_rates_beam<H, M, O>);
+        else go(k_rates<H, M, O>);
+      }); }); });
     if (slabs) HIPCHK(c, hipEventRecord(c->ev_slab[piece], st));
   }
   if (pieces > 1) {
@@ -4216,167 +3887,7 @@ static std::vector<int> dealt_share(const c2r_ctx *c, int first, int stride) {
   return mine;
 }
 
-static int plane_face_cells(const c2r_ctx *c, int axis) {
-  const PlaneGeom G = plane_geometry(c->g.n1, c->g.n2, c->g.n3, axis, 0);
-  return G.fa * G.fb;
-}
-
-// The planes of a pass (0-based numbers, in order), queued on the sweep stream: columns, rates, exit loss of each, one
-// plane after the other -- they share the column scratch, and every addition to a rate grid is grid = grid + term in plane
-// order.  The rate grids must hold what they are to be added to (the caller has carried out a pending zeroing).
-static int run_planes(PassCtx &P, const std::vector<int> &planes) {
-  c2r_ctx *c = P.c;
-  const Grid &g = c->g;
-  SedSet ss = P.ss; // a plane's SEDs need the tables only, whatever the point sources use
-  for (int k = 0; k < 2; k++) {
-    const bool on = c->have_sed[k];
-    ss.photo_thick[k + 1] = on ? c->d_sed_tab[k][0] : nullptr;
-    ss.photo_thin[k + 1] = on ? c->d_sed_tab[k][1] : nullptr;
-    ss.heat_thick[k + 1] = on && c->have_sed_heat[k] ? c->d_heat_woven[k + 1][0] : nullptr;
-    ss.heat_thin[k + 1] = on && c->have_sed_heat[k] ? c->d_heat_woven[k + 1][1] : nullptr;
-    ss.lo[k + 1] = on ? c->sed_lo[k] : 0;
-    ss.hi[k + 1] = on ? c->sed_hi[k] : 0;
-  }
-  const int tiles = ((g.n1 + 7) / 8) * ((g.n2 + 7) / 8) * ((g.n3 + 3) / 4);
-  // a tilted plane (c2r_set_plane_tilt): the weights and the path from the dr of this pass, the wrap from its boundaries;
-  // refused before anything is queued where dr has changed so that the beam moves more than a cell sideways per layer
-  PlaneTilt tilt_of[PLANE_MAX] = {};
-  for (int p : planes) {
-    if (!plane_tilted(c->plane_tilt[p])) continue;
-    const double dr[3] = {P.sc.dr1, P.sc.dr2, P.sc.dr3};
-    const int per[3] = {c->per[0], c->per[1], c->per[2]};
-    tilt_of[p] = PlaneTilt(c->plane_tilt[p], dr, c->planes[p].axis, per);
-    if (!tilt_of[p].valid())
-      return fail(c, "plane %d: with the cell sizes of this pass its tilt moves the beam %g and %g cells sideways per layer, more than 1 "
-                  "(c2r_set_plane_tilt)", p + 1, tilt_of[p].a_f, tilt_of[p].a_g);
-    if (!c->d_plane_layer[0] || !c->d_plane_layer[1]) return fail(c, "plane %d: tilted, but the layer buffers are missing", p + 1);
-    if (c->plane_fmap_set[p] && (!c->d_pflux_layer[0] || !c->d_pflux_layer[1] || !c->d_pflux_cell))
-      return fail(c, "plane %d: tilted with a flux map, but the flux buffers are missing", p + 1);
-  }
-  for (int p : planes) {
-    const c2r_plane_source &pl = c->planes[p];
-    PlaneDev pd;
-    for (int s = 0; s < NSED; s++) pd.nf[s] = pl.normflux[s];
-    const bool mapped = c->plane_fmap_set[p]; // a flux map replaces normflux[] (c2r_set_plane_flux_map)
-    const bool uses[2] = {mapped ? c->plane_fmap_uses[p][0] : pd.nf[1] != 0.0, mapped ? c->plane_fmap_uses[p][1] : pd.nf[2] != 0.0};
-    const bool multi = uses[0] || uses[1];
-    for (int k = 0; k < 2; k++) {
-      if (uses[k] && !c->have_sed[k]) return fail(c, "plane %d: flux of SED %d without c2r_set_sed_tables(%d)", p + 1, k + 1, k + 1);
-      if (uses[k] && !c->isothermal && !c->have_sed_heat[k])
-        return fail(c, "plane %d: non-isothermal run needs the heating tables of SED %d", p + 1, k + 1);
-    }
-    const PlaneGeom G = plane_geometry(g.n1, g.n2, g.n3, pl.axis, pl.from_high);
-    const bool tilted = plane_tilted(c->plane_tilt[p]);
-    const PlaneTilt &T = tilt_of[p];
-    const double path = tilted ? T.path : (pl.axis == 0 ? P.sc.dr1 : (pl.axis == 1 ? P.sc.dr2 : P.sc.dr3));
-    const int face = G.fa * G.fb, fblk = (face + BLOCK - 1) / BLOCK;
-    hipEvent_t ev[3] = {};
-    for (hipEvent_t &e : ev)
-      if (c->timing && pool_event(c, &e)) return 1;
-    if (c->timing) HIPCHK(c, hipEventRecord(ev[0], c->stream));
-    const double *exit_flux = nullptr; // 3 x face: the flux of the last cell of every line of a plane with a map
-    if (tilted && mapped) { // the layers with the flux carried along; the last layer's flux is the exit flux
-      const dim3 lgrid((unsigned)((G.fa + PLANE_LAYER_BX - 1) / PLANE_LAYER_BX), (unsigned)((G.fb + PLANE_LAYER_BY - 1) / PLANE_LAYER_BY));
-      const double *prev = c->plane_entry_set[p] ? c->d_plane_entry[p] : nullptr;
-      const double *fprev = c->d_plane_fmap[p];
-      for (int m = 0; m < G.na; m++) {
-        double *next = m == G.na - 1 ? c->d_plane_exit[p] : c->d_plane_layer[m & 1];
-        double *fnext = m == G.na - 1 ? c->d_plane_fexit[p] : c->d_pflux_layer[m & 1];
-        hipLaunchKernelGGL(k_pflux_layer, lgrid, dim3(PLANE_LAYER_BX, PLANE_LAYER_BY), 0, c->stream, G, T, P.sc, m, g.ncell, c->d_ndens,
-                           c->d_xh_av, c->d_xhe_av, c->lls_on_grid ? c->d_lls : nullptr, prev, c->d_plane_cin, next, fprev, c->d_pflux_cell,
-                           fnext);
-        prev = next;
-        fprev = fnext;
-      }
-      c->tm.sweep_launches += G.na;
-      exit_flux = c->d_plane_fexit[p];
-    } else if (tilted) { // one launch per layer, in travel order; the last layer's outgoing columns are the exit columns
-      const dim3 lgrid((unsigned)((G.fa + PLANE_LAYER_BX - 1) / PLANE_LAYER_BX), (unsigned)((G.fb + PLANE_LAYER_BY - 1) / PLANE_LAYER_BY));
-      const double *prev = c->plane_entry_set[p] ? c->d_plane_entry[p] : nullptr;
-      for (int m = 0; m < G.na; m++) {
-        double *next = m == G.na - 1 ? c->d_plane_exit[p] : c->d_plane_layer[m & 1];
-        hipLaunchKernelGGL(k_plane_layer, lgrid, dim3(PLANE_LAYER_BX, PLANE_LAYER_BY), 0, c->stream, G, T, P.sc, m, g.ncell, c->d_ndens,
-                           c->d_xh_av, c->d_xhe_av, c->lls_on_grid ? c->d_lls : nullptr, prev, c->d_plane_cin, next);
-        prev = next;
-      }
-      c->tm.sweep_launches += G.na;
-    } else {
-      hipLaunchKernelGGL(k_plane_columns, dim3(fblk), dim3(BLOCK), 0, c->stream, G, P.sc, path, g.ncell, c->d_ndens, c->d_xh_av, c->d_xhe_av,
-                         c->lls_on_grid ? c->d_lls : nullptr, c->plane_entry_set[p] ? c->d_plane_entry[p] : nullptr, c->d_plane_cin,
-                         c->d_plane_exit[p]);
-      c->tm.sweep_launches++;
-      if (mapped) { // normal incidence: every cell of line f sees map[k][f], and so does the next slab
-        exit_flux = c->d_plane_fmap[p];
-        HIPCHK(c, hipMemcpyAsync(c->d_plane_fexit[p], c->d_plane_fmap[p], sizeof(double) * 3 * (size_t)face, hipMemcpyDeviceToDevice, c->stream));
-      }
-    }
-    c->plane_fexit_valid[p] = mapped;
-    if (c->timing) HIPCHK(c, hipEventRecord(ev[1], c->stream));
-    auto go = [&](auto kernel) {
-      hipLaunchKernelGGL(kernel, dim3(tiles), dim3(BLOCK), 0, c->stream, g, path, pd, c->d_ndens, c->d_xh_av, c->d_xhe_av, c->d_bands, ss,
-                         c->d_plane_cin, c->d_rates);
-    };
-    auto go_map = [&](auto kernel) { // the flux of the cell's own: the map by face cell, or what the layers left per cell
-      const PlaneFaceIndex fx = {pl.axis == 0 ? 0 : 1, pl.axis == 0 ? 1 : (pl.axis == 1 ? 0 : g.n1), pl.axis == 2 ? 0 : (pl.axis == 0 ? g.n2 : g.n1)};
-      hipLaunchKernelGGL(kernel, dim3(tiles), dim3(BLOCK), 0, c->stream, g, path, fx, face, tilted ? c->d_pflux_cell : c->d_plane_fmap[p],
-                         c->d_ndens, c->d_xh_av, c->d_xhe_av, c->d_bands, ss, c->d_plane_cin, c->d_rates);
-    };
-    if (mapped) {
-      if (c->isothermal) {
-        if (tilted) multi ? go_map(k_pflux_rates<false, true, true>) : go_map(k_pflux_rates<false, false, true>);
-        else multi ? go_map(k_pflux_rates<false, true, false>) : go_map(k_pflux_rates<false, false, false>);
-      } else {
-        if (tilted) multi ? go_map(k_pflux_rates<true, true, true>) : go_map(k_pflux_rates<true, false, true>);
-        else multi ? go_map(k_pflux_rates<true, true, false>) : go_map(k_pflux_rates<true, false, false>);
-      }
-    } else if (c->isothermal) multi ? go(k_plane_rates<false, true>) : go(k_plane_rates<false, false>);
-    else multi ? go(k_plane_rates<true, true>) : go(k_plane_rates<true, false>);
-    if (mapped) {
-      if (c->d_face_maps) {
-        const FaceLayout L = face_layout(c);
-        double *map = c->d_face_maps + face_map_offset(L.n, L.open, 2 * pl.axis + (1 - pl.from_high));
-        if (multi)
-          hipLaunchKernelGGL(k_face_pflux_exit<true>, dim3(fblk), dim3(BLOCK), 0, c->stream, G, P.sc, path, exit_flux, c->d_bands, ss,
-                             c->d_plane_cin, c->d_plane_exit[p], c->d_plane_partial, map);
-        else
-          hipLaunchKernelGGL(k_face_pflux_exit<false>, dim3(fblk), dim3(BLOCK), 0, c->stream, G, P.sc, path, exit_flux, c->d_bands, ss,
-                             c->d_plane_cin, c->d_plane_exit[p], c->d_plane_partial, map);
-      } else if (multi)
-        hipLaunchKernelGGL(k_pflux_exit<true>, dim3(fblk), dim3(BLOCK), 0, c->stream, G, P.sc, path, exit_flux, c->d_bands, ss, c->d_plane_cin,
-                           c->d_plane_exit[p], c->d_plane_partial);
-      else
-        hipLaunchKernelGGL(k_pflux_exit<false>, dim3(fblk), dim3(BLOCK), 0, c->stream, G, P.sc, path, exit_flux, c->d_bands, ss, c->d_plane_cin,
-                           c->d_plane_exit[p], c->d_plane_partial);
-    } else if (c->d_face_maps) { // escape maps: the same sum with every line's term kept, at the far face
-      const FaceLayout L = face_layout(c);
-      double *map = c->d_face_maps + face_map_offset(L.n, L.open, 2 * pl.axis + (1 - pl.from_high));
-      if (multi)
-        hipLaunchKernelGGL(k_face_plane_exit<true>, dim3(fblk), dim3(BLOCK), 0, c->stream, G, P.sc, path, pd, c->d_bands, ss, c->d_plane_cin,
-                           c->d_plane_exit[p], c->d_plane_partial, map);
-      else
-        hipLaunchKernelGGL(k_face_plane_exit<false>, dim3(fblk), dim3(BLOCK), 0, c->stream, G, P.sc, path, pd, c->d_bands, ss, c->d_plane_cin,
-                           c->d_plane_exit[p], c->d_plane_partial, map);
-    } else if (multi)
-      hipLaunchKernelGGL(k_plane_exit<true>, dim3(fblk), dim3(BLOCK), 0, c->stream, G, P.sc, path, pd, c->d_bands, ss, c->d_plane_cin,
-                         c->d_plane_exit[p], c->d_plane_partial);
-    else
-      hipLaunchKernelGGL(k_plane_exit<false>, dim3(fblk), dim3(BLOCK), 0, c->stream, G, P.sc, path, pd, c->d_bands, ss, c->d_plane_cin,
-                         c->d_plane_exit[p], c->d_plane_partial);
-    hipLaunchKernelGGL(k_loss_finish, dim3(1), dim3(BLOCK), 0, c->stream, c->d_plane_partial, fblk, fblk, c->d_plane_loss + p);
-    HIPCHK(c, hipGetLastError());
-    c->tm.rates_launches += 3;
-    if (c->timing) {
-      HIPCHK(c, hipEventRecord(ev[2], c->stream));
-      const hipEvent_t quad[4] = {ev[0], ev[1], ev[1], ev[2]}; // sweep start, sweep end, rates start, rates end (pass_finish)
-      P.tev.insert(P.tev.end(), quad, quad + 4);
-    }
-    HIPCHK(c, hipMemcpyAsync(c->h_plane_loss + p, c->d_plane_loss + p, sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    if (!c->isothermal) c->phiheat_dirty = true;
-    c->plane_stamp[p] = P.stamp;
-    c->pass_planes.push_back(p);
-  }
-  return 0;
-}
+#include "c2ray_planes.inc" // the plane kernels, run_planes, the plane buffers and the c2r_*plane* entry points
 
 // nslab > 0: the caller wants to consume the rate grids slab by slab (z ranges) while later slabs are
 // still being computed: the rates launch of the LAST batch is cut into nslab launches, an event is
@@ -4508,8 +4019,8 @@ static int pass_finish(c2r_ctx *c) {
   resolve_tails(c, 0);
   resolve_tails(c, 1);
   for (int p : c->pass_planes) { // the planes came first
-    c->plane_loss[p] = c->h_plane_loss[p];
-    c->photon_loss[0] = c->photon_loss[0] + c->plane_loss[p];
+    c->plane[p].loss = c->h_plane_loss[p];
+    c->photon_loss[0] = c->photon_loss[0] + c->plane[p].loss;
   }
   c->pass_planes.clear();
   for (const c2r_ctx::BatchTail &bt : c->tails)
@@ -4739,25 +4250,10 @@ extern "C" int c2r_evolve0d(c2r_ctx *c, const int rtpos[3], int ns, int niter, i
   source_cut(c, ns, S);
   double *dl = on_surface ? c->d_point_loss : nullptr;
   if (!c->isothermal) c->phiheat_dirty = true;
-#define C2R_LAUNCH_POINT(H, M) \
-  hipLaunchKernelGGL((k_evolve0d<H, M>), dim3(1), dim3(64), 0, c->stream, SA, S, di, dj, dk, c->d_bands, ss, c->d_rates, dl)
-#define C2R_LAUNCH_POINT_OPEN(H, M) \
-  hipLaunchKernelGGL((k_evolve0d<H, M, true>), dim3(1), dim3(64), 0, c->stream, SA, S, di, dj, dk, c->d_bands, ss, c->d_rates, dl)
-  if (c->periodic) {
-    if (c->isothermal) {
-      if (multi) C2R_LAUNCH_POINT(false, true); else C2R_LAUNCH_POINT(false, false);
-    } else {
-      if (multi) C2R_LAUNCH_POINT(true, true); else C2R_LAUNCH_POINT(true, false);
-    }
-  } else {
-    if (c->isothermal) {
-      if (multi) C2R_LAUNCH_POINT_OPEN(false, true); else C2R_LAUNCH_POINT_OPEN(false, false);
-    } else {
-      if (multi) C2R_LAUNCH_POINT_OPEN(true, true); else C2R_LAUNCH_POINT_OPEN(true, false);
-    }
-  }
-#undef C2R_LAUNCH_POINT
-#undef C2R_LAUNCH_POINT_OPEN
+  with_flag(!c->isothermal, [&](auto heat) { with_flag(multi, [&](auto three) { with_flag(!c->periodic, [&](auto open) {
+    const auto kernel = k_evolve0d<decltype(heat)::value, decltype(three)::value, decltype(open)::value>;
+    hipLaunchKernelGGL(kernel, dim3(1), dim3(64), 0, c->stream, SA, S, di, dj, dk, c->d_bands, ss, c->d_rates, dl);
+  }); }); });
   HIPCHK(c, hipGetLastError());
   if (on_surface) {
     HIPCHK(c, hipMemcpyAsync(c->h_point_loss, c->d_point_loss, sizeof(double), hipMemcpyDeviceToHost, c->stream));
@@ -5198,219 +4694,6 @@ extern "C" int c2r_set_sources(c2r_ctx *c, int nsrc, const int *srcpos, const do
 }
 
 // ---------------------------------------------------------------------------------------------
-// plane-parallel sources
-static int set_plane_sources_one(c2r_ctx *c, int nplane, const c2r_plane_source *planes) {
-  if (!c) return 1;
-  if (c->pass_open) return fail(c, "c2r_set_plane_sources: a pass opened by c2r_pass_sources_begin is still open (close it with c2r_pass_sources_end first)");
-  if (nplane < 0 || nplane > PLANE_MAX) return fail(c, "c2r_set_plane_sources: %d planes, expected 0..%d", nplane, PLANE_MAX);
-  if (nplane > 0 && !planes) return fail(c, "c2r_set_plane_sources: null argument");
-  for (int p = 0; p < nplane; p++) {
-    const c2r_plane_source &pl = planes[p];
-    if (pl.axis < 0 || pl.axis > 2) return fail(c, "c2r_set_plane_sources: plane %d: axis %d, expected 0, 1 or 2", p + 1, pl.axis);
-    if (pl.from_high != 0 && pl.from_high != 1) return fail(c, "c2r_set_plane_sources: plane %d: from_high %d, expected 0 or 1", p + 1, pl.from_high);
-    if (c->per[pl.axis])
-      return fail(c, "c2r_set_plane_sources: plane %d travels along axis %d, which is periodic (open it with c2r_set_boundaries_axes first)",
-                  p + 1, pl.axis);
-    for (int k = 0; k < NSED; k++)
-      if (!(pl.normflux[k] >= 0.0) || !std::isfinite(pl.normflux[k]))
-        return fail(c, "c2r_set_plane_sources: plane %d: normflux[%d] = %g", p + 1, k, pl.normflux[k]);
-    for (int k = 0; k < 2; k++)
-      if (pl.normflux[k + 1] != 0.0 && !c->have_sed[k])
-        return fail(c, "c2r_set_plane_sources: plane %d has a flux of SED %d, whose tables have not been set (c2r_set_sed_tables(%d))",
-                    p + 1, k + 1, k + 1);
-  }
-  HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, hipStreamSynchronize(c->stream)); // nothing queued may still use the buffers that are about to go
-  free_plane_buffers(c);
-  c->nplane = 0;
-  c->pass_planes.clear();
-  for (int p = 0; p < PLANE_MAX; p++) { c->plane_loss[p] = 0.0; c->plane_stamp[p] = 0; }
-  if (nplane == 0) return 0;
-  int face_max = 0;
-  HIPCHK(c, hipMalloc(&c->d_plane_cin, sizeof(double) * 3 * c->g.ncell));
-  for (int p = 0; p < nplane; p++) {
-    const size_t n3 = 3 * (size_t)plane_face_cells(c, planes[p].axis);
-    face_max = std::max(face_max, (int)(n3 / 3));
-    HIPCHK(c, hipMalloc(&c->d_plane_entry[p], sizeof(double) * n3));
-    HIPCHK(c, hipMalloc(&c->d_plane_exit[p], sizeof(double) * n3));
-    HIPCHK(c, zero_device(c->d_plane_exit[p], sizeof(double) * n3, c->stream));
-  }
-  HIPCHK(c, hipMalloc(&c->d_plane_partial, sizeof(double) * (size_t)((face_max + BLOCK - 1) / BLOCK)));
-  HIPCHK(c, hipMalloc(&c->d_plane_loss, sizeof(double) * PLANE_MAX));
-  HIPCHK(c, hipHostMalloc(&c->h_plane_loss, sizeof(double) * PLANE_MAX));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  std::copy(planes, planes + nplane, c->planes);
-  c->nplane = nplane;
-  return 0;
-}
-
-extern "C" int c2r_set_plane_sources(c2r_ctx *c, int nplane, const c2r_plane_source *planes) {
-  if (int e_ = set_plane_sources_one(c, nplane, planes)) return e_;
-  return for_replicas(c, [&](c2r_ctx *r) { return set_plane_sources_one(r, nplane, planes); });
-}
-
-extern "C" int c2r_get_plane_count(const c2r_ctx *c) { return c ? c->nplane : 0; }
-
-static int set_plane_entry_columns_one(c2r_ctx *c, int plane, const double *cols3) {
-  if (!c) return 1;
-  if (plane < 1 || plane > c->nplane) return fail(c, "c2r_set_plane_entry_columns: plane %d not in [1,%d]", plane, c->nplane);
-  if (c->pass_open) return fail(c, "c2r_set_plane_entry_columns: a pass opened by c2r_pass_sources_begin is still open");
-  const int p = plane - 1;
-  c->plane_entry_set[p] = false;
-  if (!cols3) return 0;
-  HIPCHK(c, hipSetDevice(c->device));
-  const size_t n3 = 3 * (size_t)plane_face_cells(c, c->planes[p].axis);
-  HIPCHK(c, hipMemcpyAsync(c->d_plane_entry[p], cols3, sizeof(double) * n3, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  c->plane_entry_set[p] = true;
-  return 0;
-}
-
-extern "C" int c2r_set_plane_entry_columns(c2r_ctx *c, int plane, const double *cols3) {
-  if (int e_ = set_plane_entry_columns_one(c, plane, cols3)) return e_;
-  return for_replicas(c, [&](c2r_ctx *r) { return set_plane_entry_columns_one(r, plane, cols3); });
-}
-
-// The buffers only a tilted plane with a flux map needs -- two flux layers for the largest face of the list and the flux
-// of every cell -- made by whichever of c2r_set_plane_tilt and c2r_set_plane_flux_map completes the pair first.
-static int ensure_pflux_buffers(c2r_ctx *c) {
-  if (c->d_pflux_cell) return 0;
-  HIPCHK(c, hipSetDevice(c->device));
-  size_t face_max = 0;
-  for (int k = 0; k < c->nplane; k++) face_max = std::max(face_max, (size_t)plane_face_cells(c, c->planes[k].axis));
-  for (double *&b : c->d_pflux_layer)
-    if (!b) HIPCHK(c, hipMalloc(&b, sizeof(double) * 3 * face_max));
-  HIPCHK(c, hipMalloc(&c->d_pflux_cell, sizeof(double) * 3 * c->g.ncell));
-  return 0;
-}
-
-static int set_plane_tilt_one(c2r_ctx *c, int plane, const double *tilt) {
-  if (!c) return 1;
-  if (plane < 1 || plane > c->nplane) return fail(c, "c2r_set_plane_tilt: plane %d not in [1,%d]", plane, c->nplane);
-  if (c->pass_open) return fail(c, "c2r_set_plane_tilt: a pass opened by c2r_pass_sources_begin is still open");
-  const int p = plane - 1;
-  const double t[2] = {tilt ? tilt[0] : 0.0, tilt ? tilt[1] : 0.0};
-  if (!std::isfinite(t[0]) || !std::isfinite(t[1])) return fail(c, "c2r_set_plane_tilt: plane %d: tilt (%g, %g) is not finite", plane, t[0], t[1]);
-  if (plane_tilted(t)) {
-    const double dr[3] = {c->sc.dr1, c->sc.dr2, c->sc.dr3};
-    const int per[3] = {c->per[0], c->per[1], c->per[2]};
-    if (!(dr[0] > 0.0 && dr[1] > 0.0 && dr[2] > 0.0))
-      return fail(c, "c2r_set_plane_tilt: the cell sizes are not set yet (c2r_set_step first: the tilt is checked against them)");
-    const PlaneTilt T(t, dr, c->planes[p].axis, per);
-    if (!T.valid())
-      return fail(c, "c2r_set_plane_tilt: plane %d: tilt (%g, %g) moves the beam %g and %g cells sideways per layer of axis %d; more than 1 "
-                  "makes another axis the dominant one (send the plane along that axis instead)", plane, t[0], t[1], T.a_f, T.a_g,
-                  c->planes[p].axis);
-    if (!c->d_plane_layer[0]) { // first tilted plane of this list: the two layer buffers, for the largest face of the list
-      HIPCHK(c, hipSetDevice(c->device));
-      size_t face_max = 0;
-      for (int k = 0; k < c->nplane; k++) face_max = std::max(face_max, (size_t)plane_face_cells(c, c->planes[k].axis));
-      for (double *&b : c->d_plane_layer) HIPCHK(c, hipMalloc(&b, sizeof(double) * 3 * face_max));
-    }
-    if (c->plane_fmap_set[p] && ensure_pflux_buffers(c)) return 1;
-  }
-  c->plane_tilt[p][0] = t[0];
-  c->plane_tilt[p][1] = t[1];
-  return 0;
-}
-
-extern "C" int c2r_set_plane_tilt(c2r_ctx *c, int plane, const double tilt[2]) {
-  if (int e_ = set_plane_tilt_one(c, plane, tilt)) return e_;
-  return for_replicas(c, [&](c2r_ctx *r) { return set_plane_tilt_one(r, plane, tilt); });
-}
-
-extern "C" int c2r_get_plane_tilt(const c2r_ctx *c, int plane, double tilt[2]) {
-  if (!c || !tilt || plane < 1 || plane > c->nplane) return 1;
-  tilt[0] = c->plane_tilt[plane - 1][0];
-  tilt[1] = c->plane_tilt[plane - 1][1];
-  return 0;
-}
-
-static int set_plane_flux_map_one(c2r_ctx *c, int plane, const double *flux3) {
-  if (!c) return 1;
-  if (plane < 1 || plane > c->nplane) return fail(c, "c2r_set_plane_flux_map: plane %d not in [1,%d]", plane, c->nplane);
-  if (c->pass_open) return fail(c, "c2r_set_plane_flux_map: a pass opened by c2r_pass_sources_begin is still open");
-  const int p = plane - 1;
-  if (!flux3) { // the plane's uniform normflux again
-    c->plane_fmap_set[p] = c->plane_fmap_uses[p][0] = c->plane_fmap_uses[p][1] = false;
-    return 0;
-  }
-  const size_t face = (size_t)plane_face_cells(c, c->planes[p].axis);
-  bool uses[2] = {false, false};
-  for (size_t i = 0; i < 3 * face; i++) {
-    if (!(flux3[i] >= 0.0) || !std::isfinite(flux3[i]))
-      return fail(c, "c2r_set_plane_flux_map: plane %d: entry %zu of SED %d is %g (a flux is finite and not negative)", plane, i % face,
-                  (int)(i / face), flux3[i]);
-    if (i >= face && flux3[i] != 0.0) uses[i / face - 1] = true;
-  }
-  for (int k = 0; k < 2; k++)
-    if (uses[k] && !c->have_sed[k])
-      return fail(c, "c2r_set_plane_flux_map: plane %d: the map has a flux of SED %d, whose tables have not been set (c2r_set_sed_tables(%d))",
-                  plane, k + 1, k + 1);
-  HIPCHK(c, hipSetDevice(c->device));
-  if (!c->d_plane_fmap[p]) HIPCHK(c, hipMalloc(&c->d_plane_fmap[p], sizeof(double) * 3 * face));
-  if (!c->d_plane_fexit[p]) HIPCHK(c, hipMalloc(&c->d_plane_fexit[p], sizeof(double) * 3 * face));
-  if (plane_tilted(c->plane_tilt[p]) && ensure_pflux_buffers(c)) return 1;
-  c->plane_fmap_set[p] = false;
-  HIPCHK(c, hipMemcpyAsync(c->d_plane_fmap[p], flux3, sizeof(double) * 3 * face, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  c->plane_fmap_set[p] = true;
-  c->plane_fmap_uses[p][0] = uses[0];
-  c->plane_fmap_uses[p][1] = uses[1];
-  return 0;
-}
-
-extern "C" int c2r_set_plane_flux_map(c2r_ctx *c, int plane, const double *flux3) {
-  if (int e_ = set_plane_flux_map_one(c, plane, flux3)) return e_;
-  return for_replicas(c, [&](c2r_ctx *r) { return set_plane_flux_map_one(r, plane, flux3); });
-}
-
-extern "C" int c2r_get_plane_flux_map_set(const c2r_ctx *c, int plane) {
-  return c && plane >= 1 && plane <= c->nplane && c->plane_fmap_set[plane - 1] ? 1 : 0;
-}
-
-// the device of the context that ran plane p (0-based) last: the deal gives a plane to one device per pass
-static c2r_ctx *plane_owner(c2r_ctx *c, int p) {
-  c2r_ctx *best = c;
-  for (c2r_ctx *r : c->replicas)
-    if (r->plane_stamp[p] > best->plane_stamp[p]) best = r;
-  return best;
-}
-
-extern "C" int c2r_download_plane_exit_columns(c2r_ctx *c, int plane, double *cols3) {
-  if (!c) return 1;
-  if (plane < 1 || plane > c->nplane || !cols3) return fail(c, "c2r_download_plane_exit_columns: plane %d not in [1,%d], or null argument", plane, c->nplane);
-  c2r_ctx *d = plane_owner(c, plane - 1);
-  HIPCHK(c, hipSetDevice(d->device));
-  const size_t n3 = 3 * (size_t)plane_face_cells(d, d->planes[plane - 1].axis);
-  HIPCHK(c, hipMemcpyAsync(cols3, d->d_plane_exit[plane - 1], sizeof(double) * n3, hipMemcpyDeviceToHost, d->stream));
-  HIPCHK(c, hipStreamSynchronize(d->stream));
-  return 0;
-}
-
-extern "C" int c2r_download_plane_exit_flux(c2r_ctx *c, int plane, double *flux3) {
-  if (!c) return 1;
-  if (plane < 1 || plane > c->nplane || !flux3) return fail(c, "c2r_download_plane_exit_flux: plane %d not in [1,%d], or null argument", plane, c->nplane);
-  if (c->pass_open) return fail(c, "c2r_download_plane_exit_flux: a pass opened by c2r_pass_sources_begin is still open");
-  c2r_ctx *d = plane_owner(c, plane - 1);
-  if (!d->plane_fexit_valid[plane - 1])
-    return fail(c, "c2r_download_plane_exit_flux: no pass has run plane %d with a flux map yet (c2r_set_plane_flux_map, then a pass)", plane);
-  HIPCHK(c, hipSetDevice(d->device));
-  const size_t n3 = 3 * (size_t)plane_face_cells(d, d->planes[plane - 1].axis);
-  HIPCHK(c, hipMemcpyAsync(flux3, d->d_plane_fexit[plane - 1], sizeof(double) * n3, hipMemcpyDeviceToHost, d->stream));
-  HIPCHK(c, hipStreamSynchronize(d->stream));
-  return 0;
-}
-
-extern "C" int c2r_get_plane_loss(c2r_ctx *c, int plane, double *loss) {
-  if (!c) return 1;
-  if (plane < 1 || plane > c->nplane || !loss) return fail(c, "c2r_get_plane_loss: plane %d not in [1,%d], or null argument", plane, c->nplane);
-  if (c->pass_open) return fail(c, "c2r_get_plane_loss: a pass opened by c2r_pass_sources_begin is still open");
-  *loss = plane_owner(c, plane - 1)->plane_loss[plane - 1];
-  return 0;
-}
-
-// ---------------------------------------------------------------------------------------------
 // escape maps
 static int enable_face_loss_one(c2r_ctx *c, int on) {
   if (!c) return 1;
@@ -5655,9 +4938,9 @@ static int set_boundaries_one(c2r_ctx *c, const int periodic[3]) {
   if (c->pass_open) return fail(c, "c2r_set_boundaries: a pass opened by c2r_pass_sources_begin is still open (close it with c2r_pass_sources_end first)");
   const bool per[3] = {periodic[0] != 0, periodic[1] != 0, periodic[2] != 0};
   for (int p = 0; p < c->nplane; p++)
-    if (per[c->planes[p].axis])
+    if (per[c->plane[p].src.axis])
       return fail(c, "c2r_set_boundaries: plane source %d travels along axis %d, which has to stay open (remove the planes with "
-                  "c2r_set_plane_sources(ctx, 0, NULL) first)", p + 1, c->planes[p].axis);
+                  "c2r_set_plane_sources(ctx, 0, NULL) first)", p + 1, c->plane[p].src.axis);
   if (per[0] == c->per[0] && per[1] == c->per[1] && per[2] == c->per[2]) return 0;
   const bool want = per[0] && per[1] && per[2];
   HIPCHK(c, hipSetDevice(c->device));

@@ -1,6 +1,6 @@
 // TEST-ONLY: plane flux maps (c2r_set_plane_flux_map; plane_layer_flux and plane_dark of
 // c2-ray3dm1d_helium_amd/csrc/c2ray_plane.hpp) compiled with the host C++ compiler, marching a whole mesh the way
-// k_plane_columns or k_pflux_layer, k_pflux_rates and k_pflux_exit do on the device, so that
+// k_plane_columns or k_plane_layer<true>, k_plane_rates and k_plane_exit do on the device for a plane with a map, so that
 // tests/test_flux_reference_host.py can hold it to the Python reference (tests/flux_reference.py) bit for bit before the
 // code reaches a GPU.  Nothing in the product links this file.
 //   g++ -O2 -ffp-contract=off -mfma -fPIC -shared -std=c++17 -o _flux_harness.so flux_harness.cpp
@@ -16,7 +16,7 @@ bool S_set[2] = {false, false};
 template <bool HEAT, bool MULTI>
 static void fx_rates(size_t nc, double path, const SedSet &ss, const double *ndens, const double *xh_av, const double *xhe_av,
                      const double *cin, const double *cell_flux, double *rates) {
-  for (size_t q = 0; q < nc; q++) { // k_pflux_rates
+  for (size_t q = 0; q < nc; q++) { // k_plane_rates<.., PlaneFlux::by_cell>
     const double nf[NSED] = {cell_flux[3 * q], cell_flux[3 * q + 1], cell_flux[3 * q + 2]};
     if (plane_dark(nf)) continue;
     double u_HI, u_HeI, u_HeII, cout_HI, cout_HeI, cout_HeII, add[4];
@@ -68,7 +68,7 @@ void fx_set_sed(int sed, const double *pthick, const double *pthin, const double
 }
 
 // Columns and fluxes of a plane with a map over a whole mesh.  Tilted: layer by layer, two alternating face buffers for the
-// columns and two for the flux (k_pflux_layer); untilted: every line on its own (k_plane_columns), the flux of a cell its
+// columns and two for the flux (k_plane_layer<true>); untilted: every line on its own (k_plane_columns), the flux of a cell its
 // line's map entry.  cin, cell_flux: 3 per cell; exit3, exit_flux: 3 x face.  Returns the number of cells not visited once.
 int fx_columns(const int *mesh, const double *dr, const double *ndens, const double *xh_av, const double *xhe_av, int axis, int from_high,
                const double *tilt, const int *periodic, int use_lls, double coldensh_lls, const float *lls_grid, const double *entry3,
@@ -172,7 +172,7 @@ int fx_march(const int *mesh, const double *dr, double vol, const double *ndens,
   else multi ? fx_rates<false, true>(nc, path, ss, ndens, xh_av, xhe_av, cin.data(), cell_flux, rates)
              : fx_rates<false, false>(nc, path, ss, ndens, xh_av, xhe_av, cin.data(), cell_flux, rates);
   const BandData &bd = T.bd;
-  for (int f = 0; f < face; f++) { // k_pflux_exit
+  for (int f = 0; f < face; f++) { // k_plane_exit<.., MAPPED>
     const double nf[NSED] = {exit_flux[f], exit_flux[face + f], exit_flux[2 * face + f]};
     if (plane_dark(nf)) { terms[f] = 0.0; continue; }
     const size_t q = plane_cell(G, f, G.na - 1);

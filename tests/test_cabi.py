@@ -6,6 +6,8 @@ from pathlib import Path
 
 import pytest
 
+from code_object import READELF, kernel_notes
+
 ROOT = Path(__file__).resolve().parent.parent
 
 
@@ -44,39 +46,18 @@ def test_no_device_fails_loudly(pkg):
 def test_product_does_not_touch_the_oracle():
     """Nothing under the package may import, link or name the oracle."""
     for p in (ROOT / "c2-ray3dm1d_helium_amd").rglob("*"):
-        if p.suffix in {".py", ".hip", ".hpp", ".h", ".F90", ".f90"}:
+        if p.suffix in {".py", ".hip", ".hpp", ".inc", ".h", ".F90", ".f90"}:
             t = p.read_text()
             assert "liboracle" not in t and "import oracle" not in t and "c2ray_oracle" not in t, p
 
 
-def test_hot_kernels_keep_nothing_in_scratch_memory(pkg, tmp_path):
+def test_hot_kernels_keep_nothing_in_scratch_memory(pkg):
     """The gfx950 code object inside the built library: the kernels of the hot path have no private segment.  (Round 3
     found 12 bytes of it in the sweep kernel -- three offsets assigned through a pointer the compiler selected at run
     time -- that a register census reports as "0 spills" and that cost 5 % of the sweep.)"""
-    import shutil
-    import struct
-    import subprocess
-    readelf = "/opt/rocm/lib/llvm/bin/llvm-readelf"
-    if not Path(readelf).exists():
+    if not Path(READELF).exists():
         pytest.skip("llvm-readelf not present")
-    blob = Path(pkg.build()).read_bytes()
-    at = blob.find(b"__CLANG_OFFLOAD_BUNDLE__")
-    assert at >= 0, "no offload bundle in the library"
-    (count,) = struct.unpack_from("<Q", blob, at + 24)
-    pos, device = at + 32, None
-    for _ in range(count):
-        off, size, tl = struct.unpack_from("<QQQ", blob, pos)
-        triple = blob[pos + 24: pos + 24 + tl].decode()
-        pos += 24 + tl
-        if "gfx950" in triple:
-            device = blob[at + off: at + off + size]
-    assert device, "no gfx950 code object in the library"
-    co = tmp_path / "device.co"
-    co.write_bytes(device)
-    notes = subprocess.run([readelf, "--notes", str(co)], capture_output=True, text=True, check=True).stdout
-    # within a kernel's map the keys are sorted: .name comes before .private_segment_fixed_size
-    pairs = re.findall(r"\.name:\s+(\S+).*?\.private_segment_fixed_size:\s+(\d+)", notes, flags=re.S)
-    seg = {name: int(size) for name, size in pairs}
+    seg = {name: v["private_segment"] for name, v in kernel_notes(pkg.build()).items()}
     hot = [n for n in seg if re.search(r"k_sweep_shell|k_chemistry|k_loss|k_pack_state|k_transpose_packed|7k_ratesILb[01]ELb[01]E", n)]
     assert len(hot) >= 12, sorted(seg)
     assert {n: seg[n] for n in hot if seg[n]} == {}
@@ -92,7 +73,8 @@ def test_no_null_stream_fills_outside_context_creation():
     end = src.index('extern "C" void c2r_destroy(')
     outside = src[:start] + src[end:]
     assert "hipMemset(" not in outside
-    assert "hipMemset(" not in (ROOT / "c2-ray3dm1d_helium_amd" / "csrc" / "c2ray_comm.inc").read_text()
+    for inc in ("c2ray_comm.inc", "c2ray_planes.inc"):
+        assert "hipMemset(" not in (ROOT / "c2-ray3dm1d_helium_amd" / "csrc" / inc).read_text()
     # inside c2r_create the fills are followed by a device synchronisation
     create = src[start:end]
     assert create.rindex("hipDeviceSynchronize()") > create.rindex("hipMemset(")

@@ -7,9 +7,6 @@ The bar is that of tests/test_gpu_plane_sources.py, whose helpers this file uses
 bit; the loss, one sum whose order differs from math.fsum's, to 1e-13 relative.  The cells are no cubes, dr = (d, 1.25 d,
 0.8 d), chosen so that the tilts of the cases stay within one cell per layer along every axis.
 """
-import re
-import struct
-import subprocess
 from pathlib import Path
 
 import numpy as np
@@ -430,31 +427,3 @@ def test_10_refusals(pkg, orc, otables, tables, gas_9):
     e.set_plane_sources([(2, 0, FLUX)])               # a new list: every tilt is {0, 0} again
     assert e.plane_tilt(1) == (0.0, 0.0)
     e.close()
-
-
-# -- 11 --------------------------------------------------------------------------------------------------------------------
-def test_11_k_plane_layer_keeps_nothing_in_scratch_memory(pkg, tmp_path):
-    """The gfx950 code object inside the built library: k_plane_layer has no private segment."""
-    readelf = "/opt/rocm/lib/llvm/bin/llvm-readelf"
-    if not Path(readelf).exists():
-        pytest.skip("llvm-readelf not present")
-    blob = Path(pkg.build()).read_bytes()
-    at = blob.find(b"__CLANG_OFFLOAD_BUNDLE__")
-    assert at >= 0, "no offload bundle in the library"
-    (count,) = struct.unpack_from("<Q", blob, at + 24)
-    pos, device = at + 32, None
-    for _ in range(count):
-        off, size, tl = struct.unpack_from("<QQQ", blob, pos)
-        triple = blob[pos + 24: pos + 24 + tl].decode()
-        pos += 24 + tl
-        if "gfx950" in triple:
-            device = blob[at + off: at + off + size]
-    assert device, "no gfx950 code object in the library"
-    co = tmp_path / "device.co"
-    co.write_bytes(device)
-    notes = subprocess.run([readelf, "--notes", str(co)], capture_output=True, text=True, check=True).stdout
-    pairs = re.findall(r"\.name:\s+(\S+).*?\.private_segment_fixed_size:\s+(\d+)", notes, flags=re.S)
-    seg = {name: int(size) for name, size in pairs if "k_plane_layer" in name}
-    print(seg)
-    assert len(seg) == 1, sorted(seg)
-    assert not any(seg.values())

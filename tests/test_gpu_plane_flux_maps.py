@@ -5,9 +5,6 @@ product's host-compiled functions to it on the CPU).  python -m pytest tests -m 
 The bar is that of tests/test_gpu_plane_sources.py, whose helpers this file uses: every grid, the exit columns and the exit
 flux bit for bit; the loss, one sum whose order differs from math.fsum's, to 1e-13 relative.
 """
-import re
-import struct
-import subprocess
 from pathlib import Path
 from types import SimpleNamespace
 
@@ -430,35 +427,3 @@ def test_9_refusals_and_lifetime(pkg, orc, otables, tables, gas_8, map_8):
     with pytest.raises(E, match="c2r_download_plane_exit_flux.*no pass"):
         e.plane_exit_flux(1)
     e.close()
-
-
-# -- 10 --------------------------------------------------------------------------------------------------------------------
-def test_10_the_map_kernels_keep_nothing_in_scratch_memory(pkg, tmp_path):
-    """The gfx950 code object inside the built library: k_pflux_layer, k_pflux_exit, k_face_pflux_exit and the isothermal
-    k_pflux_rates have no private segment; the heating instantiations are reported."""
-    readelf = "/opt/rocm/lib/llvm/bin/llvm-readelf"
-    if not Path(readelf).exists():
-        pytest.skip("llvm-readelf not present")
-    blob = Path(pkg.build()).read_bytes()
-    at = blob.find(b"__CLANG_OFFLOAD_BUNDLE__")
-    assert at >= 0, "no offload bundle in the library"
-    (count,) = struct.unpack_from("<Q", blob, at + 24)
-    pos, device = at + 32, None
-    for _ in range(count):
-        off, size, tl = struct.unpack_from("<QQQ", blob, pos)
-        triple = blob[pos + 24: pos + 24 + tl].decode()
-        pos += 24 + tl
-        if "gfx950" in triple:
-            device = blob[at + off: at + off + size]
-    assert device, "no gfx950 code object in the library"
-    co = tmp_path / "device.co"
-    co.write_bytes(device)
-    notes = subprocess.run([readelf, "--notes", str(co)], capture_output=True, text=True, check=True).stdout
-    pairs = re.findall(r"\.name:\s+(\S+).*?\.private_segment_fixed_size:\s+(\d+)", notes, flags=re.S)
-    seg = {name: int(size) for name, size in pairs if "pflux" in name}
-    print(seg)
-    cold = [n for n in seg if re.search(r"k_pflux_layer|k_pflux_exit|k_face_pflux_exit|k_pflux_ratesILb0E", n)]
-    heating = [n for n in seg if re.search(r"k_pflux_ratesILb1E", n)]
-    assert len(cold) == 1 + 2 + 2 + 4 and len(heating) == 4, sorted(seg)
-    assert {n: seg[n] for n in cold if seg[n]} == {}
-    print("private segment of the heating instantiations:", {n: seg[n] for n in heating})

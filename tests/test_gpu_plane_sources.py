@@ -8,9 +8,6 @@ Every case has a log-normal density and mixed ionisation, put into xh_av / xhe_a
 cubes (dr = d, 1.25 d, 0.75 d), so that the path, the fog's dr(1) and vol_ph each have to pick their own.
 """
 import ctypes as C
-import re
-import struct
-import subprocess
 from pathlib import Path
 from types import SimpleNamespace
 
@@ -445,35 +442,3 @@ def test_j_refusals(pkg, orc, otables, tables, gas_g):
     e.set_boundaries(True)                           # nothing stands in the way any more
     assert e.periodic is True
     e.close()
-
-
-# -- k ---------------------------------------------------------------------------------------------------------------------
-def test_k_plane_kernels_keep_nothing_in_scratch_memory(pkg, tmp_path):
-    """The gfx950 code object inside the built library: k_plane_columns, k_plane_exit and the isothermal k_plane_rates have no
-    private segment; the heating instantiations are reported."""
-    readelf = "/opt/rocm/lib/llvm/bin/llvm-readelf"
-    if not Path(readelf).exists():
-        pytest.skip("llvm-readelf not present")
-    blob = Path(pkg.build()).read_bytes()
-    at = blob.find(b"__CLANG_OFFLOAD_BUNDLE__")
-    assert at >= 0, "no offload bundle in the library"
-    (count,) = struct.unpack_from("<Q", blob, at + 24)
-    pos, device = at + 32, None
-    for _ in range(count):
-        off, size, tl = struct.unpack_from("<QQQ", blob, pos)
-        triple = blob[pos + 24: pos + 24 + tl].decode()
-        pos += 24 + tl
-        if "gfx950" in triple:
-            device = blob[at + off: at + off + size]
-    assert device, "no gfx950 code object in the library"
-    co = tmp_path / "device.co"
-    co.write_bytes(device)
-    notes = subprocess.run([readelf, "--notes", str(co)], capture_output=True, text=True, check=True).stdout
-    pairs = re.findall(r"\.name:\s+(\S+).*?\.private_segment_fixed_size:\s+(\d+)", notes, flags=re.S)
-    seg = {name: int(size) for name, size in pairs if "k_plane_" in name}
-    print(seg)
-    cold = [n for n in seg if re.search(r"k_plane_columns|k_plane_exit|k_plane_ratesILb0E", n)]
-    heating = [n for n in seg if re.search(r"k_plane_ratesILb1E", n)]
-    assert len(cold) == 5 and len(heating) == 2, sorted(seg)
-    assert {n: seg[n] for n in cold if seg[n]} == {}
-    print("private segment of the heating instantiations:", {n: seg[n] for n in heating})

@@ -6,8 +6,10 @@
 2. The product's per-cell rule (csrc/c2ray_plane.hpp) and its cell map, compiled for the host (tests/plane_harness.cpp)
    and marched over a whole mesh the way the three device kernels do, against that reference: every rate grid, the exit
    columns and every column's loss term bit for bit.
+3. The notes of the gfx950 code object: which plane kernels the library holds, and that they keep nothing in scratch memory.
 """
 import ctypes as C
+import re
 import subprocess
 from pathlib import Path
 
@@ -15,6 +17,7 @@ import numpy as np
 import pytest
 
 import plane_reference as pr
+from code_object import READELF, kernel_notes
 
 ROOT = Path(__file__).resolve().parent.parent
 ZRED = 9.0
@@ -136,3 +139,21 @@ def test_entry_columns_and_a_fog_grid(ph, orc, otables, slab):
         assert np.array_equal(got[k], ref[k]), k
     plain = pr.plane_pass(orc, otables, MESH, dr, vol, ndens, xh_av, xhe_av, 1, 1, 4.0e5, heat=True)
     assert np.all(ref["phih_grid"] < plain["phih_grid"])
+
+
+def test_plane_kernels_keep_nothing_in_scratch_memory(pkg):
+    """The gfx950 code object inside the built library (no device needed): k_plane_columns, the two k_plane_layer, the eight
+    k_plane_exit and the six isothermal k_plane_rates instantiations have no private segment; the six heating k_plane_rates
+    exist and are reported."""
+    if not Path(READELF).exists():
+        pytest.skip("llvm-readelf not present")
+    seg = {name: v["private_segment"] for name, v in kernel_notes(pkg.build()).items() if "k_plane_" in name}
+    print(seg)
+    count = lambda pattern: len([n for n in seg if re.search(pattern, n)])
+    assert count(r"15k_plane_columnsE") == 1 and count(r"13k_plane_layerILb[01]EE") == 2, sorted(seg)
+    assert count(r"12k_plane_exitILb[01]ELb[01]ELb[01]EE") == 8, sorted(seg)
+    cold = [n for n in seg if re.search(r"k_plane_columns|k_plane_layer|k_plane_exit|k_plane_ratesILb0E", n)]
+    heating = [n for n in seg if re.search(r"k_plane_ratesILb1E", n)]
+    assert len(cold) == 1 + 2 + 8 + 6 and len(heating) == 6 and len(seg) == 23, sorted(seg)
+    assert {n: seg[n] for n in cold if seg[n]} == {}
+    print("private segment of the heating instantiations:", {n: seg[n] for n in heating})

@@ -18,7 +18,6 @@ IS exact is axis (1,1,0) with cos_half = 0.5: K = 0.25 * 2 = 0.5, and on cubic c
 import ctypes as C
 import json
 import re
-import struct
 import subprocess
 from pathlib import Path
 
@@ -26,9 +25,9 @@ import numpy as np
 import pytest
 
 import beam_reference as br
+from code_object import READELF, kernel_notes
 
 ROOT = Path(__file__).resolve().parent.parent
-READELF = "/opt/rocm/lib/llvm/bin/llvm-readelf"
 HALF = 4
 D = 2.3e24                                   # a cell size of the order the test grids have, cm; no power of two
 CELLS = {"cubic": (D, D, D), "box": (D, 1.25 * D, 0.75 * D)}
@@ -162,38 +161,14 @@ def test_wall_case_has_the_columns_and_rounds_the_gpu_test_relies_on(pkg, orc, o
 
 
 # -- the code object ---------------------------------------------------------------------------------------------------------
-def kernel_notes(lib, tmp_path):
-    blob = Path(lib).read_bytes()
-    at = blob.find(b"__CLANG_OFFLOAD_BUNDLE__")
-    assert at >= 0, "no offload bundle in the library"
-    (count,) = struct.unpack_from("<Q", blob, at + 24)
-    pos, device = at + 32, None
-    for _ in range(count):
-        off, size, tl = struct.unpack_from("<QQQ", blob, pos)
-        triple = blob[pos + 24: pos + 24 + tl].decode()
-        pos += 24 + tl
-        if "gfx950" in triple:
-            device = blob[at + off: at + off + size]
-    assert device, "no gfx950 code object in the library"
-    co = tmp_path / "device.co"
-    co.write_bytes(device)
-    notes = subprocess.run([READELF, "--notes", str(co)], capture_output=True, text=True, check=True).stdout
-    out = {}
-    for t in re.split(r"\n  - (?=\.agpr_count:)", notes)[1:]:
-        g = lambda k: re.search(rf"\.{k}:\s+(\S+)", t).group(1)
-        out[g("name")] = dict(vgpr=int(g("vgpr_count")), agpr=int(g("agpr_count")), sgpr=int(g("sgpr_count")),
-                              private_segment=int(g("private_segment_fixed_size")), lds=int(g("group_segment_fixed_size")))
-    return out
-
-
-def test_rates_kernels_in_the_code_object(pkg, tmp_path):
+def test_rates_kernels_in_the_code_object(pkg):
     """k_rates_beam: eight instantiations, none with a private segment; the isothermal one-SED ones within the vector registers
     of the waves per SIMD their __launch_bounds__ asks for (512 registers per lane and SIMD, allocated in eights).  k_rates: the
     eight instantiations, each with the figures the parent commit's library has (profiles/source_beams_resources.json, 'before'),
     and the file's 'after' is what the library holds."""
     if not Path(READELF).exists():
         pytest.skip("llvm-readelf not present")
-    notes = kernel_notes(pkg.build(), tmp_path)
+    notes = kernel_notes(pkg.build())
     beam = {n: v for n, v in notes.items() if "12k_rates_beamILb" in n}
     plain = {n: v for n, v in notes.items() if "7k_ratesILb" in n}
     assert len(beam) == 8 and len(plain) == 8, sorted(notes)

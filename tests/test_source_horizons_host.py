@@ -23,7 +23,8 @@ import pytest
 import beam_reference as br
 import horizon_reference as hr
 import mix_reference as mr
-from test_source_beams_host import READELF, kernel_notes, two_source_case
+from code_object import READELF, kernel_notes
+from test_source_beams_host import two_source_case
 
 ROOT = Path(__file__).resolve().parent.parent
 HALF = 12
@@ -203,13 +204,13 @@ def test_bindings_have_the_two_calls(pkg):
     assert "int c2r_get_source_horizon(const c2r_ctx *ctx, int ns, double *radius);" in h
 
 
-def test_rates_kernels_in_the_code_object(pkg, tmp_path):
+def test_rates_kernels_in_the_code_object(pkg):
     """profiles/source_horizon_resources.json: every k_rates instantiation has the parent commit's figures ('before'), no
     k_rates_beam instantiation has a private segment or more than the 128 vector registers of the four waves per SIMD its
     __launch_bounds__ asks for, and 'after' is what the library holds."""
     if not Path(READELF).exists():
         pytest.skip("llvm-readelf not present")
-    notes = kernel_notes(pkg.build(), tmp_path)
+    notes = kernel_notes(pkg.build())
     beam = {n: v for n, v in notes.items() if "12k_rates_beamILb" in n}
     plain = {n: v for n, v in notes.items() if "7k_ratesILb" in n}
     assert len(beam) == 8 and len(plain) == 8, sorted(notes)

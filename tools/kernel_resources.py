@@ -40,6 +40,18 @@ def resources(lib: Path):
     return out
 
 
+def short_name(demangled: str) -> str:
+    """k_plane_rates<false, true, (PlaneFlux)1> of a demangled kernel signature: no namespace, return type or parameter list
+    (which opens at the first parenthesis outside the template arguments)."""
+    nm = demangled.replace("(anonymous namespace)::", "").replace("void ", "")
+    depth = 0
+    for at, ch in enumerate(nm):
+        depth += (ch == "<") - (ch == ">")
+        if ch == "(" and depth == 0:
+            return nm[:at]
+    return nm
+
+
 if __name__ == "__main__":
     args = [a for a in sys.argv[1:] if not a.startswith("--")]
     lib = ROOT / "c2-ray3dm1d_helium_amd" / "libc2ray_hip.so"
@@ -51,8 +63,7 @@ if __name__ == "__main__":
     names = subprocess.run([FILT], input="\n".join(r["name"] for r in rows), capture_output=True, text=True).stdout.splitlines()
     print(f"{'kernel':70s} vgpr agpr sgpr scratch   lds spillV spillS")
     for r, nm in zip(rows, names):
-        nm = nm.replace("(anonymous namespace)::", "").replace("void ", "")
-        nm = re.sub(r"\(.*", "", nm)
+        nm = short_name(nm)
         if pat and not pat.search(nm):
             continue
         print(f"{nm[:70]:70s} {r['vgpr']:>4} {r['agpr']:>4} {r['sgpr']:>4} {r['scratch']:>7} {r['lds']:>5} {r['spill_v']:>6} {r['spill_s']:>6}")

@@ -16,10 +16,8 @@ import argparse
 import importlib.util
 import json
 import re
-import struct
 import subprocess
 import sys
-import tempfile
 import time
 from pathlib import Path
 
@@ -28,8 +26,7 @@ import numpy as np
 ZRED = 9.0
 FLUX = 3.0e-41
 TILT = (0.35, -0.6)
-READELF = "/opt/rocm/lib/llvm/bin/llvm-readelf"
-FIELDS = ("vgpr_count", "agpr_count", "sgpr_count", "group_segment_fixed_size", "private_segment_fixed_size", "vgpr_spill_count")
+FIELDS = ("vgpr", "agpr", "sgpr", "lds", "scratch", "spill_v")  # the columns of tools/kernel_resources.py
 
 
 def load(root):
@@ -40,37 +37,15 @@ def load(root):
 
 
 def resources(pkg):
-    """{kernel name: {field: value}} of the plane kernels, from the notes of the library's gfx950 code object (metadata only)."""
-    blob = Path(pkg.build()).read_bytes()
-    at = blob.find(b"__CLANG_OFFLOAD_BUNDLE__")
-    (count,) = struct.unpack_from("<Q", blob, at + 24)
-    pos, device = at + 32, None
-    for _ in range(count):
-        off, size, tl = struct.unpack_from("<QQQ", blob, pos)
-        triple = blob[pos + 24: pos + 24 + tl].decode()
-        pos += 24 + tl
-        if "gfx950" in triple:
-            device = blob[at + off: at + off + size]
-    with tempfile.TemporaryDirectory() as d:
-        co = Path(d) / "device.co"
-        co.write_bytes(device)
-        notes = subprocess.run([READELF, "--notes", str(co)], capture_output=True, text=True, check=True).stdout
-    def demangle(n):  # _ZN...13k_pflux_ratesILb0ELb1ELb0EEEv... -> k_pflux_rates<0,1,0>
-        m = re.search(r"\d+(k_[a-z_]+)(?:I((?:Lb[01]E)+)E)?", n)
-        return m.group(1) + ("<" + ",".join(re.findall(r"Lb([01])E", m.group(2))) + ">" if m.group(2) else "") if m else n
-    out = {}
-    for block in re.split(r"\n\s+- \.agpr_count:", notes)[1:]:
-        block = ".agpr_count:" + block
-        name = re.search(r"\.name:\s+(\S+)", block)
-        if not name or not re.search(r"k_plane_|k_face_plane_exit|pflux", name.group(1)):
-            continue
-        vals = {}
-        for f in FIELDS:
-            m = re.search(r"\." + f + r":\s+(\d+)", block)
-            if m:
-                vals[f] = int(m.group(1))
-        out[demangle(name.group(1))] = vals
-    return out
+    """{kernel name: {field: value}} of the plane kernels (k_plane_columns, k_plane_layer<FLUX>, k_plane_rates<HEAT, MULTI,
+    FLUX>, k_plane_exit<MULTI, MAPPED, KEEP>; in a checkout from before they were merged also k_pflux_* and k_face_p*_exit),
+    from the notes of the library's gfx950 code object (metadata only)."""
+    sys.path.insert(0, str(Path(__file__).resolve().parent))
+    import kernel_resources as kr
+    rows = kr.resources(Path(pkg.build()))
+    names = subprocess.run([kr.FILT], input="\n".join(r["name"] for r in rows), capture_output=True, text=True).stdout.splitlines()
+    return {kr.short_name(nm): {f: int(r[f]) for f in FIELDS} for r, nm in zip(rows, names)
+            if re.search(r"k_plane_|k_face_plane_exit|pflux", r["name"])}
 
 
 def main():
