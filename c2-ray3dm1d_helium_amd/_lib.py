@@ -63,6 +63,14 @@ class SourceBeam(C.Structure):
     _fields_ = [("kind", C.c_int), ("axis", C.c_double * 3), ("cos_half", C.c_double)]
 
 
+CURVE_MAX_STEPS = 8
+
+
+class SourceCurve(C.Structure):
+    """c2r_source_curve (include/c2ray_hip.h)."""
+    _fields_ = [("nstep", C.c_int), ("radius", C.c_double * CURVE_MAX_STEPS), ("factor", C.c_double * (CURVE_MAX_STEPS + 1))]
+
+
 class SedSetup(C.Structure):
     """struct c2r_sed_setup (include/c2ray_hip.h)."""
     _fields_ = [("nfreq", C.c_int), ("sed", C.c_int), ("freq_min", _dp), ("delta_freq", _dp), ("xsec_index", _dp),
@@ -94,6 +102,8 @@ SYMBOLS = {
     "c2r_get_source_beam": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(SourceBeam)]),
     "c2r_set_source_horizons": (C.c_int, [C.c_void_p, C.c_int, _dp]),
     "c2r_get_source_horizon": (C.c_int, [C.c_void_p, C.c_int, _dp]),
+    "c2r_set_source_curves": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(SourceCurve)]),
+    "c2r_get_source_curve": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(SourceCurve)]),
     "c2r_build_tables": (C.c_int, [C.c_void_p, C.POINTER(SedSetup), C.c_int]),
     "c2r_download_tables": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, _dp, _dp]),
     "c2r_set_lls": (C.c_int, [C.c_void_p, C.c_int, C.c_double, _fp]),

@@ -1247,9 +1247,11 @@ struct SedSet {
   int lo[NSED], hi[NSED]; // 0-based first band, one past the last band; lo == hi: SED absent
 };
 
-template <bool HEAT, class LT = double, class BD = BandData>
+// NF: what NFlux[k] reads the three fluxes from -- an array of them (const double *) everywhere but in k_rates_curve's heating
+// kernel, which hands down an object that forms them where they are used (c2ray_rates_body.inc)
+template <bool HEAT, class LT = double, class BD = BandData, class NF = const double *>
 C2R_HD void photoion_rates_multi(const BD &bd, const SedSet &ss, double cin_HI, double cout_HI, double cin_HeI,
-                                 double cout_HeI, double cin_HeII, double cout_HeII, double vol, const double *NFlux,
+                                 double cout_HeI, double cin_HeII, double cout_HeII, double vol, const NF NFlux,
                                  const Ricotti &ric, PhotoOut &o, const LT *logtab = C2R_LOGTAB_DEFAULT,
                                  const gm::LogPins *pins = nullptr) {
   o.photo_HI = o.photo_HeI = o.photo_HeII = 0.0;

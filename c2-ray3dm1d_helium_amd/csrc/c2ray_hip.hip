@@ -42,6 +42,7 @@
 #include "c2ray_device.hpp"
 #include "c2ray_beam.hpp"
 #include "c2ray_horizon.hpp"
+#include "c2ray_curve.hpp"
 #include "c2ray_face.hpp"
 #include "c2ray_rim.hpp"
 #include "c2ray_plane.hpp"
@@ -85,13 +86,25 @@ struct SrcDev {
   double bax, bay, baz; // ... the beam's axis as given ...
   double bK;           // ... beam_K, cos^2 of the half opening angle times the axis's squared length (0 without a beam) ...
   double hR2;          // ... and horizon_R2, the squared radius of the horizon (+infinity without one)
+  // cut & CUT_CURVE: the source has a light curve (c2r_set_source_curves; c2ray_curve.hpp), else the tables are never read:
+  double cR2[CURVE_MAX_STEPS];      // curve_fill: the squared radii of its steps, +infinity behind the last
+  double cfac[CURVE_MAX_STEPS + 1]; // ... and the factor of each shell
 };
 // Is the cell at offset (di, dj, dk) lit by source S?  Uniform branch on S.cut (a scalar register: the record is read through
 // the scalar cache), so a source with neither beam nor horizon costs a wave one scalar compare; the loss and per-cell kernels
-// ask this beside their in-box test.  (k_rates never asks: batches with such a source run k_rates_beam.)
-__device__ __forceinline__ bool source_lights(const SrcDev &S, double dr1, double dr2, double dr3, int di, int dj, int dk) {
+// ask this beside their in-box test.  (k_rates never asks: batches with such a source run k_rates_beam or k_rates_curve.)
+// They go on to use the source's fluxes, so the answer comes with f: the factor of the cell's shell where the source has a
+// curve (c2ray_curve.hpp; a shell with f == 0.0 is unlit), 1.0 where it has none -- one more uniform branch.
+__device__ __forceinline__ bool source_flux(const SrcDev &S, double dr1, double dr2, double dr3, int di, int dj, int dk, double &f) {
+  f = 1.0;
   if (S.cut == CUT_NONE) return true;
-  return cut_lit(S.cut, S.bax, S.bay, S.baz, S.bK, S.hR2, dr1, dr2, dr3, di, dj, dk);
+  if (!(S.cut & CUT_CURVE)) return cut_lit(S.cut, S.bax, S.bay, S.baz, S.bK, S.hR2, dr1, dr2, dr3, di, dj, dk);
+  return cut_flux(S.cut, S.bax, S.bay, S.baz, S.bK, S.hR2, S.cR2, S.cfac, dr1, dr2, dr3, di, dj, dk, f);
+}
+// NormFlux, NormFluxPL or NormFluxQPL of the source as a cell in a shell of factor f sees it: one rounded product where the
+// source has a curve (uniform), the flux itself where it has none
+__device__ __forceinline__ double curve_scaled(const SrcDev &S, double nflux, double f) {
+  return (S.cut & CUT_CURVE) ? nflux * f : nflux;
 }
 // the sub-box of the round in flight: the same for every active source of a batch (all are in the same round)
 struct Box {
@@ -299,7 +312,9 @@ k_loss(Grid g, const SrcDev *__restrict__ src, const int *__restrict__ list, int
                         dk <= box.hi[2];
     const bool boundary = on_counted_face<OPEN>(box, S, di, dj, dk, MOVABLE ? 1 : 0);
     // (an unlit cell of a beamed source loses nothing: its term is 0.0, as beyond max_coldensh)
-    if (inside && boundary && source_lights(S, sc.dr1, sc.dr2, sc.dr3, di, dj, dk)) {
+    // (likewise a cell in a shell of factor 0 of a curved source; any other shell scales the source's fluxes)
+    double cf;
+    if (inside && boundary && source_flux(S, sc.dr1, sc.dr2, sc.dr3, di, dj, dk, cf)) {
       const size_t cz = S.cz;
       const size_t p = (OPEN ? (size_t)RS.off : (size_t)shell_offset(shell)) + (size_t)t;
       const global_double *cs = (const global_double *)S.cols;
@@ -317,11 +332,11 @@ k_loss(Grid g, const SrcDev *__restrict__ src, const int *__restrict__ list, int
         }
         double po;
         if (multi) {
-          const double nf[NSED] = {S.nflux, S.nflux_sed[0], S.nflux_sed[1]};
+          const double nf[NSED] = {curve_scaled(S, S.nflux, cf), curve_scaled(S, S.nflux_sed[0], cf), curve_scaled(S, S.nflux_sed[1], cf)};
           po = photo_out_multi(*bd, ss, cin_HI, cout_HI, cin_HeI, cout_HeI, cin_HeII, cout_HeII, nf);
         } else {
           po = photo_out_only(*bd, ss.photo_thick[0], ss.photo_thin[0], cin_HI, cout_HI, cin_HeI, cout_HeI, cin_HeII,
-                              cout_HeII, S.nflux);
+                              cout_HeII, curve_scaled(S, S.nflux, cf));
         }
         loss = po * sc.vol / vol_ph;
       }
@@ -670,7 +685,9 @@ k_loss_probe_rounds(Grid g, const SrcDev *__restrict__ src, const int *__restric
                         dk <= box.hi[2];
     const bool boundary = on_counted_face<OPEN>(box, S, di, dj, dk, 1);
     // (unlit cells of a beamed source are left out: terms are only ever left out, so this stays a lower bound)
-    if (inside && boundary && source_lights(S, sc.dr1, sc.dr2, sc.dr3, di, dj, dk)) {
+    // (a curved source: the terms are those of its scaled fluxes, a lower bound of the loss k_loss will find)
+    double cf;
+    if (inside && boundary && source_flux(S, sc.dr1, sc.dr2, sc.dr3, di, dj, dk, cf)) {
       const size_t cz = S.cz;
       const size_t p = (OPEN ? (size_t)RS.off : (size_t)shell_offset(shell)) + (size_t)t;
       const global_double *cs = (const global_double *)S.cols;
@@ -685,7 +702,7 @@ k_loss_probe_rounds(Grid g, const SrcDev *__restrict__ src, const int *__restric
           const double xs = sc.dr1 * (double)di, ys = sc.dr2 * (double)dj, zs = sc.dr3 * (double)dk;
           vol_ph = 4.0 * pi * (xs * xs + ys * ys + zs * zs) * path;
         }
-        const double nf[NSED] = {S.nflux, S.nflux_sed[0], S.nflux_sed[1]};
+        const double nf[NSED] = {curve_scaled(S, S.nflux, cf), curve_scaled(S, S.nflux_sed[0], cf), curve_scaled(S, S.nflux_sed[1], cf)};
         double po = 0.0;
         for (int sd = 0; sd < (multi ? NSED : 1); sd++) {
           if (!(nf[sd] > 0.0)) continue;
@@ -771,7 +788,7 @@ k_rates(Grid g, const SrcDev *__restrict__ src, int nsrc, StepScalars sc, const 
         const double *__restrict__ xh_av, const double *__restrict__ xhe_av,
         const BandDataByRow *__restrict__ bdr, SedSet ss, double *__restrict__ rates, const int *__restrict__ tiles,
         const int *__restrict__ tile_ptr, const int *__restrict__ tile_src, int tile_base, int fresh) {
-  constexpr bool BEAM = false;
+  constexpr bool BEAM = false, CURVE = false;
 #include "c2ray_rates_body.inc"
 }
 template <bool HEAT, bool MULTI, bool OPEN = false>
@@ -780,7 +797,20 @@ k_rates_beam(Grid g, const SrcDev *__restrict__ src, int nsrc, StepScalars sc, c
              const double *__restrict__ xh_av, const double *__restrict__ xhe_av,
              const BandDataByRow *__restrict__ bdr, SedSet ss, double *__restrict__ rates, const int *__restrict__ tiles,
              const int *__restrict__ tile_ptr, const int *__restrict__ tile_src, int tile_base, int fresh) {
-  constexpr bool BEAM = true;
+  constexpr bool BEAM = true, CURVE = false;
+#include "c2ray_rates_body.inc"
+}
+// CURVE (source light curves, c2ray_curve.hpp): batches that hold at least one curved source run k_rates_curve, the third
+// kernel over the same text.  What it adds to k_rates_beam: the flux of a cell.source of a curved source is a value per lane,
+// NormFlux times the factor of the cell's shell, where the two other kernels hold it in scalar registers; a source of the
+// batch without a curve takes k_rates_beam's path, scalar flux included (a uniform branch on its record).
+template <bool HEAT, bool MULTI, bool OPEN = false>
+__global__ void C2R_RATES_BOUNDS
+k_rates_curve(Grid g, const SrcDev *__restrict__ src, int nsrc, StepScalars sc, const double *__restrict__ ndens,
+              const double *__restrict__ xh_av, const double *__restrict__ xhe_av,
+              const BandDataByRow *__restrict__ bdr, SedSet ss, double *__restrict__ rates, const int *__restrict__ tiles,
+              const int *__restrict__ tile_ptr, const int *__restrict__ tile_src, int tile_base, int fresh) {
+  constexpr bool BEAM = true, CURVE = true;
 #include "c2ray_rates_body.inc"
 }
 #undef C2R_RATES_BOUNDS
@@ -1271,16 +1301,18 @@ k_evolve0d(SweepArgs A, SrcDev S, int di, int dj, int dk, const BandData *__rest
   }
   double photo_out = 0.0;
   // (the columns above are the cell's whatever the beam: an unlit cell adds no rates and loses nothing)
-  if (cin_HI < max_coldensh && source_lights(S, A.sc.dr1, A.sc.dr2, A.sc.dr3, di, dj, dk)) {
+  // (a curved source: the factor of the cell's shell scales its fluxes, and a shell of factor 0 is unlit)
+  double cf;
+  if (cin_HI < max_coldensh && source_flux(S, A.sc.dr1, A.sc.dr2, A.sc.dr3, di, dj, dk, cf)) {
     Ricotti ric = {};
     if (HEAT) ric = ricotti_parameters(h1);
     PhotoOut o;
     if (MULTI) {
-      const double nf[NSED] = {S.nflux, S.nflux_sed[0], S.nflux_sed[1]};
+      const double nf[NSED] = {curve_scaled(S, S.nflux, cf), curve_scaled(S, S.nflux_sed[0], cf), curve_scaled(S, S.nflux_sed[1], cf)};
       photoion_rates_multi<HEAT>(*bd, ss, cin_HI, cout_HI, cin_HeI, cout_HeI, cin_HeII, cout_HeII, vol_ph, nf, ric, o);
     } else {
       photoion_rates<HEAT>(*bd, ss.photo_thick[0], ss.photo_thin[0], ss.heat_thick[0], ss.heat_thin[0], cin_HI, cout_HI, cin_HeI,
-                           cout_HeI, cin_HeII, cout_HeII, vol_ph, S.nflux, ric, o);
+                           cout_HeI, cin_HeII, cout_HeII, vol_ph, curve_scaled(S, S.nflux, cf), ric, o);
     }
     rates[q] = rates[q] + o.photo_HI / (h0 * nd * (1.0 - abu_he));
     rates[q + nc] = rates[q + nc] + o.photo_HeI / (he0 * nd * abu_he);
@@ -1423,7 +1455,8 @@ k_face_loss(FaceLayout L, const SrcDev *__restrict__ src, int nsrc, StepScalars 
     const bool outside = o[0] < S.lo[0] || o[0] > S.hi[0] || o[1] < S.lo[1] || o[1] > S.hi[1] || o[2] < S.lo[2] || o[2] > S.hi[2];
     if (outside) continue;
     if (face_of_cell(L.n, L.open, m, o, dr) != face) continue;
-    if (!source_lights(S, sc.dr1, sc.dr2, sc.dr3, o[0], o[1], o[2])) continue; // the term of an unlit cell is 0.0: acc + 0.0 == acc
+    double cf; // (the factor of the cell's shell where the source has a curve)
+    if (!source_flux(S, sc.dr1, sc.dr2, sc.dr3, o[0], o[1], o[2], cf)) continue; // the term of an unlit cell is 0.0: acc + 0.0 == acc
     const size_t cz = S.cz;
     const size_t p = reach_position(S.rl, S.rr, o[0], o[1], o[2]);
     const global_double *cs = (const global_double *)S.cols;
@@ -1441,10 +1474,11 @@ k_face_loss(FaceLayout L, const SrcDev *__restrict__ src, int nsrc, StepScalars 
     }
     double po;
     if (MULTI) {
-      const double nf[NSED] = {S.nflux, S.nflux_sed[0], S.nflux_sed[1]};
+      const double nf[NSED] = {curve_scaled(S, S.nflux, cf), curve_scaled(S, S.nflux_sed[0], cf), curve_scaled(S, S.nflux_sed[1], cf)};
       po = photo_out_multi(*bd, ss, cin_HI, cout_HI, cin_HeI, cout_HeI, cin_HeII, cout_HeII, nf);
     } else {
-      po = photo_out_only(*bd, ss.photo_thick[0], ss.photo_thin[0], cin_HI, cout_HI, cin_HeI, cout_HeI, cin_HeII, cout_HeII, S.nflux);
+      po = photo_out_only(*bd, ss.photo_thick[0], ss.photo_thin[0], cin_HI, cout_HI, cin_HeI, cout_HeI, cin_HeII, cout_HeII,
+                          curve_scaled(S, S.nflux, cf));
     }
     acc = acc + po * sc.vol / vol_ph;
     touched = true;
@@ -1477,7 +1511,14 @@ k_horizon_rim(const SrcDev *__restrict__ src, const int *__restrict__ list, Step
   if (rim_decode(S.lo, S.hi, t, fc, oa, ob)) {
     int k, o0, o1, o2;
     double w;
-    if (rim_column(S.cut, S.bax, S.bay, S.baz, S.bK, S.hR2, sc.dr1, sc.dr2, sc.dr3, S.lo, S.hi, fc, oa, ob, k, o0, o1, o2, w)) {
+    // (a curved source: the face cell's own factor scales the fluxes of its po; a cell in a shell of factor 0 has no face)
+    double cf = 1.0;
+    bool face = rim_column(S.cut, S.bax, S.bay, S.baz, S.bK, S.hR2, sc.dr1, sc.dr2, sc.dr3, S.lo, S.hi, fc, oa, ob, k, o0, o1, o2, w);
+    if (face && (S.cut & CUT_CURVE)) {
+      cf = curve_factor_at(S.cR2, S.cfac, sc.dr1, sc.dr2, sc.dr3, o0, o1, o2);
+      face = cf != 0.0;
+    }
+    if (face) {
       const size_t cz = S.cz;
       const size_t p = OPEN ? reach_position(S.rl, S.rr, o0, o1, o2) : shell_position(o0, o1, o2);
       if (p < cz) { // (an interior cell of the final box: the block holds its shell)
@@ -1487,10 +1528,11 @@ k_horizon_rim(const SrcDev *__restrict__ src, const int *__restrict__ list, Step
         if (cin_HI < max_coldensh) {
           double po;
           if (MULTI) {
-            const double nf[NSED] = {S.nflux, S.nflux_sed[0], S.nflux_sed[1]};
+            const double nf[NSED] = {curve_scaled(S, S.nflux, cf), curve_scaled(S, S.nflux_sed[0], cf), curve_scaled(S, S.nflux_sed[1], cf)};
             po = photo_out_multi(*bd, ss, cin_HI, cout_HI, cin_HeI, cout_HeI, cin_HeII, cout_HeII, nf);
           } else {
-            po = photo_out_only(*bd, ss.photo_thick[0], ss.photo_thin[0], cin_HI, cout_HI, cin_HeI, cout_HeI, cin_HeII, cout_HeII, S.nflux);
+            po = photo_out_only(*bd, ss.photo_thick[0], ss.photo_thin[0], cin_HI, cout_HI, cin_HeI, cout_HeI, cin_HeII, cout_HeII,
+                                curve_scaled(S, S.nflux, cf));
           }
           term = po * w;
         }
@@ -1569,6 +1611,9 @@ struct c2r_ctx {
   // c2r_set_source_horizons: one radius per source as it was given, and horizon_R2 of each (empty: no source has a horizon)
   std::vector<double> horizons;
   std::vector<double> horizon_r2;
+  // c2r_set_source_curves: one record per source as it was given, the entries behind its steps zeroed (empty: no source has
+  // a curve)
+  std::vector<c2r_source_curve> curves;
 
   double *d_xh = nullptr, *d_xhe = nullptr, *d_xh_av = nullptr, *d_xhe_av = nullptr, *d_xh_int = nullptr,
          *d_xhe_int = nullptr;
@@ -2415,6 +2460,7 @@ static int set_sources_one(c2r_ctx *c, int nsrc, const int *srcpos, const double
   c->beam_k.clear();
   c->horizons.clear();
   c->horizon_r2.clear();
+  c->curves.clear();
   forget_horizon_loss(c);
   return 0;
 }
@@ -2512,7 +2558,47 @@ static int set_source_horizons_one(c2r_ctx *c, int nsrc, const double *radius) {
   return 0;
 }
 
-// the beam and the horizon of source ns (1-based) in its device record
+// a curve that leaves the source as it is: no step, factor 1.0
+static bool curve_is_none(const c2r_source_curve &v) { return v.nstep == 0 && v.factor[0] == 1.0; }
+
+// c2r_set_source_curves on one device: everything is checked before anything is kept
+static int set_source_curves_one(c2r_ctx *c, int nsrc, const c2r_source_curve *curves) {
+  if (!c) return 1;
+  if (c->pass_open) return fail(c, "c2r_set_source_curves: a pass opened by c2r_pass_sources_begin is still open");
+  if (nsrc != c->nsrc) return fail(c, "c2r_set_source_curves: nsrc = %d, but c2r_set_sources gave %d sources", nsrc, c->nsrc);
+  if (!curves) {
+    c->curves.clear();
+    return 0;
+  }
+  std::vector<c2r_source_curve> kept((size_t)nsrc);
+  for (int s = 0; s < nsrc; s++) {
+    const c2r_source_curve &v = curves[s];
+    if (v.nstep < 0 || v.nstep > C2R_CURVE_MAX_STEPS)
+      return fail(c, "c2r_set_source_curves: source %d: nstep = %d not in [0,%d]", s + 1, v.nstep, C2R_CURVE_MAX_STEPS);
+    for (int k = 0; k < v.nstep; k++) {
+      if (!(v.radius[k] >= 0.0) || !std::isfinite(v.radius[k])) // (a NaN fails every comparison)
+        return fail(c, "c2r_set_source_curves: source %d: radius[%d] = %g is negative or not finite", s + 1, k, v.radius[k]);
+      if (k > 0 && !(v.radius[k] > v.radius[k - 1]))
+        return fail(c, "c2r_set_source_curves: source %d: radius[%d] = %g is not above radius[%d] = %g", s + 1, k, v.radius[k], k - 1,
+                    v.radius[k - 1]);
+    }
+    for (int k = 0; k <= v.nstep; k++)
+      if (!(v.factor[k] >= 0.0) || !std::isfinite(v.factor[k]))
+        return fail(c, "c2r_set_source_curves: source %d: factor[%d] = %g is negative or not finite", s + 1, k, v.factor[k]);
+    // an all-zero record is a record nobody filled in, not a source that has gone dark (that is {1, {0.0}, {0.0, 0.0}})
+    if (v.nstep == 0 && v.factor[0] == 0.0)
+      return fail(c, "c2r_set_source_curves: source %d: nstep = 0 and factor[0] = 0 (a zeroed record); no curve is factor[0] = 1", s + 1);
+    c2r_source_curve &o = kept[(size_t)s];
+    o = c2r_source_curve{};
+    o.nstep = v.nstep;
+    for (int k = 0; k < v.nstep; k++) o.radius[k] = v.radius[k];
+    for (int k = 0; k <= v.nstep; k++) o.factor[k] = v.factor[k];
+  }
+  c->curves.swap(kept);
+  return 0;
+}
+
+// the beam, the horizon and the curve of source ns (1-based) in its device record
 static void source_cut(const c2r_ctx *c, int ns, SrcDev &S) {
   S.cut = CUT_NONE;
   S.bax = S.bay = S.baz = S.bK = 0.0;
@@ -2530,6 +2616,10 @@ static void source_cut(const c2r_ctx *c, int ns, SrcDev &S) {
     S.cut |= CUT_HORIZON;
     S.hR2 = c->horizon_r2[(size_t)ns - 1];
   }
+  const c2r_source_curve none = {0, {}, {1.0}};
+  const c2r_source_curve &v = c->curves.empty() ? none : c->curves[(size_t)ns - 1];
+  curve_fill(v.nstep, v.radius, v.factor, S.cR2, S.cfac);
+  if (!curve_is_none(v)) S.cut |= CUT_CURVE;
 }
 
 // The per-frequency vectors of k_build_tables, with the host versions of the bit-exact exp / pow:
@@ -3063,6 +3153,7 @@ struct Batch {
   bool sweep_started = false;       // ev[0] goes in front of the first shell launch, behind the uploads of records and lists
   int ntiles = 0;                   // tiles in the rates launch's list h_tiles[set] (0: none, every tile of the mesh)
   bool beamed = false;              // some source of the batch has a beam or a finite horizon: its rates launch is k_rates_beam
+  bool curved = false;              // some source of the batch has a curve: its rates launch is k_rates_curve
   std::vector<int> rim_ns;          // horizon loss: the sources (1-based) whose sums queue_horizon_rim has queued, in row order
 };
 
@@ -3187,6 +3278,7 @@ static int place_batch(const PassCtx &P, const std::vector<int> &mine, Batch &B)
   SrcDev *hs = c->h_src[set];
   B.run.assign((size_t)B.nb, SrcRun());
   B.beamed = false;
+  B.curved = false;
   for (bool released = false;;) {
     c->seg_cur[set] = 0;
     c->seg_used[set] = 0;
@@ -3252,6 +3344,7 @@ static int place_batch(const PassCtx &P, const std::vector<int> &mine, Batch &B)
     for (int k = 0; k < 2; k++) S.nflux_sed[k] = c->normflux_sed[k].empty() ? 0.0 : c->normflux_sed[k][r.ns - 1];
     source_cut(c, r.ns, S);
     B.beamed = B.beamed || S.cut != CUT_NONE;
+    B.curved = B.curved || (S.cut & CUT_CURVE) != 0;
   }
   // coldensh_out = 0 for every new source (evolve_source.F90:94-95) serves two purposes in the
   // reference: the "already done" marker (replaced here by the shell order: every cell is visited
@@ -3790,7 +3883,9 @@ static int launch_rates(const PassCtx &P, Batch &B, bool last_batch) {
       with_flag(!c->isothermal, [&](auto heat) { with_flag(P.multi, [&](auto multi) { with_flag(!c->periodic, [&](auto open) {
         constexpr bool H = decltype(heat)::value, M = decltype(multi)::value, O = decltype(open)::value;
         // some source of the batch has a beam or a horizon: the kernel that asks (c2r_set_source_beams, _horizons)
-        if (B.beamed) go(k_rates_beam<H, M, O>);
+        // ... or a curve: the kernel whose flux is a value per lane (c2r_set_source_curves)
+        if (B.curved) go(k_rates_curve<H, M, O>);
+        else if (B.beamed) go(k_rates_beam<H, M, O>);
         else go(k_rates<H, M, O>);
       }); }); });
     if (slabs) HIPCHK(c, hipEventRecord(c->ev_slab[piece], st));
@@ -4887,6 +4982,23 @@ extern "C" int c2r_get_source_horizon(const c2r_ctx *c, int ns, double *radius) 
     return 1;
   }
   *radius = c->horizons.empty() ? (double)INFINITY : c->horizons[(size_t)ns - 1];
+  return 0;
+}
+
+extern "C" int c2r_set_source_curves(c2r_ctx *c, int nsrc, const c2r_source_curve *curves) {
+  if (int e_ = set_source_curves_one(c, nsrc, curves)) return e_;
+  return for_replicas(c, [&](c2r_ctx *r) { return set_source_curves_one(r, nsrc, curves); });
+}
+
+extern "C" int c2r_get_source_curve(const c2r_ctx *c, int ns, c2r_source_curve *out) {
+  if (!c || !out) return 1;
+  if (ns < 1 || ns > c->nsrc) {
+    c->err = "c2r_get_source_curve: source " + std::to_string(ns) + " not in [1," + std::to_string(c->nsrc) + "]";
+    return 1;
+  }
+  *out = c2r_source_curve{};
+  out->factor[0] = 1.0;
+  if (!c->curves.empty()) *out = c->curves[(size_t)ns - 1];
   return 0;
 }
 

@@ -1,7 +1,8 @@
-// The body of k_rates and of k_rates_beam (c2ray_hip.hip), included into both kernels after `constexpr bool BEAM`: what
-// the second kernel adds is compiled under `if constexpr (BEAM)`, and k_rates stays, statement for statement, the kernel it
-// was before beams existed (register figures of both: profiles/source_beams_resources.json).  Not a function: a body that
-// reaches the kernel through a call, even an inlined one, costs the isothermal kernel two vector registers.
+// The body of k_rates, of k_rates_beam and of k_rates_curve (c2ray_hip.hip), included into each kernel after `constexpr bool
+// BEAM, CURVE`: what the second kernel adds is compiled under `if constexpr (BEAM)`, what the third adds to the second under
+// `if constexpr (CURVE)`, and k_rates stays the kernel it was before beams existed, k_rates_beam the one it was before curves
+// did (register figures: profiles/source_beams_resources.json, profiles/source_curves_resources.json).  Not a function: a
+// body that reaches the kernel through a call, even an inlined one, costs the isothermal kernel two vector registers.
   const size_t nc = g.ncell;
   // One block = a tile of 8 x 8 x 4 cells, one wave = a 4 x 4 x 4 cube of it.  Neighbouring cells see
   // similar optical depths: the lanes of a cube mostly take the same branch of the bit-exact log (its
@@ -85,6 +86,9 @@
   // the three denominators of the cell and its four running sums, touched once per source: [den_HI, den_HeI, den_HeII,
   // a_HI, a_HeI, a_HeII, a_heat] x BLOCK (each lane reads back only what it wrote itself: no barrier)
   __shared__ double s_den[PARK ? 7 * BLOCK : 1];
+  // k_rates_curve: and the flux factor of the cell for the source in hand, one per lane (likewise read back only by the lane
+  // that wrote it)
+  [[maybe_unused]] __shared__ double s_flux[PARK && CURVE ? BLOCK : 1];
   if (PARK) {
     s_den[threadIdx.x] = den_HI;
     s_den[BLOCK + threadIdx.x] = den_HeI;
@@ -121,8 +125,17 @@
     // cell is a cell the source does not reach.  One thing remains to do for it: where the rates launch leaves the terms
     // of the kept loss behind (S.loss_lo >= 0), an unlit cell of the counted surface leaves its term, 0.0, in the N_in(HI)
     // slot that k_loss_stored will read.
-    if constexpr (BEAM) { // (k_rates_beam only)
-      if (S.cut != CUT_NONE && !cut_lit(S.cut, S.bax, S.bay, S.baz, S.bK, S.hR2, sc.dr1, sc.dr2, sc.dr3, di, dj, dk)) {
+    // A source with a curve (k_rates_curve; S.cut & CUT_CURVE, uniform): cut_flux asks the same and also finds cf, the factor
+    // of the cell's shell, a value per lane that lives until the source's fluxes are formed below; a shell of factor 0 is unlit.
+    [[maybe_unused]] double cf = 1.0;
+    if constexpr (BEAM) { // (k_rates_beam and k_rates_curve only)
+      bool unlit;
+      if constexpr (CURVE)
+        unlit = S.cut != CUT_NONE && !((S.cut & CUT_CURVE) ? cut_flux(S.cut, S.bax, S.bay, S.baz, S.bK, S.hR2, S.cR2, S.cfac, sc.dr1, sc.dr2, sc.dr3, di, dj, dk, cf)
+                                                           : cut_lit(S.cut, S.bax, S.bay, S.baz, S.bK, S.hR2, sc.dr1, sc.dr2, sc.dr3, di, dj, dk));
+      else
+        unlit = S.cut != CUT_NONE && !cut_lit(S.cut, S.bax, S.bay, S.baz, S.bK, S.hR2, sc.dr1, sc.dr2, sc.dr3, di, dj, dk);
+      if (unlit) {
         if (!HEAT && S.loss_lo >= 0) {
           const int ia = di < 0 ? -di : di, ja = dj < 0 ? -dj : dj, ka = dk < 0 ? -dk : dk;
           const int shell = ia > ja ? (ia > ka ? ia : ka) : (ja > ka ? ja : ka);
@@ -153,13 +166,32 @@
     // photoion_rates and the sums of this cell; with_loss: also return photo_out, which the kernel otherwise never
     // forms (one addition per band, registers that stay alive through the band loop, scalar registers short
     // enough already: 4 % of the launch when every wave pays it) -- two copies of the code, chosen per wave below
-    auto rates_of_source = [&](auto with_loss) -> double {
+    // per_lane (k_rates_curve, a curved source): the fluxes are the source's times cf, one rounded product per SED held in
+    // vector registers; otherwise they are the scalar registers they always were
+    auto rates_of_flux = [&](auto with_loss, auto per_lane) -> double {
+      constexpr bool LANE = CURVE && decltype(per_lane)::value;
+      auto flux = [&](const double nflux) -> double {
+        if constexpr (LANE) return nflux * cf;
+        else return nflux;
+      };
       double photo_out = 0.0;
       if (cin_HI < max_coldensh) {
         PhotoOut o;
         if (MULTI) {
-          const double nf[NSED] = {S.nflux, S.nflux_sed[0], S.nflux_sed[1]};
-          if constexpr (HEAT) // this kernel reads cross sections and factors band by band (BandDataByRow)
+          const double nf[NSED] = {flux(S.nflux), flux(S.nflux_sed[0]), flux(S.nflux_sed[1])};
+          if constexpr (HEAT && LANE) {
+            // The parked kernel has no six vector registers for three fluxes per lane: cf waits in LDS, and each flux is
+            // formed where it is used -- the same rounded product every time (volatile: read there, not hoisted).
+            struct LaneFlux {
+              const SrcDev &S;
+              volatile __attribute__((address_space(3))) double *cf;
+              __device__ double operator[](int k) const { return (k == 0 ? S.nflux : (k == 1 ? S.nflux_sed[0] : S.nflux_sed[1])) * *cf; }
+            };
+            volatile __attribute__((address_space(3))) double *const pf = (volatile __attribute__((address_space(3))) double *)&s_flux[threadIdx.x];
+            *pf = cf;
+            photoion_rates_multi<HEAT>(*bdr, ss, cin_HI, cout_HI, cin_HeI, cout_HeI, cin_HeII, cout_HeII,
+                                       vol_ph, LaneFlux{S, pf}, ric, o, &s_logtab[0], pins);
+          } else if constexpr (HEAT) // this kernel reads cross sections and factors band by band (BandDataByRow)
             photoion_rates_multi<HEAT>(*bdr, ss, cin_HI, cout_HI, cin_HeI, cout_HeI, cin_HeII, cout_HeII,
                                        vol_ph, nf, ric, o, &s_logtab[0], pins);
           else
@@ -167,7 +199,7 @@
         } else {
           // gathers first (band_positions_gathers_first) where the registers allow it: the isothermal kernel
           photoion_rates<HEAT, gm::LogEntry, BandData, !HEAT>(*bd, ss.photo_thick[0], ss.photo_thin[0], ss.heat_thick[0], ss.heat_thin[0], cin_HI, cout_HI,
-                                                                   cin_HeI, cout_HeI, cin_HeII, cout_HeII, vol_ph, S.nflux, ric, o, &s_logtab[0], pins);
+                                                                   cin_HeI, cout_HeI, cin_HeII, cout_HeII, vol_ph, flux(S.nflux), ric, o, &s_logtab[0], pins);
         }
         if (PARK) { // (volatile: read here, not hoisted back into registers)
           volatile __attribute__((address_space(3))) double *dn = (volatile __attribute__((address_space(3))) double *)&s_den[threadIdx.x];
@@ -186,6 +218,17 @@
         // rates are zero: x + 0.0 == x
       }
       return photo_out;
+    };
+    // (a uniform branch: a source without a curve in a curved batch takes k_rates_beam's code)
+    auto rates_of_source = [&](auto with_loss) -> double {
+      // (The three-SED heating kernel has no room for two copies of its band loops -- with both it needs a private segment,
+      // 16 to 32 bytes -- so there every source of a curved batch takes the per-lane copy, an uncurved one with cf = 1.0:
+      // x*1.0 == x, the same bits.)
+      if constexpr (CURVE && HEAT && MULTI) return rates_of_flux(with_loss, std::true_type{});
+      if constexpr (CURVE) {
+        if (S.cut & CUT_CURVE) return rates_of_flux(with_loss, std::true_type{});
+      }
+      return rates_of_flux(with_loss, std::false_type{});
     };
     // evolve_point.F90:310-315: a cell on the surface of the (final) sub-box loses photo_out * vol / vol_ph photons
     // through it.  For a source whose last round ended for geometric reasons (SrcDev::loss_lo >= 0) that loss is

@@ -410,6 +410,37 @@ class HipEngine:
         self._chk(self.lib.c2r_get_source_horizon(self.h, int(ns), C.byref(r)))
         return float(r.value)
 
+    def set_source_curves(self, curves=None):
+        """c2r_set_source_curves: one light curve per point source, in source order -- None (no curve) or (radii, factors):
+        up to 8 radii, physical lengths in the length unit of dr, strictly ascending, and one factor more than radii, factors[b]
+        the flux factor of distance shell b ([0, r0], (r0, r1], ..., beyond the last radius).  curves=None: no source has a
+        curve.  set_sources clears the curves."""
+        if curves is None:
+            self._chk(self.lib.c2r_set_source_curves(self.h, int(self.nsrc), None))
+            return
+        curves = list(curves)
+        arr = (_lib.SourceCurve * max(len(curves), 1))()
+        for rec, c in zip(arr, curves):
+            rec.factor[0] = 1.0
+            if c is None:
+                continue
+            radii, factors = [float(r) for r in c[0]], [float(f) for f in c[1]]
+            if len(factors) != len(radii) + 1:
+                raise ValueError(f"a curve of {len(radii)} radii takes {len(radii) + 1} factors, not {len(factors)}")
+            rec.nstep = len(radii)                 # (more than 8: the library refuses the call, the record holds the first 8)
+            for k, r in enumerate(radii[:_lib.CURVE_MAX_STEPS]):
+                rec.radius[k] = r
+            for k, f in enumerate(factors[:_lib.CURVE_MAX_STEPS + 1]):
+                rec.factor[k] = f
+        self._chk(self.lib.c2r_set_source_curves(self.h, len(curves), arr))
+
+    def source_curve(self, ns):
+        """c2r_get_source_curve for source `ns` (1-based): (radii, factors) as it was set, ([], [1.0]) while it has none."""
+        c = _lib.SourceCurve()
+        self._chk(self.lib.c2r_get_source_curve(self.h, int(ns), C.byref(c)))
+        n = int(c.nstep)
+        return [float(c.radius[k]) for k in range(n)], [float(c.factor[k]) for k in range(n + 1)]
+
     def upload_state(self, mat: Material):
         xh, xhe = _f64(mat.xh).reshape(-1), _f64(mat.xhe).reshape(-1)
         assert xh.size == 2 * self.ncell and xhe.size == 3 * self.ncell

@@ -69,6 +69,15 @@ module c2ray_hip
      real(c_double) :: cos_half
   end type c2r_source_beam
 
+  !> c2r_source_curve of include/c2ray_hip.h: the light curve of one point source -- nstep ascending radii (physical lengths in
+  !> the unit of dr) and the flux factor of each of the nstep + 1 distance shells; nstep = 0 and factor(1) = 1: no curve
+  integer(c_int), parameter :: C2R_CURVE_MAX_STEPS = 8
+  type, bind(C) :: c2r_source_curve
+     integer(c_int) :: nstep
+     real(c_double) :: radius(C2R_CURVE_MAX_STEPS)
+     real(c_double) :: factor(C2R_CURVE_MAX_STEPS + 1)
+  end type c2r_source_curve
+
   !> c2r_sed_setup of include/c2ray_hip.h: what spec_integration starts from for one SED
   type, bind(C) :: c2r_sed_setup
      integer(c_int) :: nfreq, sed
@@ -217,6 +226,22 @@ module c2ray_hip
        integer(c_int), value :: ns
        real(c_double), intent(out) :: radius
      end function c2r_get_source_horizon
+
+     !> light curves: c_loc of NumSrc records of type(c2r_source_curve), or c_null_ptr: no source has a curve
+     integer(c_int) function c2r_set_source_curves(ctx, nsrc, curves) bind(C, name="c2r_set_source_curves")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: ctx
+       integer(c_int), value :: nsrc
+       type(c_ptr), value :: curves
+     end function c2r_set_source_curves
+
+     !> the curve of source ns (1-based) as it was set; nstep = 0 and factor(1) = 1 while it has none
+     integer(c_int) function c2r_get_source_curve(ctx, ns, curve) bind(C, name="c2r_get_source_curve")
+       import :: c_int, c_ptr, c2r_source_curve
+       type(c_ptr), value :: ctx
+       integer(c_int), value :: ns
+       type(c2r_source_curve), intent(out) :: curve
+     end function c2r_get_source_curve
 
      integer(c_int) function c2r_build_tables(ctx, setup, with_heat) bind(C, name="c2r_build_tables")
        import :: c_int, c_ptr, c2r_sed_setup

@@ -213,6 +213,65 @@ int c2r_get_source_beam(const c2r_ctx *ctx, int ns, c2r_source_beam *out);
 int c2r_set_source_horizons(c2r_ctx *ctx, int nsrc, const double *radius);
 int c2r_get_source_horizon(const c2r_ctx *ctx, int ns, double *radius);
 
+/* Source light curves: a flux factor per shell of distance, per point source.  A cell at distance r sees a source at the
+ * retarded time t - r/c, and the light-crossing time of a large box is many time steps: a host that knows a source's history
+ * (a galaxy whose emissivity grows, a quasar that flickers or has switched off, a burst) hands it over as a piecewise-constant
+ * curve, radius[k] = c*(t - t_k) and factor = L(t_k)/L(t).  A horizon is the crudest such curve: 1 within the sphere, 0 beyond.
+ *   nstep     the number of steps, 0 .. C2R_CURVE_MAX_STEPS
+ *   radius    radius[0..nstep-1]: physical lengths in the length unit of dr (a pass uses the dr of that pass, as for a
+ *             horizon), finite, >= 0 and strictly ascending
+ *   factor    factor[0..nstep]: finite and >= 0; factor[b] holds in distance shell b.  The shells are [0, r0], (r0, r1], ...,
+ *             (r_{nstep-1}, infinity)
+ * Entries behind nstep (radius) and nstep + 1 (factor) mean nothing and are not looked at.
+ * The rule (csrc/c2ray_curve.hpp).  When the curves are set the host forms R2[k] = radius[k]*radius[k] for k < nstep.  For a
+ * cell at offset (di, dj, dk) from the source -- the offset exactly as the kernel in question already forms it, as for a beam
+ * -- and the dr of the pass, every product and sum rounded as written and evaluated from the left (the horizon's own xs, ys,
+ * zs, d2):
+ *     xs = dr1*(double)di    ys = dr2*(double)dj    zs = dr3*(double)dk
+ *     d2 = (xs*xs + ys*ys) + zs*zs
+ *     b  = the number of k < nstep with d2 > R2[k]
+ *     f  = factor[b]
+ * No square root and no division: a cell exactly on a radius belongs to the inner shell, and the source's own cell is always
+ * shell 0.
+ * A cell with f == 0.0 is UNLIT for that source, in exactly the sense of c2r_set_source_beams: it adds nothing to phih, phihe
+ * or phiheat, and its loss term photo_out*vol/vol_ph is 0.0 in the loss that decides whether the sub-box grows, in the loss
+ * that is kept, in photon_loss(1), in the escape maps and in the horizon rim (the po of a rim face is formed with the face
+ * cell's scaled flux; a cell with f = 0 has no face).  Any other cell runs the per-cell routine the source always ran, with the
+ * same columns and vol_ph, and NormFlux*f in the place of NormFlux -- in a three-SED run NormFluxPL*f and NormFluxQPL*f as
+ * well: one rounded product per SED and nothing else, so f == 1.0 gives the uncurved bits.  A source with a beam, a horizon
+ * and a curve lights a cell iff it is lit for each of them.
+ * What a curve does not do.  Columns are swept as before.  The threshold 1e-10 * total_source_flux of the sub-box loop uses
+ * the unscaled fluxes; sum_nbox, reaches, column blocks and tile lists are untouched.  Planes are untouched.  Nothing is
+ * rescaled to conserve anything.
+ * Identities.
+ *   Curves off: with none set, or every source nstep = 0 and factor[0] = 1.0, every grid, loss, map and sum_nbox has the bits
+ *     it had before curves existed, from the same kernel launches.
+ *   All factors 1.0: the uncurved bits, through the curved kernel.
+ *   Step to zero: {1, {R}, {1, 0}} is the horizon R bit for bit, rounds included.
+ *   A factor 2^n scales phih, phihe, phiheat and the loss terms of its shell exactly.
+ * c2r_set_source_curves gives all NumSrc sources their curves at once (nsrc must equal the NumSrc of c2r_set_sources); curves
+ * = NULL: no source has a curve.  A source with nstep == 0 and factor[0] == 1.0 has no curve.  c2r_set_sources clears the
+ * curves; c2r_set_boundaries*, c2r_set_source_beams and c2r_set_source_horizons keep them.  The curves act on every device of
+ * a multi-device context, and every route that traces a point source honours them: c2r_pass_sources and its slab-wise form,
+ * c2r_do_source, c2r_pass_allreduce_chemistry, c2r_iteration, c2r_evolve3d, c2r_evolve0d, the escape maps and the horizon
+ * loss.
+ * Refused, each with an error text: a call between c2r_pass_sources_begin and c2r_pass_sources_end; nsrc != NumSrc; an nstep
+ * outside 0..C2R_CURVE_MAX_STEPS; a radius that is negative, not finite or not above its predecessor; a factor that is
+ * negative or not finite; and a ZEROED RECORD (nstep == 0 and factor[0] == 0.0).  By the rule that record is a source that
+ * lights nothing, which is not what a record nobody filled in should do, and reading it as "no curve" would make factor[0]
+ * = 0 the one factor that does not scale: so it is refused, "no curve" is factor[0] = 1.0, and a source that has gone dark
+ * is {1, {0.0}, {0.0, 0.0}}.  A refused call changes nothing.
+ * c2r_get_source_curve returns the curve of source ns (1-based) as it was set, the entries behind its steps zeroed, and {0, {},
+ * {1.0}} while none is set; an ns outside 1..NumSrc is refused with an error text. */
+#define C2R_CURVE_MAX_STEPS 8
+typedef struct {
+  int nstep;
+  double radius[C2R_CURVE_MAX_STEPS];
+  double factor[C2R_CURVE_MAX_STEPS + 1];
+} c2r_source_curve;
+int c2r_set_source_curves(c2r_ctx *ctx, int nsrc, const c2r_source_curve *curves);
+int c2r_get_source_curve(const c2r_ctx *ctx, int ns, c2r_source_curve *out);
+
 /* Horizon loss: what crosses each source's photon horizon, per source.  The rule (csrc/c2ray_rim.hpp).  The cells within a
  * horizon are a closed staircase around the source whose boundary is made of cell faces; the solid angles of those faces add up
  * to 4 pi, so a weight per exposed face, taken at the face centre, tiles the sphere: summed over a box that contains the
