@@ -565,11 +565,23 @@ C2R_HD TauPos tau_table_position(double tau, const double *logtab = C2R_LOGTAB_D
 // straight line -- their loads and dependent fma chains overlap --, and the polynomial path of __log_fma
 // (arguments near 1: one in ten, spatially coherent) is entered only when some lane of the wave needs it.
 // The table comes in two forms, told apart by its type: (invc, logc) pairs (const double *) or the 256 entries with
-// the power of two folded in (const gm::LogEntry *; k_rates keeps that one in LDS).  (A third, with log10's two
-// products of its own power of two tabulated per exponent as well -- 17 KB more LDS, three instructions fewer per
-// logarithm -- was measured: 19.4 against 18.2 ms per launch; six more live registers cost the fifth wave per SIMD.)
+// the power of two folded in (const gm::LogEntry *; k_rates keeps that one in LDS).  A third form brings a second table
+// along (const gm::LogEntryExp *): log10's two products of its own power of two, tabulated per exponent (gm::Log10Exp,
+// 17 KB more LDS, three FP64-rate instructions fewer and one integer one more per logarithm).  Only the isothermal one-SED
+// k_rates uses it, and only together with its denominators parked in LDS: on top of the 93 registers of that kernel the
+// two pairs cost four more (97: one wave per SIMD less, and the register budget of tests/test_rates_registers.py gone),
+// and an earlier build of that kind measured 19.4 against 18.2 ms per launch -- a loss that was put down to the fifth
+// wave without proof (3, 4 and 5 waves run within 0.5 % of each other) and was never looked into.  With the denominators
+// out of the way the kernel has 92 registers and 31.8 KB of LDS (five blocks per compute unit) and runs about 0.2 ms per
+// launch (1 %) faster than without the table, a third of what the instruction count promises ("Exponent
+// table").
 C2R_HD double log_table_path_of(const gm::Log10Arg &a, const double *tab, const gm::LogPins *pins) { return gm::log_table_path(a, tab, pins); }
 C2R_HD double log_table_path_of(const gm::Log10Arg &a, const gm::LogEntry *tab, const gm::LogPins *pins) { return gm::log_table_path4(a, tab, pins); }
+C2R_HD double log_table_path_of(const gm::Log10Arg &a, const gm::LogEntryExp *tab, const gm::LogPins *pins) { return gm::log_table_path4(a, tab->tab, pins); }
+// __ieee754_log10's tail: with the exponent terms computed, or read from the table that a gm::LogEntryExp brings along
+C2R_HD double log10_finish_of(const gm::Log10Arg &a, double lg, const double *) { return gm::log10_finish(a, lg); }
+C2R_HD double log10_finish_of(const gm::Log10Arg &a, double lg, const gm::LogEntry *) { return gm::log10_finish(a, lg); }
+C2R_HD double log10_finish_of(const gm::Log10Arg &a, double lg, const gm::LogEntryExp *tab) { return gm::log10_finish(a, lg, tab->exp); }
 
 template <class LT>
 C2R_HD void tau_table_positions(double tau_a, double tau_b, const LT *logtab, TauPos &pa, TauPos &pb,
@@ -584,8 +596,8 @@ C2R_HD void tau_table_positions(double tau_a, double tau_b, const LT *logtab, Ta
     if (na) lga = gm::log_near1(gm::log10_arg_value(a));
     if (nb) lgb = gm::log_near1(gm::log10_arg_value(b));
   }
-  pa = table_position_of_log(gm::log10_finish(a, lga));
-  pb = table_position_of_log(gm::log10_finish(b, lgb));
+  pa = table_position_of_log(log10_finish_of(a, lga, logtab));
+  pb = table_position_of_log(log10_finish_of(b, lgb, logtab));
 }
 #else
 C2R_HD TauPos tau_table_position(double tau, const double * = nullptr) {

@@ -285,6 +285,37 @@ C2R_MHD double log10_finish(const Log10Arg &a, double lg) {
   const double zz = y * log10_2lo + ivln10 * lg;
   return zz + y * log10_2hi;
 }
+// The same tail with its exponent terms tabulated.  y = (double)ky and the two products y*log10_2lo, y*log10_2hi depend on
+// the integer ky alone: a table indexed by ky holds the pair, filled by the very multiplications it replaces
+// (make_log10_exp), and the tail is left with its two additions and the product ivln10*lg -- no fma, two roundings each,
+// as the generic build of e_log10.c has them.  ky of a positive normal double that is at least 1e-20 lies in [-66, 1023];
+// the table covers [-67, 1024], so that +inf (ky = 1024, which max(tau, 1e-20) lets through) reads an entry as well.
+struct Log10Exp {
+  double ylo, yhi; // y*log10_2lo, y*log10_2hi
+};
+constexpr int LOG10_KY_LO = -67, LOG10_KY_HI = 1024, LOG10_NEXP = LOG10_KY_HI - LOG10_KY_LO + 1;
+C2R_MHD Log10Exp make_log10_exp(int ky) {
+  const double log10_2hi = asdouble(0x3FD34413509F6000ULL);
+  const double log10_2lo = asdouble(0x3D59FEF311F12B36ULL);
+  const double y = (double)ky;
+  Log10Exp e;
+  e.ylo = y * log10_2lo;
+  e.yhi = y * log10_2hi;
+  return e;
+}
+// `xt`: entry 0 is ky = LOG10_KY_LO; precondition LOG10_KY_LO <= a.ky <= LOG10_KY_HI
+C2R_MHD double log10_finish(const Log10Arg &a, double lg, const Log10Exp *xt) {
+  const double ivln10 = asdouble(0x3FDBCB7B1526E50EULL);
+  const Log10Exp *e = (const Log10Exp *)((const char *)xt + ((uint32_t)(a.ky - LOG10_KY_LO) << 4));
+  const double ylo = e->ylo, yhi = e->yhi;
+  const double zz = ylo + ivln10 * lg;
+  return zz + yhi;
+}
+// both tables of a kernel that keeps them in LDS: a type of its own, by which tau_table_positions chooses this tail
+struct LogEntryExp {
+  const LogEntry *tab;
+  const Log10Exp *exp;
+};
 // log10_norm: the caller guarantees a positive, normal, finite argument (tau_table_position passes
 // max(1e-20, tau)); log10_pos adds the check and falls back to log10_.
 C2R_MHD double log10_norm(double x, const double *tab) {

@@ -19,7 +19,18 @@
   // gathers per band iteration that no longer queue behind the photo-table gathers in the vector memory path
   __shared__ gm::LogEntry s_logtab[256];
   s_logtab[threadIdx.x] = gm::make_log_entry((int)threadIdx.x);
+  // k_rates, isothermal, one SED (ISO1; its beam and curve twins stay the kernels they were): the exponent terms of
+  // log10's tail are read from a table (gm::Log10Exp, 17 KB) that each block fills here with the multiplications the table
+  // replaces -- per band six FP64-rate instructions less and two integer ones more -- and the four registers that the two
+  // pairs need come from the cell's denominators, which wait in LDS (below)
+  constexpr bool ISO1 = !HEAT && !MULTI && !BEAM;
+  constexpr bool EXPT = ISO1;
+  __shared__ gm::Log10Exp s_exptab[EXPT ? gm::LOG10_NEXP : 1];
+  if constexpr (EXPT) {
+    for (int e = (int)threadIdx.x; e < gm::LOG10_NEXP; e += BLOCK) s_exptab[e] = gm::make_log10_exp(gm::LOG10_KY_LO + e);
+  }
   __syncthreads();
+  [[maybe_unused]] const gm::LogEntryExp logx = {&s_logtab[0], &s_exptab[0]};
   // the band data as uploaded (a BandDataByRow: the plain arrays and, behind them, the same numbers band by band); a kernel
   // chooses its reading of them by the TYPE it hands down -- the base for the array form (an upcast, not a reinterpretation)
   const BandData *const bd = bdr;
@@ -85,7 +96,13 @@
   constexpr bool PARK = HEAT && MULTI;
   // the three denominators of the cell and its four running sums, touched once per source: [den_HI, den_HeI, den_HeII,
   // a_HI, a_HeI, a_HeII, a_heat] x BLOCK (each lane reads back only what it wrote itself: no barrier)
-  __shared__ double s_den[PARK ? 7 * BLOCK : 1];
+  // The isothermal one-SED k_rates parks its three denominators the same way (PARK_DEN): 93 -> 88 registers, which the
+  // exponent table's two pairs bring to 92.  Its running sums stay in registers: parked as well they free nothing more (88
+  // either way), and their 6 KB would not fit beside the tables.
+  constexpr bool PARK_DEN = ISO1;
+  __shared__ double s_den[PARK ? 7 * BLOCK : (PARK_DEN ? 3 * BLOCK : 1)];
+  // five blocks of this kernel per compute unit (160 KB of LDS): at most 32 KB each
+  static_assert(!ISO1 || sizeof(s_logtab) + sizeof(s_exptab) + sizeof(s_den) <= 32768, "k_rates: LDS for five blocks per compute unit");
   // k_rates_curve: and the flux factor of the cell for the source in hand, one per lane (likewise read back only by the lane
   // that wrote it)
   [[maybe_unused]] __shared__ double s_flux[PARK && CURVE ? BLOCK : 1];
@@ -97,6 +114,11 @@
     s_den[4 * BLOCK + threadIdx.x] = a_HeI;
     s_den[5 * BLOCK + threadIdx.x] = a_HeII;
     s_den[6 * BLOCK + threadIdx.x] = a_heat;
+  }
+  if constexpr (PARK_DEN) {
+    s_den[threadIdx.x] = den_HI;
+    s_den[BLOCK + threadIdx.x] = den_HeI;
+    s_den[2 * BLOCK + threadIdx.x] = den_HeII;
   }
   bool touched = false;
   const int slot = tile_base + vb;
@@ -198,8 +220,12 @@
             photoion_rates_multi<HEAT>(*bd, ss, cin_HI, cout_HI, cin_HeI, cout_HeI, cin_HeII, cout_HeII, vol_ph, nf, ric, o, &s_logtab[0], pins);
         } else {
           // gathers first (band_positions_gathers_first) where the registers allow it: the isothermal kernel
-          photoion_rates<HEAT, gm::LogEntry, BandData, !HEAT>(*bd, ss.photo_thick[0], ss.photo_thin[0], ss.heat_thick[0], ss.heat_thin[0], cin_HI, cout_HI,
-                                                                   cin_HeI, cout_HeI, cin_HeII, cout_HeII, vol_ph, flux(S.nflux), ric, o, &s_logtab[0], pins);
+          if constexpr (EXPT)
+            photoion_rates<HEAT, gm::LogEntryExp, BandData, !HEAT>(*bd, ss.photo_thick[0], ss.photo_thin[0], ss.heat_thick[0], ss.heat_thin[0], cin_HI, cout_HI,
+                                                                      cin_HeI, cout_HeI, cin_HeII, cout_HeII, vol_ph, flux(S.nflux), ric, o, &logx, pins);
+          else
+            photoion_rates<HEAT, gm::LogEntry, BandData, !HEAT>(*bd, ss.photo_thick[0], ss.photo_thin[0], ss.heat_thick[0], ss.heat_thin[0], cin_HI, cout_HI,
+                                                                     cin_HeI, cout_HeI, cin_HeII, cout_HeII, vol_ph, flux(S.nflux), ric, o, &s_logtab[0], pins);
         }
         if (PARK) { // (volatile: read here, not hoisted back into registers)
           volatile __attribute__((address_space(3))) double *dn = (volatile __attribute__((address_space(3))) double *)&s_den[threadIdx.x];
@@ -207,6 +233,11 @@
           dn[4 * BLOCK] = dn[4 * BLOCK] + o.photo_HeI / dn[BLOCK];
           dn[5 * BLOCK] = dn[5 * BLOCK] + o.photo_HeII / dn[2 * BLOCK];
           dn[6 * BLOCK] = dn[6 * BLOCK] + o.heat;
+        } else if constexpr (PARK_DEN) { // (likewise)
+          volatile __attribute__((address_space(3))) double *dn = (volatile __attribute__((address_space(3))) double *)&s_den[threadIdx.x];
+          a_HI = a_HI + o.photo_HI / dn[0];
+          a_HeI = a_HeI + o.photo_HeI / dn[BLOCK];
+          a_HeII = a_HeII + o.photo_HeII / dn[2 * BLOCK];
         } else {
           a_HI = a_HI + o.photo_HI / den_HI;
           a_HeI = a_HeI + o.photo_HeI / den_HeI;
