@@ -71,6 +71,15 @@ class SourceCurve(C.Structure):
     _fields_ = [("nstep", C.c_int), ("radius", C.c_double * CURVE_MAX_STEPS), ("factor", C.c_double * (CURVE_MAX_STEPS + 1))]
 
 
+PLANE_CURVE_MAX_STEPS = 8
+
+
+class PlaneCurve(C.Structure):
+    """c2r_plane_curve (include/c2ray_hip.h)."""
+    _fields_ = [("nstep", C.c_int), ("layer0", C.c_int), ("depth0", C.c_double), ("depth", C.c_double * PLANE_CURVE_MAX_STEPS),
+                ("factor", C.c_double * (PLANE_CURVE_MAX_STEPS + 1))]
+
+
 class SedSetup(C.Structure):
     """struct c2r_sed_setup (include/c2ray_hip.h)."""
     _fields_ = [("nfreq", C.c_int), ("sed", C.c_int), ("freq_min", _dp), ("delta_freq", _dp), ("xsec_index", _dp),
@@ -153,6 +162,8 @@ SYMBOLS = {
     "c2r_set_plane_flux_map": (C.c_int, [C.c_void_p, C.c_int, _dp]),
     "c2r_get_plane_flux_map_set": (C.c_int, [C.c_void_p, C.c_int]),
     "c2r_download_plane_exit_flux": (C.c_int, [C.c_void_p, C.c_int, _dp]),
+    "c2r_set_plane_curve": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(PlaneCurve)]),
+    "c2r_get_plane_curve": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(PlaneCurve)]),
     "c2r_enable_face_loss": (C.c_int, [C.c_void_p, C.c_int]),
     "c2r_get_face_loss_enabled": (C.c_int, [C.c_void_p]),
     "c2r_download_face_loss": (C.c_int, [C.c_void_p, C.c_int, _dp]),

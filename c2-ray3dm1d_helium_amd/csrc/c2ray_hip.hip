@@ -46,6 +46,7 @@
 #include "c2ray_face.hpp"
 #include "c2ray_rim.hpp"
 #include "c2ray_plane.hpp"
+#include "c2ray_pcurve.hpp"
 #include "c2ray_shell.hpp"
 
 using namespace c2r;
@@ -1733,6 +1734,9 @@ struct c2r_ctx {
     bool fmap_set = false;            // the plane has a map (it replaces normflux[])
     bool fmap_uses[2] = {false, false}; // some entry of SED 1 / SED 2 is non-zero (either: the three-SED routine)
     bool fexit_valid = false;         // the last pass that ran the plane ran it with a map: d_fexit holds its exit flux
+    // c2r_set_plane_curve: the curve as it was given, the entries behind its steps zeroed (curve_set false: none, no path changes)
+    c2r_plane_curve curve = {0, 0, 0.0, {}, {1.0}};
+    bool curve_set = false;
     double loss = 0.0;                // the term the plane added to photon_loss(1) in the last pass that ran it
     long long stamp = 0;              // ... and which pass that was (as trace_stamp)
   };

@@ -9,6 +9,7 @@
 //   the rates   k_plane_rates     no dependencies, one lane per cell; the flux uniform, by face cell or by cell (PlaneFlux)
 //   the loss    k_plane_exit      what leaves through the far face; the flux of a map or uniform (MAPPED), the per-line
 //                                 term also kept in the escape map of that face (KEEP, c2r_enable_face_loss)
+// A plane with a light curve (c2r_set_plane_curve, c2ray_pcurve.hpp) runs k_pcurve_rates and k_pcurve_exit for the last two.
 namespace {
 
 struct PlaneDev {
@@ -220,6 +221,109 @@ k_plane_exit(PlaneGeom G, StepScalars sc, double path, PlaneDev pl, const double
   if (threadIdx.x == 0) partial[blockIdx.x] = bs;
 }
 
+// Plane light curves (c2r_set_plane_curve; the rule is c2ray_pcurve.hpp): a plane with a curve runs the two kernels below in
+// the place of k_plane_rates and k_plane_exit, behind the same march.
+
+// plane_rates_cell for the three-SED heating kernel of a curved plane: the same statements, the fluxes a PlaneCurveFlux
+// (each product formed where the band loops use it, not kept in registers through them).
+__device__ __forceinline__ void pcurve_rates_cell_heat3(size_t q, size_t nc, double path, const PlaneCurveFlux &nf, const double *__restrict__ ndens,
+                                                        const double *__restrict__ xh_av, const double *__restrict__ xhe_av,
+                                                        const BandDataByRow *__restrict__ bdr, const SedSet &ss, const double *__restrict__ cin,
+                                                        double *__restrict__ rates, const gm::LogEntry *logtab) {
+  double u_HI, u_HeI, u_HeII;
+  plane_cell_state(ndens[q], xh_av[q], xhe_av[q], xhe_av[q + nc], u_HI, u_HeI, u_HeII);
+  const double cin_HI = cin[3 * q], cin_HeI = cin[3 * q + 1], cin_HeII = cin[3 * q + 2];
+  double cout_HI, cout_HeI, cout_HeII;
+  plane_cell_out(cin_HI, cin_HeI, cin_HeII, u_HI, u_HeI, u_HeII, path, cout_HI, cout_HeI, cout_HeII);
+  double add[4];
+  if (!plane_cell_rates<true, true>(*bdr, ss, cin_HI, cout_HI, cin_HeI, cout_HeI, cin_HeII, cout_HeII, path, nf, xh_av[q + nc], u_HI, u_HeI,
+                                    u_HeII, add, logtab, nullptr))
+    return; // beyond max_coldensh: nothing is added
+  rates[q] = rates[q] + add[0];
+  rates[q + nc] = rates[q + nc] + add[1];
+  rates[q + 2 * nc] = rates[q + 2 * nc] + add[2];
+  rates[q + 3 * nc] = rates[q + 3 * nc] + add[3];
+}
+
+// k_plane_rates for a plane with a curve: the same tile, the same cube per wave, the same table in LDS.  A cube spans four
+// layers whatever the axis, so the factor f -- and with it the fluxes -- is a value per lane: each lane finds its layer from
+// its own (i, j, k) (PlaneLayerIndex), forms f by curve_factor's compares and selects on the record `cv` (a kernel argument:
+// scalar registers, read at constant places) and leaves where its layer is unlit (f == 0.0) or its unscaled fluxes are dark.
+// Then one rounded product per SED and plane_rates_cell, as ever.  The three-SED heating kernel forms each product where it
+// is used instead (pcurve_rates_cell_heat3).
+template <bool HEAT, bool MULTI, PlaneFlux FLUX>
+__global__ void __launch_bounds__(BLOCK, MULTI ? (HEAT ? C2R_RATES_WAVES_HEAT_MULTI : 4) : (HEAT ? C2R_RATES_WAVES_HEAT : C2R_RATES_WAVES_ISO))
+k_pcurve_rates(Grid g, double path, PlaneDev pl, PlaneFaceIndex fx, int face, const double *__restrict__ flux, PlaneCurveDev cv,
+               PlaneLayerIndex lx, const double *__restrict__ ndens, const double *__restrict__ xh_av, const double *__restrict__ xhe_av,
+               const BandDataByRow *__restrict__ bdr, SedSet ss, const double *__restrict__ cin, double *__restrict__ rates) {
+  const size_t nc = g.ncell;
+  __shared__ gm::LogEntry s_logtab[256];
+  s_logtab[threadIdx.x] = gm::make_log_entry((int)threadIdx.x);
+  __syncthreads();
+  gm::LogPins pins_ = {0.0, 0.0};
+  const gm::LogPins *pins = nullptr;
+  if (!HEAT) {
+    pins_ = gm::pin_log_constants();
+    pins = &pins_;
+  }
+  // the tile decode: the cell (i, j, k) of this lane
+  const int ti = (g.n1 + 7) >> 3, tj = (g.n2 + 7) >> 3;
+  const int tile = (int)blockIdx.x;
+  const int bi = tile % ti, bj = (tile / ti) % tj, bk = tile / (ti * tj);
+  const int lane = threadIdx.x & 63;
+  const int w_ = threadIdx.x >> 6;
+  const int i = bi * 8 + (w_ & 1) * 4 + (lane & 3), j = bj * 8 + (w_ >> 1) * 4 + ((lane >> 2) & 3), k = bk * 4 + (lane >> 4);
+  if (!(i < g.n1 && j < g.n2 && k < g.n3)) return;
+  const double cf = pcurve_factor(cv, pcurve_layer(lx, i, j, k), path);
+  if (cf == 0.0) return; // an unlit layer
+  const size_t q = (size_t)i + (size_t)g.n1 * ((size_t)j + (size_t)g.n2 * (size_t)k);
+  double nfu[NSED]; // the unscaled fluxes
+  if constexpr (FLUX == PlaneFlux::uniform) {
+    for (int s = 0; s < NSED; s++) nfu[s] = pl.nf[s];
+  } else if constexpr (FLUX == PlaneFlux::by_cell) {
+    for (int s = 0; s < NSED; s++) nfu[s] = flux[3 * q + s];
+  } else {
+    const int f = i * fx.fi + j * fx.fj + k * fx.fk;
+    for (int s = 0; s < NSED; s++) nfu[s] = flux[s * face + f];
+  }
+  if (plane_dark(nfu)) return;
+  if constexpr (HEAT && MULTI) {
+    pcurve_rates_cell_heat3(q, nc, path, PlaneCurveFlux{nfu[0], nfu[1], nfu[2], cf}, ndens, xh_av, xhe_av, bdr, ss, cin, rates, &s_logtab[0]);
+  } else {
+    double nf[NSED];
+    pcurve_fluxes(nfu, cf, nf);
+    plane_rates_cell<HEAT, MULTI>(q, nc, path, nf, ndens, xh_av, xhe_av, bdr, ss, cin, rates, &s_logtab[0], pins);
+  }
+}
+
+// k_plane_exit for a plane with a curve: `cf` is the factor of the last layer (the host forms it with the function the lanes of
+// k_pcurve_rates use).  The same terms with nf*cf for nf, 0.0 for an unlit last layer or a dark line; the same block sums,
+// the same k_loss_finish behind it, the same map = map + term.
+template <bool MULTI, bool MAPPED, bool KEEP>
+__global__ void __launch_bounds__(BLOCK)
+k_pcurve_exit(PlaneGeom G, StepScalars sc, double path, PlaneDev pl, const double *__restrict__ flux, double cf,
+              const BandData *__restrict__ bd, SedSet ss, const double *__restrict__ cin, const double *__restrict__ exit_cols,
+              double *__restrict__ partial, double *__restrict__ map) {
+  __shared__ double sh[BLOCK / 64];
+  const int face = G.fa * G.fb;
+  const int f = (int)blockIdx.x * BLOCK + (int)threadIdx.x;
+  double term = 0.0;
+  if (f < face) {
+    double nfu[NSED];
+    for (int s = 0; s < NSED; s++) nfu[s] = MAPPED ? flux[s * face + f] : pl.nf[s];
+    if (cf != 0.0 && !plane_dark(nfu)) {
+      double nf[NSED];
+      pcurve_fluxes(nfu, cf, nf);
+      const size_t q = plane_cell(G, f, G.na - 1);
+      term = plane_exit_term<MULTI>(*bd, ss, cin[3 * q], exit_cols[f], cin[3 * q + 1], exit_cols[face + f], cin[3 * q + 2],
+                                    exit_cols[2 * face + f], nf, sc.vol, path);
+    }
+    if constexpr (KEEP) map[f] = map[f] + term;
+  }
+  const double bs = block_sum(term, sh);
+  if (threadIdx.x == 0) partial[blockIdx.x] = bs;
+}
+
 } // namespace
 
 // ---------------------------------------------------------------------------------------------
@@ -320,8 +424,23 @@ static int run_planes(PassCtx &P, const std::vector<int> &planes) {
 
     // the rates: the flux uniform, or of the cell's own -- the map by face cell, or what the layers left per cell
     const PlaneFaceIndex fx = {pl.axis == 0 ? 0 : 1, pl.axis == 0 ? 1 : (pl.axis == 1 ? 0 : g.n1), pl.axis == 2 ? 0 : (pl.axis == 0 ? g.n2 : g.n1)};
+    // a plane with a curve (c2r_set_plane_curve): its record, and the factor of the last layer for the exit loss
+    const bool curved = pn.curve_set;
+    PlaneCurveDev cv = {};
+    double cf_last = 1.0;
+    if (curved) {
+      pcurve_fill(pn.curve.nstep, pn.curve.depth, pn.curve.factor, pn.curve.layer0, pn.curve.depth0, cv);
+      cf_last = pcurve_factor(cv, G.na - 1, path);
+    }
+    const PlaneLayerIndex lx = plane_layer_index(pl.axis, pl.from_high, G.na);
     auto rates = [&](auto flux, const double *field) {
       with_flag(!c->isothermal, [&](auto heat) { with_flag(multi, [&](auto three) {
+        if (curved) {
+          const auto kernel = k_pcurve_rates<decltype(heat)::value, decltype(three)::value, decltype(flux)::value>;
+          hipLaunchKernelGGL(kernel, dim3(tiles), dim3(BLOCK), 0, c->stream, g, path, pd, fx, face, field, cv, lx, c->d_ndens, c->d_xh_av,
+                             c->d_xhe_av, c->d_bands, ss, c->d_plane_cin, c->d_rates);
+          return;
+        }
         const auto kernel = k_plane_rates<decltype(heat)::value, decltype(three)::value, decltype(flux)::value>;
         hipLaunchKernelGGL(kernel, dim3(tiles), dim3(BLOCK), 0, c->stream, g, path, pd, fx, face, field, c->d_ndens, c->d_xh_av,
                            c->d_xhe_av, c->d_bands, ss, c->d_plane_cin, c->d_rates);
@@ -338,6 +457,12 @@ static int run_planes(PassCtx &P, const std::vector<int> &planes) {
       map = c->d_face_maps + face_map_offset(L.n, L.open, 2 * pl.axis + (1 - pl.from_high));
     }
     with_flag(multi, [&](auto three) { with_flag(mapped, [&](auto from_map) { with_flag(map != nullptr, [&](auto keep) {
+      if (curved) {
+        const auto kernel = k_pcurve_exit<decltype(three)::value, decltype(from_map)::value, decltype(keep)::value>;
+        hipLaunchKernelGGL(kernel, dim3(fblk), dim3(BLOCK), 0, c->stream, G, P.sc, path, pd, exit_flux, cf_last, c->d_bands, ss,
+                           c->d_plane_cin, pn.d_exit, c->d_plane_partial, map);
+        return;
+      }
       const auto kernel = k_plane_exit<decltype(three)::value, decltype(from_map)::value, decltype(keep)::value>;
       hipLaunchKernelGGL(kernel, dim3(fblk), dim3(BLOCK), 0, c->stream, G, P.sc, path, pd, exit_flux, c->d_bands, ss, c->d_plane_cin,
                          pn.d_exit, c->d_plane_partial, map);
@@ -549,6 +674,60 @@ extern "C" int c2r_set_plane_flux_map(c2r_ctx *c, int plane, const double *flux3
 
 extern "C" int c2r_get_plane_flux_map_set(const c2r_ctx *c, int plane) {
   return c && plane >= 1 && plane <= c->nplane && c->plane[plane - 1].fmap_set ? 1 : 0;
+}
+
+// c2r_set_plane_curve on one device: everything is checked before anything is kept; nothing is allocated (the curve travels
+// as a kernel argument)
+static int set_plane_curve_one(c2r_ctx *c, int plane, const c2r_plane_curve *curve) {
+  if (!c) return 1;
+  if (plane < 1 || plane > c->nplane) return fail(c, "c2r_set_plane_curve: plane %d not in [1,%d]", plane, c->nplane);
+  if (c->pass_open) return fail(c, "c2r_set_plane_curve: a pass opened by c2r_pass_sources_begin is still open");
+  c2r_ctx::Plane &pn = c->plane[plane - 1];
+  c2r_plane_curve kept = {0, 0, 0.0, {}, {1.0}};
+  if (curve) {
+    const c2r_plane_curve &v = *curve;
+    if (v.nstep < 0 || v.nstep > C2R_PLANE_CURVE_MAX_STEPS)
+      return fail(c, "c2r_set_plane_curve: plane %d: nstep = %d not in [0,%d]", plane, v.nstep, C2R_PLANE_CURVE_MAX_STEPS);
+    if (v.layer0 < 0) return fail(c, "c2r_set_plane_curve: plane %d: layer0 = %d is negative", plane, v.layer0);
+    if (!(v.depth0 >= 0.0) || !std::isfinite(v.depth0)) // (a NaN fails every comparison)
+      return fail(c, "c2r_set_plane_curve: plane %d: depth0 = %g is negative or not finite", plane, v.depth0);
+    for (int k = 0; k < v.nstep; k++) {
+      if (!(v.depth[k] >= 0.0) || !std::isfinite(v.depth[k]))
+        return fail(c, "c2r_set_plane_curve: plane %d: depth[%d] = %g is negative or not finite", plane, k, v.depth[k]);
+      if (k > 0 && !(v.depth[k] > v.depth[k - 1]))
+        return fail(c, "c2r_set_plane_curve: plane %d: depth[%d] = %g is not above depth[%d] = %g", plane, k, v.depth[k], k - 1,
+                    v.depth[k - 1]);
+    }
+    for (int k = 0; k <= v.nstep; k++)
+      if (!(v.factor[k] >= 0.0) || !std::isfinite(v.factor[k]))
+        return fail(c, "c2r_set_plane_curve: plane %d: factor[%d] = %g is negative or not finite", plane, k, v.factor[k]);
+    // an all-zero record is a record nobody filled in, not a plane that has gone dark (that is {1, .., {0.0}, {0.0, 0.0}})
+    if (v.nstep == 0 && v.factor[0] == 0.0)
+      return fail(c, "c2r_set_plane_curve: plane %d: nstep = 0 and factor[0] = 0 (a zeroed record); no curve is factor[0] = 1", plane);
+    kept.nstep = v.nstep;
+    kept.layer0 = v.layer0;
+    kept.depth0 = v.depth0;
+    for (int k = 0; k < v.nstep; k++) kept.depth[k] = v.depth[k];
+    for (int k = 0; k <= v.nstep; k++) kept.factor[k] = v.factor[k];
+  }
+  pn.curve = kept;
+  pn.curve_set = !(kept.nstep == 0 && kept.factor[0] == 1.0); // no step and factor 1.0: no curve, the uncurved kernels
+  return 0;
+}
+
+extern "C" int c2r_set_plane_curve(c2r_ctx *c, int plane, const c2r_plane_curve *curve) {
+  if (int e_ = set_plane_curve_one(c, plane, curve)) return e_;
+  return for_replicas(c, [&](c2r_ctx *r) { return set_plane_curve_one(r, plane, curve); });
+}
+
+extern "C" int c2r_get_plane_curve(const c2r_ctx *c, int plane, c2r_plane_curve *out) {
+  if (!c || !out) return 1;
+  if (plane < 1 || plane > c->nplane) {
+    c->err = "c2r_get_plane_curve: plane " + std::to_string(plane) + " not in [1," + std::to_string(c->nplane) + "]";
+    return 1;
+  }
+  *out = c->plane[plane - 1].curve;
+  return 0;
 }
 
 // the device of the context that ran plane p (0-based) last: the deal gives a plane to one device per pass

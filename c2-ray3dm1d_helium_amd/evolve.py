@@ -617,6 +617,35 @@ class HipEngine:
         self._chk(self.lib.c2r_download_plane_exit_flux(self.h, int(p), _dp(out)))
         return out
 
+    def set_plane_curve(self, p, curve=None):
+        """c2r_set_plane_curve: the light curve of plane p (1-based) -- None (no curve) or (depths, factors, layer0=0,
+        depth0=0.0): up to 8 depths along the beam, lengths in the length unit of dr, strictly ascending, and one factor more
+        than depths, factors[b] the flux factor of depth shell b ([0, d0], (d0, d1], ..., beyond the last depth); layer0 layers
+        of the plane's path and the length depth0 lie in front of this mesh.  set_plane_sources drops every curve."""
+        if curve is None:
+            self._chk(self.lib.c2r_set_plane_curve(self.h, int(p), None))
+            return
+        depths, factors = [float(d) for d in curve[0]], [float(f) for f in curve[1]]
+        if len(factors) != len(depths) + 1:
+            raise ValueError(f"a curve of {len(depths)} depths takes {len(depths) + 1} factors, not {len(factors)}")
+        rec = _lib.PlaneCurve()
+        rec.nstep = len(depths)                    # (more than 8: the library refuses the call, the record holds the first 8)
+        rec.layer0 = int(curve[2]) if len(curve) > 2 else 0
+        rec.depth0 = float(curve[3]) if len(curve) > 3 else 0.0
+        for k, d in enumerate(depths[:_lib.PLANE_CURVE_MAX_STEPS]):
+            rec.depth[k] = d
+        for k, f in enumerate(factors[:_lib.PLANE_CURVE_MAX_STEPS + 1]):
+            rec.factor[k] = f
+        self._chk(self.lib.c2r_set_plane_curve(self.h, int(p), C.byref(rec)))
+
+    def plane_curve(self, p):
+        """c2r_get_plane_curve for plane p (1-based): (depths, factors, layer0, depth0) as it was set, ([], [1.0], 0, 0.0) while
+        it has none."""
+        c = _lib.PlaneCurve()
+        self._chk(self.lib.c2r_get_plane_curve(self.h, int(p), C.byref(c)))
+        n = int(c.nstep)
+        return [float(c.depth[k]) for k in range(n)], [float(c.factor[k]) for k in range(n + 1)], int(c.layer0), float(c.depth0)
+
     def set_plane_tilt(self, p, tilt=None):
         """Oblique incidence of plane p (1-based): `tilt` = the tangents of the beam's inclination towards the two face axes
         (the lower axis first), in physical lengths.  None or (0, 0): normal incidence again.  set_plane_sources resets

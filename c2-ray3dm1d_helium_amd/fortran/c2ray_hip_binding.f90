@@ -78,6 +78,18 @@ module c2ray_hip
      real(c_double) :: factor(C2R_CURVE_MAX_STEPS + 1)
   end type c2r_source_curve
 
+  !> c2r_plane_curve of include/c2ray_hip.h: the light curve of one plane -- nstep ascending depths along its beam (lengths in
+  !> the unit of dr) and the flux factor of each of the nstep + 1 depth shells; layer0 layers and the length depth0 lie in
+  !> front of the mesh; nstep = 0 and factor(1) = 1: no curve
+  integer(c_int), parameter :: C2R_PLANE_CURVE_MAX_STEPS = 8
+  type, bind(C) :: c2r_plane_curve
+     integer(c_int) :: nstep
+     integer(c_int) :: layer0
+     real(c_double) :: depth0
+     real(c_double) :: depth(C2R_PLANE_CURVE_MAX_STEPS)
+     real(c_double) :: factor(C2R_PLANE_CURVE_MAX_STEPS + 1)
+  end type c2r_plane_curve
+
   !> c2r_sed_setup of include/c2ray_hip.h: what spec_integration starts from for one SED
   type, bind(C) :: c2r_sed_setup
      integer(c_int) :: nfreq, sed
@@ -685,6 +697,22 @@ module c2ray_hip
        integer(c_int), value :: plane
        real(c_double), intent(out) :: flux3(*)
      end function c2r_download_plane_exit_flux
+
+     !> plane light curves: c_loc of one type(c2r_plane_curve), or c_null_ptr: the plane has no curve
+     integer(c_int) function c2r_set_plane_curve(ctx, plane, curve) bind(C, name="c2r_set_plane_curve")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: ctx
+       integer(c_int), value :: plane
+       type(c_ptr), value :: curve
+     end function c2r_set_plane_curve
+
+     !> the curve of plane `plane` (1-based) as it was set; nstep = 0 and factor(1) = 1 while it has none
+     integer(c_int) function c2r_get_plane_curve(ctx, plane, curve) bind(C, name="c2r_get_plane_curve")
+       import :: c_int, c_ptr, c2r_plane_curve
+       type(c_ptr), value :: ctx
+       integer(c_int), value :: plane
+       type(c2r_plane_curve), intent(out) :: curve
+     end function c2r_get_plane_curve
 
      !> escape maps (include/c2ray_hip.h): the kept photon loss per cell of the open mesh face it leaves through;
      !> face = 2*axis + high, axis 0-based, high = 0 the face at index 1

@@ -629,6 +629,72 @@ int c2r_set_plane_flux_map(c2r_ctx *ctx, int plane, const double *flux3);
 int c2r_get_plane_flux_map_set(const c2r_ctx *ctx, int plane);          /* 1 / 0 */
 int c2r_download_plane_exit_flux(c2r_ctx *ctx, int plane, double *flux3);
 
+/* Plane light curves: a flux factor per shell of depth along a plane's beam, per plane.  What c2r_set_source_curves is to a
+ * point source: a layer at depth d along the beam sees the plane at the retarded time t - d/c, and a stack of slabs that hand
+ * their exit columns on models a light-cone strip many light-crossing times long.  A host that knows the history of what
+ * shines through the face (a distant quasar that flickers, switches on or has switched off; a background that ramps up) hands
+ * it over as a piecewise-constant curve, depth[k] = c*(t - t_k) and factor = F(t_k)/F(t).  A depth horizon is the crudest such
+ * curve: {1, layer0, depth0, {D}, {1, 0}}.
+ *   nstep     the number of steps, 0 .. C2R_PLANE_CURVE_MAX_STEPS
+ *   layer0    >= 0: the layers of this plane's path the beam crossed before it entered this mesh (the layers of the slabs
+ *             upstream, where they share the tilt and the cell size)
+ *   depth0    finite, >= 0: a length the beam travelled before that, in the length unit of dr
+ *   depth     depth[0..nstep-1]: lengths along the beam in the length unit of dr, finite, >= 0 and strictly ascending
+ *   factor    factor[0..nstep]: finite and >= 0; factor[b] holds in depth shell b.  The shells are [0, depth[0]],
+ *             (depth[0], depth[1]], ..., (depth[nstep-1], infinity)
+ * Entries behind nstep (depth) and nstep + 1 (factor) mean nothing and are not looked at.
+ * The rule (csrc/c2ray_pcurve.hpp).  For layer m = 0 .. mesh[axis]-1 in travel order and the per-layer path of the pass --
+ * dr[axis] at normal incidence, dr[axis]*sqrt(1 + tilt[0]^2 + tilt[1]^2) as the tilted march forms it, from the dr of that
+ * pass -- every operation rounded as written, no fused multiply-add:
+ *     d = depth0 + ((double)(layer0 + m) + 0.5) * path
+ *     b = the number of k < nstep with d > depth[k]
+ *     f = factor[b]
+ * No square root and no division: a layer whose centre lies exactly on a depth belongs to the nearer shell.  f is uniform
+ * over a layer.
+ * A cell of a layer with f == 0.0 is UNLIT: it adds nothing to phih, phihe or phiheat and no per-cell routine runs for it; if
+ * it lies in the last layer its line's loss term is 0.0, in photon_loss(1), in c2r_get_plane_loss and in the far face's escape
+ * map.  Any other cell is the plane's cell in every respect but one: nf[k]*f takes the place of nf[k], one rounded product per
+ * SED, where nf is whatever the cell uses without a curve -- the plane's normflux, the map entry of its line, or the flux the
+ * tilted march carried to the cell.  The exit term of a line uses the last layer's f in the same way.  A cell is skipped iff
+ * its unscaled fluxes are dark (all three == 0.0) or f == 0.0; whether the plane takes the three-SED routine is decided from
+ * the unscaled fluxes, as without a curve.
+ * What a curve does not touch.  The march, the fog, the columns, the exit columns and the max_coldensh guard; vol_ph = path;
+ * the flux a tilted plane with a map carries from layer to layer, and c2r_download_plane_exit_flux, which stays the UNSCALED
+ * flux of the last layer (the slab downstream applies its own curve, with its own layer0 / depth0); sum_nbox and the deal of
+ * planes to callers.  Nothing is rescaled to conserve anything.
+ * Identities.
+ *   Off: with no curve set every grid, loss, map and exit buffer has the bits it had before curves existed, from the same
+ *     kernel launches.
+ *   All factors 1.0: the same bits, through the curved kernels.
+ *   Step to zero: {1, .., {D}, {1, 0}} is a depth horizon -- layers within D have the uncurved bits, layers beyond have rates
+ *     of exactly zero, and the loss is exactly 0.0 when the last layer lies beyond D.
+ *   A factor 2^n scales the rates and the loss terms of its layers exactly.
+ *   Stacking: an upstream slab of n_a layers and a downstream slab with layer0 larger by n_a, the same tilt and the same
+ *     path, the exit columns handed on (and the exit flux, where the plane has a map), reproduce one mesh of the combined
+ *     depth bit for bit.
+ * c2r_set_plane_curve gives plane `plane` (1-based) its curve; curve = NULL, or a record with nstep == 0 and factor[0] == 1.0:
+ * the plane has no curve.  c2r_set_plane_sources drops every curve; c2r_set_plane_tilt, c2r_set_plane_flux_map,
+ * c2r_set_plane_entry_columns, c2r_set_boundaries* and c2r_set_sources keep them.  The calls act on every device of a
+ * multi-device context, and every route that runs a plane honours the curve: c2r_pass_sources and its slab-wise form,
+ * c2r_do_source(NumSrc + p), c2r_pass_allreduce_chemistry, c2r_iteration, c2r_evolve3d.  Setting a curve allocates nothing.
+ * Refused, each with an error text: a bad plane number; a call between c2r_pass_sources_begin and c2r_pass_sources_end; an
+ * nstep outside 0..C2R_PLANE_CURVE_MAX_STEPS; a negative layer0; a negative or non-finite depth0; a depth that is negative,
+ * not finite or not above its predecessor; a factor that is negative or not finite; and the ZEROED RECORD (nstep == 0 and
+ * factor[0] == 0.0), for the reasons c2r_set_source_curves gives: a plane that has gone dark is {1, .., {0.0}, {0.0, 0.0}}.  A
+ * refused call changes nothing.
+ * c2r_get_plane_curve returns the curve of the plane as it was set, the entries behind its steps zeroed, and {0, 0, 0.0, {},
+ * {1.0}} while none is set; a bad plane number is refused with an error text. */
+#define C2R_PLANE_CURVE_MAX_STEPS 8
+typedef struct {
+  int nstep;
+  int layer0;
+  double depth0;
+  double depth[C2R_PLANE_CURVE_MAX_STEPS];
+  double factor[C2R_PLANE_CURVE_MAX_STEPS + 1];
+} c2r_plane_curve;
+int c2r_set_plane_curve(c2r_ctx *ctx, int plane, const c2r_plane_curve *curve);
+int c2r_get_plane_curve(const c2r_ctx *ctx, int plane, c2r_plane_curve *out);
+
 /* Escape maps: WHERE the photons that photon_loss(1) counts left an open box -- the kept loss per cell of the open mesh
  * face it leaves through.  Off by default; with it off nothing is allocated, launched or waited for.
  * Faces: face = 2*axis + high, axis 0, 1, 2; high = 0 is the face at mesh index 1, high = 1 the one at index mesh[axis].
