@@ -147,6 +147,11 @@ def _oracle_columns(pkg, orc, otables, case, key, ns):
 
 def cell_photo_out(pkg, orc, otables, case, key, ns, o):
     """photo_out of the cell at offset o from source ns (0-based), the source alone: face_loss_reference.source_terms' steps."""
+    return cell_photo_out_vol(pkg, orc, otables, case, key, ns, o)[0]
+
+
+def cell_photo_out_vol(pkg, orc, otables, case, key, ns, o):
+    """(photo_out, vol_ph) of that cell: its loss term is photo_out * vol / vol_ph (evolve_point.F90:310-315)."""
     n, m, periodic = fl.geometry(case)
     st, s, _ = _oracle_columns(pkg, orc, otables, case, key, ns)
     consts = orc.constants()
@@ -175,15 +180,15 @@ def cell_photo_out(pkg, orc, otables, case, key, ns, o):
         xs, ys, zs = dr[0] * float(o[0]), dr[1] * float(o[1]), dr[2] * float(o[2])
         vol_ph = 4.0 * pi * (xs * xs + ys * ys + zs * zs) * path
     if not cin[0] < fl.MAX_COLDENSH:
-        return 0.0
+        return 0.0, vol_ph
     cols6 = [cin[0], float(cH[q]), cin[1], float(cHe[q]), cin[2], float(cHe[q + ncell_m])]
     i_state = max(float(s.xh_av[q + ncell_m]), eps)
     if case.pl is not None:
         r = orc.PhotRates()
         orc.lib().orc_photoion_rates3(C.byref(otables.c), *[C.c_double(x) for x in cols6], C.c_double(vol_ph), (C.c_double * 3)(*nf),
                                       C.c_double(i_state), C.c_int(0 if case.heat else 1), C.byref(r))
-        return float(r.photo_out)
-    return float(orc.photoion_rates(otables, cols6, vol_ph, nf[0], i_state, not case.heat)[20])
+        return float(r.photo_out), vol_ph
+    return float(orc.photoion_rates(otables, cols6, vol_ph, nf[0], i_state, not case.heat)[20]), vol_ph
 
 
 def source_terms(pkg, orc, otables, case, key, ns, radius, lo, hi, beam=None):
