@@ -619,18 +619,22 @@ C2R_HD double read_table(const double *col, const TauPos &p) {
 // The same two rows, fetched apart from their interpolation (the gathers-first order of band_rates), at a 32-bit BYTE
 // offset from the column base: the base is uniform over a wave, so the gather takes its scalar-base form (one 32-bit
 // shift per position, no 64-bit vector address arithmetic).  The offset stays within one column.
-struct TableRows {
-  double a, b; // rows ipos and ipos + 1
+// The gathers-first readers do not read the table itself but its PAIR copy (k_table_pairs, c2ray_hip.hip): entry (band b,
+// row r) is {c[r], c[r + 1] - c[r]}, the difference formed once per table set by the very subtraction read_table makes per
+// cell, source and band.  A position is then one 16-byte load that never straddles a cache line, and the interpolation a
+// product and a sum.  The pair of the last used row (r = NumTau) has difference c[2001] - c[2000] == +0.
+struct alignas(16) TablePair {
+  double c, d; // row ipos, and row ipos + 1 minus row ipos
 };
-static_assert((size_t)NTAUP * sizeof(double) < ((size_t)1 << 32), "load_rows: a column is addressed by 32-bit byte offsets");
-C2R_HD TableRows load_rows(const double *col, const TauPos &p) {
-  const double *e = (const double *)((const char *)col + ((unsigned)p.ipos << 3));
-  TableRows r;
-  r.a = e[0];
-  r.b = e[1];
-  return r;
+typedef TablePair TableRows;
+// entries of one band's column in the pair copy, and where (band b, row r) stands in it
+constexpr size_t TABLE_PAIR_PITCH = (size_t)NTAUP;
+C2R_HD constexpr size_t table_pair_index(int b, int r) { return (size_t)b * TABLE_PAIR_PITCH + (size_t)r; }
+static_assert(TABLE_PAIR_PITCH * sizeof(TablePair) < ((size_t)1 << 32), "load_rows: a column is addressed by 32-bit byte offsets");
+C2R_HD TableRows load_rows(const TablePair *col, const TauPos &p) {
+  return *(const TablePair *)((const char *)col + ((unsigned)p.ipos << 4));
 }
-C2R_HD double interpolate_rows(const TableRows &r, const TauPos &p) { return r.a + (r.b - r.a) * p.residual; }
+C2R_HD double interpolate_rows(const TableRows &r, const TauPos &p) { return r.c + r.d * p.residual; }
 
 // Heating tables as the rates kernels read them: INTERLEAVED by band.  The reference keeps one column of 0:NumTau
 // per (band, species) -- 1 + 2 x 26 + 3 x 20 = 113 columns (radiation_sizes.f90:23) -- and heat_lookuptable reads,
@@ -804,7 +808,7 @@ struct BandRows {
 // same statement it cannot be moved behind the wait.
 C2R_HD void band_gathers_arrive(const BandRows &R, double under) {
 #if defined(__HIP_DEVICE_COMPILE__)
-  asm volatile("" ::"v"(R.in.a), "v"(R.in.b), "v"(R.out.a), "v"(R.out.b), "v"(under));
+  asm volatile("" ::"v"(R.in.c), "v"(R.in.d), "v"(R.out.c), "v"(R.out.d), "v"(under));
 #else
   (void)R; (void)under;
 #endif
@@ -1038,7 +1042,8 @@ C2R_HD void band_positions_gathers_first(const LT *logtab, const CellSrc &c, dou
       pin_here(forscaleing);
     }
   }
-  const double *tk = photo_thick + (size_t)b * NTAUP;
+  // (gathers first: `photo_thick` is the table's pair copy, RatesTables::pairs, handed down under the table's name)
+  const TablePair *tk = (const TablePair *)photo_thick + table_pair_index(b, 0);
   R.in = load_rows(tk, B.pin);
   R.out = load_rows(tk, B.pout);
   if (CLS >= 1 && c.recip_safe) {
@@ -1126,7 +1131,7 @@ C2R_HD void sed_rates(const BD &bd, const double *photo_thick, const double *pho
                       const double *heat_thick, const double *heat_thin, int blo, int bhi, double cin_HI,
                       double cout_HI, double cin_HeI, double cout_HeI, double cin_HeII, double cout_HeII, double vol,
                       double NFlux, const Ricotti &ric, SedAcc &out, const LT *logtab, const double *tau_zero,
-                      const gm::LogPins *pins = nullptr) {
+                      const gm::LogPins *pins = nullptr, const Recip *rvol = nullptr) {
   out.photo_HI = out.photo_HeI = out.photo_HeII = 0.0;
   out.photo_out = 0.0;
   out.f_heat = out.f_ion_HI = out.f_ion_HeI = 0.0;
@@ -1138,7 +1143,9 @@ C2R_HD void sed_rates(const BD &bd, const double *photo_thick, const double *pho
   c.cell_HeI = cout_HeI - cin_HeI;
   c.cell_HeII = cout_HeII - cin_HeII;
   c.NFlux = NFlux;
-  c.rvol = make_recip(vol);
+  // `rvol`: the divisor as the caller read it from the shell table (ShellVol: `vol` and RN(1/vol), formed there by the
+  // expressions of make_recip); without it the reciprocal is formed here, per cell and source
+  c.rvol = rvol ? *rvol : make_recip(vol);
   c.pins = pins;
   c.recip_safe = column_in_recip_range(c.cell_HI) && column_in_recip_range(c.cell_HeI) && column_in_recip_range(c.cell_HeII);
   SedSums o = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
@@ -1231,10 +1238,10 @@ C2R_HD void photoion_rates(const BD &bd, const double *photo_thick, const double
                            const double *heat_thick, const double *heat_thin, double cin_HI, double cout_HI,
                            double cin_HeI, double cout_HeI, double cin_HeII, double cout_HeII, double vol,
                            double NFlux, const Ricotti &ric, PhotoOut &o, const LT *logtab = C2R_LOGTAB_DEFAULT,
-                           const gm::LogPins *pins = nullptr) {
+                           const gm::LogPins *pins = nullptr, const Recip *rvol = nullptr) {
   SedAcc a;
   sed_rates<HEAT, GF, LT>(bd, photo_thick, photo_thin, heat_thick, heat_thin, 0, bd.bb_upper, cin_HI, cout_HI, cin_HeI, cout_HeI,
-                      cin_HeII, cout_HeII, vol, NFlux, ric, a, logtab, bd.tau_zero[0], pins);
+                      cin_HeII, cout_HeII, vol, NFlux, ric, a, logtab, bd.tau_zero[0], pins, rvol);
   o.photo_HI = a.photo_HI;
   o.photo_HeI = a.photo_HeI;
   o.photo_HeII = a.photo_HeII;

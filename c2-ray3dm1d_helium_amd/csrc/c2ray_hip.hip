@@ -181,6 +181,57 @@ __device__ __forceinline__ double sc_path(int idel, int jdel, int kdel) {
   return sqrt(1.0 + (dj * dj + dk * dk) / (di * di));
 }
 
+// What the rates kernels read instead of computing it per cell and source, made on the device from inputs that change
+// seldom (the photo table: per table set; the cell sizes: per time step):
+//   pairs     the black-body photo_thick table as (value, forward difference) pairs (TablePair, c2ray_device.hpp) for the
+//             gathers-first readers: the isothermal one-SED k_rates, k_rates_beam and k_rates_curve;
+//   shellvol  vol_ph and its reciprocal per (|di|, |dj|, |dk|) (ShellVol, c2ray_shell.hpp), extents e1 x e2 x ..., for the
+//             all-periodic one-SED k_rates; `big`: every entry satisfies Recip::ok_big.  Where one does not, every lane takes
+//             div_by_vol's plain divisions, which give the bits that Markstein's sequence gives where it is allowed.
+struct RatesTables {
+  const TablePair *pairs;
+  const ShellVol *shellvol;
+  int e1, e2, big;
+};
+// pairs[b][r] = {c[r], c[r + 1] - c[r]}: the subtraction of read_table, once per entry; row NumTau gets c[2001] - c[2000],
+// +0 by the duplicated row, and row 2001, which no position reaches, a difference of 0 as well
+__global__ void __launch_bounds__(BLOCK)
+k_table_pairs(const double *__restrict__ tab, TablePair *__restrict__ pairs) {
+  const int r = blockIdx.x * BLOCK + threadIdx.x, b = blockIdx.y;
+  if (r >= NTAUP) return;
+  const double *col = tab + (size_t)b * NTAUP;
+  TablePair p;
+  p.c = col[r];
+  p.d = r + 1 < NTAUP ? col[r + 1] - col[r] : 0.0;
+  pairs[table_pair_index(b, r)] = p;
+}
+// shellvol[|di|, |dj|, |dk|]: the expressions of the rates body and of make_recip, once per offset; *not_big is raised where
+// an entry fails Recip::ok_big (one atomic per wave that has such an entry)
+__global__ void __launch_bounds__(BLOCK)
+k_shell_volumes(double dr1, double dr2, double dr3, double cellvol, int e1, int e2, int e3, ShellVol *__restrict__ tab,
+                int *__restrict__ not_big) {
+  const size_t q = (size_t)blockIdx.x * BLOCK + threadIdx.x;
+  if (q >= (size_t)e1 * e2 * e3) return;
+  const int di = (int)(q % e1), dj = (int)((q / e1) % e2), dk = (int)(q / ((size_t)e1 * e2));
+  double vol_ph;
+  if (di == 0 && dj == 0 && dk == 0) {
+    vol_ph = cellvol;
+  } else {
+    const double path = sc_path(di, dj, dk) * dr1;
+    const double xs = dr1 * (double)di, ys = dr2 * (double)dj, zs = dr3 * (double)dk;
+    const double dist2 = xs * xs + ys * ys + zs * zs;
+    vol_ph = 4.0 * pi * dist2 * path;
+  }
+  const Recip R = make_recip(vol_ph);
+  ShellVol v;
+  v.vol = R.b;
+  v.rvol = R.y;
+  tab[shell_vol_index(di, dj, dk, e1, e2)] = v;
+  const bool bad = !R.ok_big;
+  const unsigned long long m = __ballot(bad);
+  if (bad && (int)(threadIdx.x & 63) == __ffsll((long long)m) - 1) atomicOr(not_big, 1);
+}
+
 // A pointer that comes out of a record in memory (SrcDev::cols) is a generic pointer to the compiler, which then uses
 // flat loads and stores; the column blocks are device memory.
 typedef __attribute__((address_space(1))) double global_double;
@@ -788,7 +839,7 @@ __global__ void C2R_RATES_BOUNDS
 k_rates(Grid g, const SrcDev *__restrict__ src, int nsrc, StepScalars sc, const double *__restrict__ ndens,
         const double *__restrict__ xh_av, const double *__restrict__ xhe_av,
         const BandDataByRow *__restrict__ bdr, SedSet ss, double *__restrict__ rates, const int *__restrict__ tiles,
-        const int *__restrict__ tile_ptr, const int *__restrict__ tile_src, int tile_base, int fresh) {
+        const int *__restrict__ tile_ptr, const int *__restrict__ tile_src, int tile_base, int fresh, RatesTables rt) {
   constexpr bool BEAM = false, CURVE = false;
 #include "c2ray_rates_body.inc"
 }
@@ -797,7 +848,7 @@ __global__ void C2R_RATES_BOUNDS
 k_rates_beam(Grid g, const SrcDev *__restrict__ src, int nsrc, StepScalars sc, const double *__restrict__ ndens,
              const double *__restrict__ xh_av, const double *__restrict__ xhe_av,
              const BandDataByRow *__restrict__ bdr, SedSet ss, double *__restrict__ rates, const int *__restrict__ tiles,
-             const int *__restrict__ tile_ptr, const int *__restrict__ tile_src, int tile_base, int fresh) {
+             const int *__restrict__ tile_ptr, const int *__restrict__ tile_src, int tile_base, int fresh, RatesTables rt) {
   constexpr bool BEAM = true, CURVE = false;
 #include "c2ray_rates_body.inc"
 }
@@ -810,7 +861,7 @@ __global__ void C2R_RATES_BOUNDS
 k_rates_curve(Grid g, const SrcDev *__restrict__ src, int nsrc, StepScalars sc, const double *__restrict__ ndens,
               const double *__restrict__ xh_av, const double *__restrict__ xhe_av,
               const BandDataByRow *__restrict__ bdr, SedSet ss, double *__restrict__ rates, const int *__restrict__ tiles,
-              const int *__restrict__ tile_ptr, const int *__restrict__ tile_src, int tile_base, int fresh) {
+              const int *__restrict__ tile_ptr, const int *__restrict__ tile_src, int tile_base, int fresh, RatesTables rt) {
   constexpr bool BEAM = true, CURVE = true;
 #include "c2ray_rates_body.inc"
 }
@@ -1579,6 +1630,15 @@ struct c2r_ctx {
   // the heating tables as the kernels read them, interleaved by band (c2ray_device.hpp heat_interleave): [sed][thick, thin];
   // the column-wise copies above (and d_sed_tab[][2..3]) stay for c2r_download_tables and band_tau_zero
   double *d_heat_woven[3][2] = {{nullptr, nullptr}, {nullptr, nullptr}, {nullptr, nullptr}};
+  // what the rates kernels read instead of computing it (RatesTables): the pair copy of d_photo_thick, remade wherever that
+  // table is written (refresh_tau_zero), and the shell volumes per offset, remade by the first pass after the cell sizes
+  // changed (rates_tables); sv_key: the dr1, dr2, dr3, cellvol the table in hand was made from, compared bit by bit
+  TablePair *d_photo_pairs = nullptr;
+  ShellVol *d_shellvol = nullptr;
+  int *d_shellvol_flag = nullptr;
+  bool shellvol_valid = false;
+  int shellvol_big = 0;
+  double sv_key[4] = {0, 0, 0, 0};
   BandDataByRow *d_bands = nullptr;
   BandDataByRow h_bands{};         // host copy (tau_zero is refreshed whenever a table set changes); d_bands is its upload: the
                                    // other kernels take it as its base BandData, the three-SED heating kernel as what it is
@@ -2164,7 +2224,7 @@ extern "C" void c2r_destroy(c2r_ctx *c) {
   for (auto &row : c->d_sed_tab)
     for (double *p : row)
       if (p) (void)hipFree(p);
-  void *ptrs[] = {c->d_photo_thick, c->d_photo_thin, c->d_heat_thick, c->d_heat_thin, c->d_bands, c->d_cool,
+  void *ptrs[] = {c->d_photo_pairs, c->d_shellvol, c->d_shellvol_flag, c->d_photo_thick, c->d_photo_thin, c->d_heat_thick, c->d_heat_thin, c->d_bands, c->d_cool,
                   c->d_ndens, c->d_xh, c->d_xhe, c->d_xh_av, c->d_xhe_av, c->d_xh_int, c->d_xhe_int, c->d_temp,
                   c->d_rates_own, c->d_stateT, c->d_loss_partial, c->d_loss_acc, c->d_conv, c->d_colgrid, c->d_rc_last, c->d_stat, c->d_lls, c->d_clump, c->d_block_base, c->d_defer[0], c->d_defer[1], c->d_chemctl, c->d_chemspread};
   for (void *p : ptrs)
@@ -2278,6 +2338,12 @@ static int refresh_tau_zero(c2r_ctx *c, int sed) {
         HIPCHK(c, hipMemcpy(c->d_heat_woven[sed][t], woven.data(), sizeof(double) * woven.size(), hipMemcpyHostToDevice));
       }
     }
+  }
+  if (sed == 0 && have) { // every writer of d_photo_thick ends here: its pair copy for the gathers-first readers
+    if (!c->d_photo_pairs) HIPCHK(c, hipMalloc(&c->d_photo_pairs, sizeof(TablePair) * table_pair_index(NFREQ, 0)));
+    hipLaunchKernelGGL(k_table_pairs, dim3((NTAUP + BLOCK - 1) / BLOCK, NFREQ), dim3(BLOCK), 0, c->stream, c->d_photo_thick, c->d_photo_pairs);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));
   }
   if (c->have_bands) {
     band_rows_fill(c->h_bands);
@@ -2830,6 +2896,40 @@ static StepScalars scalars(c2r_ctx *c) {
   return s;
 }
 
+// RatesTables of a pass: the pair copy as it stands, and, on an all-periodic mesh, the shell volumes for the cell sizes of
+// `sc` -- made here, on the main stream (which every rates launch of the pass waits for), when there are none yet or the
+// sizes differ from those the table was made from.  Within a time step the sizes stay what they are, so its outer
+// iterations, their passes and all sources share one table (16 bytes per offset: 2 bytes per mesh cell).
+static int rates_tables(c2r_ctx *c, const StepScalars &sc, RatesTables &rt) {
+  rt = RatesTables{c->d_photo_pairs, nullptr, 0, 0, 0};
+  if (!c->periodic) return 0;
+  const int e1 = shell_vol_extent(c->g.n1, c->g.l1), e2 = shell_vol_extent(c->g.n2, c->g.l2), e3 = shell_vol_extent(c->g.n3, c->g.l3);
+  const size_t n = (size_t)e1 * e2 * e3;
+  const double key[4] = {sc.dr1, sc.dr2, sc.dr3, sc.cellvol};
+  if (!c->shellvol_valid || std::memcmp(key, c->sv_key, sizeof key) != 0) {
+    c->shellvol_valid = false;
+    if (!c->d_shellvol) {
+      HIPCHK(c, hipMalloc(&c->d_shellvol, sizeof(ShellVol) * n));
+      HIPCHK(c, hipMalloc(&c->d_shellvol_flag, sizeof(int)));
+    }
+    HIPCHK(c, hipMemsetAsync(c->d_shellvol_flag, 0, sizeof(int), c->stream));
+    hipLaunchKernelGGL(k_shell_volumes, dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, c->stream, sc.dr1, sc.dr2, sc.dr3,
+                       sc.cellvol, e1, e2, e3, c->d_shellvol, c->d_shellvol_flag);
+    HIPCHK(c, hipGetLastError());
+    int not_big = 1;
+    HIPCHK(c, hipMemcpyAsync(&not_big, c->d_shellvol_flag, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->shellvol_big = not_big ? 0 : 1;
+    std::memcpy(c->sv_key, key, sizeof key);
+    c->shellvol_valid = true;
+  }
+  rt.shellvol = c->d_shellvol;
+  rt.e1 = e1;
+  rt.e2 = e2;
+  rt.big = c->shellvol_big;
+  return 0;
+}
+
 // Column scratch for the passes of the step that begins, sized from what the LAST pass learnt about every source (sub-box
 // counts carried from time step to time step, and with a source's cell from source list to source list): for each ping-pong set
 // the blocks of its largest batch, in ONE segment.  A device allocation costs ~25 ms per GB here and synchronises the device;
@@ -3140,6 +3240,7 @@ struct PassCtx {
   int nslab = 0;                // rate-grid slabs of the last batch (0: one rates launch)
   long long stamp = 0;          // this pass in the count of all passes of the process (c2r_get_source_trace)
   std::vector<hipEvent_t> tev;  // per batch: sweep start, sweep end, rates start, rates end
+  RatesTables rt{};             // what the rates launches read instead of computing it (rates_tables)
 };
 
 // One batch: the sources mine[b0 .. b0 + nb) on scratch set `set`.
@@ -3881,7 +3982,7 @@ static int launch_rates(const PassCtx &P, Batch &B, bool last_batch) {
     auto go = [&](auto kernel) {
       hipLaunchKernelGGL(kernel, dim3(cnt), dim3(BLOCK), 0, st, c->g, c->d_src[B.set], B.nb, P.sc, c->d_ndens, c->d_xh_av, c->d_xhe_av,
                          c->d_bands, P.ss, c->d_rates, lists ? c->d_tiles[B.set] : nullptr, lists ? c->d_tptr[B.set] : nullptr,
-                         lists ? c->d_tsrc[B.set] : nullptr, base, fresh);
+                         lists ? c->d_tsrc[B.set] : nullptr, base, fresh, P.rt);
     };
     if (cnt > 0)
       with_flag(!c->isothermal, [&](auto heat) { with_flag(P.multi, [&](auto multi) { with_flag(!c->periodic, [&](auto open) {
@@ -4017,6 +4118,7 @@ static int pass_list(c2r_ctx *c, const std::vector<int> &dealt, int nslab = 0) {
   }
   PassCtx P{c, scalars(c), SedSet(), false, widest, generic_sweep, arena_log};
   P.ss = sedset(c, &P.multi);
+  if (rates_tables(c, P.sc, P.rt)) return 1;
   c->tm.sweep_ms = c->tm.rates_ms = 0.0;
   c->tm.sweep_launches = c->tm.rates_launches = 0;
   c->tm.cells_swept = 0;

@@ -25,6 +25,8 @@
   // pairs need come from the cell's denominators, which wait in LDS (below)
   constexpr bool ISO1 = !HEAT && !MULTI && !BEAM;
   constexpr bool EXPT = ISO1;
+  // ... and k_rates with one SED and all axes periodic reads the shell volume of a cell.source from a table (below)
+  constexpr bool SHELLTAB = !MULTI && !BEAM && !OPEN;
   __shared__ gm::Log10Exp s_exptab[EXPT ? gm::LOG10_NEXP : 1];
   if constexpr (EXPT) {
     for (int e = (int)threadIdx.x; e < gm::LOG10_NEXP; e += BLOCK) s_exptab[e] = gm::make_log10_exp(gm::LOG10_KY_LO + e);
@@ -176,8 +178,23 @@
     const double cout_HI = cs[col_out(p, 0, cz)];
     const double cin_HI = cs[col_in(p, 0, cz)], cin_HeI = cs[col_in(p, 1, cz)], cin_HeII = cs[col_in(p, 2, cz)];
     const double cout_HeI = cs[col_out(p, 1, cz)], cout_HeII = cs[col_out(p, 2, cz)];
+    // The shell volume and its reciprocal.  SHELLTAB (k_rates, one SED, all axes periodic): read from the table per offset
+    // (rt.shellvol, k_shell_volumes: these expressions and make_recip's, once per time step) -- one 16-byte load for a
+    // division, a square root and a reciprocal per cell and source; rt.big, uniform, stands for Recip::ok_big of every entry.
+    // The open and mixed-boundary kernels, whose offsets span the whole mesh, the beam and curve kernels and the three-SED
+    // ones compute as they did.
     double vol_ph;
-    if (di == 0 && dj == 0 && dk == 0) {
+    [[maybe_unused]] Recip rvol_;
+    const Recip *rvol = nullptr;
+    if constexpr (SHELLTAB) {
+      const int ia = di < 0 ? -di : di, ja = dj < 0 ? -dj : dj, ka = dk < 0 ? -dk : dk;
+      const ShellVol v = rt.shellvol[shell_vol_index(ia, ja, ka, rt.e1, rt.e2)];
+      vol_ph = v.vol;
+      rvol_.b = v.vol;
+      rvol_.y = v.rvol;
+      rvol_.ok = rvol_.ok_big = rt.big != 0;
+      rvol = &rvol_;
+    } else if (di == 0 && dj == 0 && dk == 0) {
       vol_ph = sc.cellvol;
     } else {
       const double path = sc_path(di, dj, dk) * sc.dr1;
@@ -220,12 +237,14 @@
             photoion_rates_multi<HEAT>(*bd, ss, cin_HI, cout_HI, cin_HeI, cout_HeI, cin_HeII, cout_HeII, vol_ph, nf, ric, o, &s_logtab[0], pins);
         } else {
           // gathers first (band_positions_gathers_first) where the registers allow it: the isothermal kernel
+          // (... which then read the table's pair copy, rt.pairs, in the table's place: band_positions_gathers_first)
+          const double *const thick = !HEAT ? (const double *)rt.pairs : ss.photo_thick[0];
           if constexpr (EXPT)
-            photoion_rates<HEAT, gm::LogEntryExp, BandData, !HEAT>(*bd, ss.photo_thick[0], ss.photo_thin[0], ss.heat_thick[0], ss.heat_thin[0], cin_HI, cout_HI,
-                                                                      cin_HeI, cout_HeI, cin_HeII, cout_HeII, vol_ph, flux(S.nflux), ric, o, &logx, pins);
+            photoion_rates<HEAT, gm::LogEntryExp, BandData, !HEAT>(*bd, thick, ss.photo_thin[0], ss.heat_thick[0], ss.heat_thin[0], cin_HI, cout_HI,
+                                                                      cin_HeI, cout_HeI, cin_HeII, cout_HeII, vol_ph, flux(S.nflux), ric, o, &logx, pins, rvol);
           else
-            photoion_rates<HEAT, gm::LogEntry, BandData, !HEAT>(*bd, ss.photo_thick[0], ss.photo_thin[0], ss.heat_thick[0], ss.heat_thin[0], cin_HI, cout_HI,
-                                                                     cin_HeI, cout_HeI, cin_HeII, cout_HeII, vol_ph, flux(S.nflux), ric, o, &s_logtab[0], pins);
+            photoion_rates<HEAT, gm::LogEntry, BandData, !HEAT>(*bd, thick, ss.photo_thin[0], ss.heat_thick[0], ss.heat_thin[0], cin_HI, cout_HI,
+                                                                     cin_HeI, cout_HeI, cin_HeII, cout_HeII, vol_ph, flux(S.nflux), ric, o, &s_logtab[0], pins, rvol);
         }
         if (PARK) { // (volatile: read here, not hoisted back into registers)
           volatile __attribute__((address_space(3))) double *dn = (volatile __attribute__((address_space(3))) double *)&s_den[threadIdx.x];

@@ -438,4 +438,17 @@ C2R_HD double interp_column_fast(const double (&s)[4], double c1, double c2, dou
   return (c1 * w1 + c2 * w2 + c3 * w3 + c4 * w4) / (w1 + w2 + w3 + w4);
 }
 
+// The shell volume vol_ph of a cell at offset (di, dj, dk) from a source (evolve_point.F90:199-207) and its reciprocal
+// depend on (|di|, |dj|, |dk|), the three cell sizes and the cell's volume only: the same for every source, pass and outer
+// iteration of a time step.  The all-periodic rates kernel reads them from a table per offset (k_shell_volumes,
+// c2ray_hip.hip), 16 bytes an entry, indexed by the three magnitudes with |di| fastest.  An axis of n cells whose offsets run
+// from -l to n - 1 - l holds the magnitudes 0 .. max(l, n - 1 - l).
+struct alignas(16) ShellVol {
+  double vol, rvol; // vol_ph, RN(1.0 / vol_ph)
+};
+C2R_HD int shell_vol_extent(int n, int l) { return (l > n - 1 - l ? l : n - 1 - l) + 1; }
+C2R_HD size_t shell_vol_index(int ia, int ja, int ka, int e1, int e2) {
+  return (size_t)ia + (size_t)e1 * ((size_t)ja + (size_t)e2 * (size_t)ka);
+}
+
 } // namespace c2r
