@@ -2494,9 +2494,10 @@ static int set_sources_one(c2r_ctx *c, int nsrc, const int *srcpos, const double
   // What the last pass learnt about each source -- how many sub-boxes it needed: the size of its column block and the
   // rounds that are swept without waiting for a loss probe -- stays valid across time steps as long as the source list
   // is the same (the reference's driver passes the same list at every evolve3D call of a redshift slice); a wrong
-  // guess costs time, never a bit.  Forgetting it made every evolve3D call after the first regrow its column blocks
-  // and probe every round again: 2.7 ms per iteration over the 8-9 iterations of such a call (round 3's
-  // dropin timing: 26.0 against 23.1 ms).
+  // guess costs time, never a bit (tests/test_gpu_step_sequence.py holds it to that: gas that turns opaque or transparent
+  // under learnt counts, a new source on a cell with a count).  Forgetting it made every evolve3D call after the first
+  // regrow its column blocks and probe every round again: 2.7 ms per iteration over the 8-9 iterations of such a call
+  // (round 3's dropin timing: 26.0 against 23.1 ms).
   const bool same_list = nsrc == c->nsrc && c->srcpos.size() == 3 * (size_t)nsrc &&
                          std::equal(srcpos, srcpos + 3 * (size_t)nsrc, c->srcpos.begin());
   if (!same_list) {

@@ -320,14 +320,21 @@ class HipEngine:
         self._chk(self.lib.c2r_set_step(self.h, _dp(nd), dr, float(grid.vol), float(mat.clumping), float(cosmo.zred),
                                         float(cosmo.H0), float(cosmo.Omega0), int(bool(mat.isothermal)),
                                         float(mat.temper_val), _dp(rc)))
+        self.set_lls(mat)
+        self.set_clumping_grid(mat)
+
+    def set_lls(self, mat: Material):
+        """c2r_set_lls from mat.use_LLS, coldensh_LLS and LLS_grid: in force until the next call (set_step makes it)."""
         lls = None if mat.LLS_grid is None else np.ascontiguousarray(mat.LLS_grid, dtype=np.float32).reshape(-1)
-        cg = None if mat.clumping_grid is None else np.ascontiguousarray(mat.clumping_grid, dtype=np.float32).reshape(-1)
         assert lls is None or lls.size == self.ncell
-        assert cg is None or cg.size == self.ncell
-        fp = C.POINTER(C.c_float)
         self._chk(self.lib.c2r_set_lls(self.h, int(bool(mat.use_LLS)), float(mat.coldensh_LLS),
-                                       None if lls is None else lls.ctypes.data_as(fp)))
-        self._chk(self.lib.c2r_set_clumping_grid(self.h, None if cg is None else cg.ctypes.data_as(fp)))
+                                       None if lls is None else lls.ctypes.data_as(C.POINTER(C.c_float))))
+
+    def set_clumping_grid(self, mat: Material):
+        """c2r_set_clumping_grid from mat.clumping_grid (None: the scalar clumping again); set_step makes the call too."""
+        cg = None if mat.clumping_grid is None else np.ascontiguousarray(mat.clumping_grid, dtype=np.float32).reshape(-1)
+        assert cg is None or cg.size == self.ncell
+        self._chk(self.lib.c2r_set_clumping_grid(self.h, None if cg is None else cg.ctypes.data_as(C.POINTER(C.c_float))))
 
     def set_step_scalars(self, mat: Material, grid: GridProps, cosmo: Cosmology):
         """c2r_set_step without the density: what is on the device stays (see scale_ndens)."""
