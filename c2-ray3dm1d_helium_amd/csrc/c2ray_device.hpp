@@ -582,11 +582,20 @@ C2R_HD double log_table_path_of(const gm::Log10Arg &a, const gm::LogEntryExp *ta
 C2R_HD double log10_finish_of(const gm::Log10Arg &a, double lg, const double *) { return gm::log10_finish(a, lg); }
 C2R_HD double log10_finish_of(const gm::Log10Arg &a, double lg, const gm::LogEntry *) { return gm::log10_finish(a, lg); }
 C2R_HD double log10_finish_of(const gm::Log10Arg &a, double lg, const gm::LogEntryExp *tab) { return gm::log10_finish(a, lg, tab->exp); }
+// A fourth form (const gm::LogFoldExp *; the all-periodic isothermal one-SED k_rates alone): the log table with its power of two folded
+// into the reciprocal, and a split that yields the exponent table's byte offset in the place of log10's power of two
+// (c2ray_math.hpp, above LogFold; DESIGN 3.2, "Folded reciprocal and one-subtraction split").  The split is chosen by the
+// table's type like the rest.
+template <class LT>
+C2R_HD gm::Log10Arg log10_split_of(double x, const LT *) { return gm::log10_split(x); }
+C2R_HD gm::Log10ArgFold log10_split_of(double x, const gm::LogFoldExp *tab) { return gm::log10_split_fold(x, tab->fold); }
+C2R_HD double log_table_path_of(const gm::Log10ArgFold &a, const gm::LogFoldExp *tab, const gm::LogPins *pins) { return gm::log_table_path_fold(a, tab->tab, pins); }
+C2R_HD double log10_finish_of(const gm::Log10ArgFold &a, double lg, const gm::LogFoldExp *tab) { return gm::log10_finish(a, lg, tab->exp0); }
 
 template <class LT>
 C2R_HD void tau_table_positions(double tau_a, double tau_b, const LT *logtab, TauPos &pa, TauPos &pb,
                                 const gm::LogPins *pins = nullptr) {
-  const gm::Log10Arg a = gm::log10_split(dmax_const(tau_a, 1.0e-20)), b = gm::log10_split(dmax_const(tau_b, 1.0e-20));
+  const auto a = log10_split_of(dmax_const(tau_a, 1.0e-20), logtab), b = log10_split_of(dmax_const(tau_b, 1.0e-20), logtab);
   double lga = log_table_path_of(a, logtab, pins), lgb = log_table_path_of(b, logtab, pins);
   const bool na = gm::log10_near1(a), nb = gm::log10_near1(b);
   C2R_COUNT_LANES(12, na || nb);

@@ -316,6 +316,102 @@ struct LogEntryExp {
   const LogEntry *tab;
   const Log10Exp *exp;
 };
+// The isothermal one-SED k_rates with all axes periodic takes two more steps out of the integer bookkeeping of a logarithm
+// (everything from here to LogFoldExp; no other kernel uses it).
+// 1. The power of two folded into the reciprocal.  log_table_path4 uses z = x' * 2^-k (k in {-1, 0, 1}, LogEntry::kshift) in
+//    one place, r = fma(z, invc, -1).  invc * 2^-k is exact, so fma(x', invc * 2^-k, -1) is the same real number rounded
+//    once: the same bits, without kshift, its read and the subtraction.  A LogFold entry holds {invc * 2^-k, w, c} at the
+//    pitch of LogEntry (the index arithmetic stays), read as one 16-byte and one 8-byte piece.
+// 2. hx by a select, and the exponent table's offset from the same subtraction.  hx of log10_split is the mantissa of x
+//    under the exponent field of [0.5, 1) for x < 1 and of [1, 2) otherwise; hi - hx is then ky << 20, and its arithmetic
+//    shift by 16 the byte offset ky << 4 into the exponent table, counted from the entry of ky = 0.  ky itself is not formed.
+struct LogFold {
+  double invc, w, c; // invc * 2^-k; w and c as in LogEntry
+  uint64_t pad;
+};
+C2R_MHD LogFold make_log_fold(int E) { // E in [0, 256)
+  const LogEntry e = make_log_entry(E);
+  const int k = (E - 0x30) >> 7; // as make_log_entry has it
+  LogFold f;
+  f.invc = e.invc * (k < 0 ? 2.0 : (k > 0 ? 0.5 : 1.0)); // exact
+  f.w = e.w;
+  f.c = e.c;
+  f.pad = 0;
+  return f;
+}
+struct Log10ArgFold {
+  uint32_t hx, lo; // as in Log10Arg
+  int xoff;        // ky << 4: the byte offset of ky's pair from the pair of ky = 0
+};
+// the two exponent fields of the select, for a kernel that holds them in vector registers (pin_fold_constants): as operands
+// of a v_cndmask_b32 they must be there, and left to itself the compiler copies them anew for every logarithm
+struct FoldPins {
+  uint32_t below, above; // 0x3FE00000, 0x3FF00000
+};
+#if defined(__HIP_DEVICE_COMPILE__)
+__device__ __forceinline__ FoldPins pin_fold_constants() {
+  FoldPins p;
+  asm volatile("v_mov_b32 %0, %1" : "=v"(p.below) : "s"(0x3FE00000u));
+  asm volatile("v_mov_b32 %0, %1" : "=v"(p.above) : "s"(0x3FF00000u));
+  return p;
+}
+// one compare and one v_cndmask_b32, nothing else
+__device__ __forceinline__ uint32_t fold_exponent_field(uint32_t hi, const FoldPins &p) {
+  uint32_t sel;
+  asm("v_cmp_gt_u32 vcc, %3, %1\n\tv_cndmask_b32 %0, %3, %2, vcc" : "=v"(sel) : "v"(hi), "v"(p.below), "v"(p.above) : "vcc");
+  return sel;
+}
+#else
+inline FoldPins pin_fold_constants() { return FoldPins{0x3FE00000u, 0x3FF00000u}; }
+inline uint32_t fold_exponent_field(uint32_t hi, const FoldPins &p) { return hi < p.above ? p.below : p.above; }
+#endif
+C2R_MHD Log10ArgFold log10_split_fold(double x, const FoldPins *fp = nullptr) { // x positive, normal, finite
+  const uint64_t ix = asuint64(x);
+  const uint32_t hi = (uint32_t)(ix >> 32);
+  Log10ArgFold a;
+  a.lo = (uint32_t)ix;
+  const uint32_t field = fp ? fold_exponent_field(hi, *fp) : (hi < 0x3FF00000u ? 0x3FE00000u : 0x3FF00000u);
+  a.hx = (hi & 0x000FFFFFu) | field;
+  a.xoff = (int)(hi - a.hx) >> 16;
+  return a;
+}
+C2R_MHD bool log10_near1(const Log10ArgFold &a) { return a.hx - 0x3FEE0000u < 0x00030900u; }
+C2R_MHD double log10_arg_value(const Log10ArgFold &a) { return asdouble(((uint64_t)a.hx << 32) | a.lo); }
+// log_table_path4 with z = x' and no kshift
+C2R_MHD double log_table_path_fold(const Log10ArgFold &a, const LogFold *tab, const LogPins *pins = nullptr) {
+  const double *A = GMT(log_hdr) + 2;
+  const double A1 = pins ? pins->a1 : A[1], A3 = pins ? pins->a3 : A[3];
+  const uint32_t T = a.hx - 0x3FE00000u;  // [0, 0x200000)
+  const uint32_t off = (T >> 8) & 0x1FE0u; // entry T >> 13 of 32-byte entries
+  const LogFold *e = (const LogFold *)((const char *)tab + off);
+  const double invc = e->invc, w = e->w, c = e->c;
+  const double r = fma_(log10_arg_value(a), invc, -1.0);
+  const double t1 = fma_kc(r, A[2], A1);
+  const double hi_ = r + w;
+  const double r2 = r * r;
+  double lo_ = (w - hi_) + r;
+  lo_ = lo_ + c;
+  const double r3 = r * r2;
+  const double t2 = fma_kc(r, A[4], A3);
+  const double s_ = fma_(r2, A[0], lo_);
+  const double p_ = fma_(t2, r2, t1);
+  const double q_ = fma_(r3, p_, s_);
+  return q_ + hi_;
+}
+// `x0`: the pair of ky = 0, entry -LOG10_KY_LO of a table filled like Log10Exp's; precondition as there
+C2R_MHD double log10_finish(const Log10ArgFold &a, double lg, const Log10Exp *x0) {
+  const double ivln10 = asdouble(0x3FDBCB7B1526E50EULL);
+  const Log10Exp *e = (const Log10Exp *)((const char *)x0 + a.xoff);
+  const double ylo = e->ylo, yhi = e->yhi;
+  const double zz = ylo + ivln10 * lg;
+  return zz + yhi;
+}
+// the folded table, the exponent table from its ky = 0 entry, and the select's two constants: a type of its own again
+struct LogFoldExp {
+  const LogFold *tab;
+  const Log10Exp *exp0;
+  const FoldPins *fold;
+};
 // log10_norm: the caller guarantees a positive, normal, finite argument (tau_table_position passes
 // max(1e-20, tau)); log10_pos adds the check and falls back to log10_.
 C2R_MHD double log10_norm(double x, const double *tab) {

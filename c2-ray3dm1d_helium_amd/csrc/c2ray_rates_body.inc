@@ -15,15 +15,27 @@
   // `tile_ptr` / `tile_src`: for each listed tile the sources (positions in `src`, ascending = source order)
   // whose sub-box reaches into it, so that a batch of hundreds of faint sources costs a cell only the sources
   // near it.  Without lists every cell walks all nsrc sources of the batch (few sources, boxes that fill the mesh).
-  // the (invc, logc) table of the bit-exact log in LDS, with the log's power of two folded in (gm::LogEntry, 8 KB): two
-  // gathers per band iteration that no longer queue behind the photo-table gathers in the vector memory path
-  __shared__ gm::LogEntry s_logtab[256];
-  s_logtab[threadIdx.x] = gm::make_log_entry((int)threadIdx.x);
   // k_rates, isothermal, one SED (ISO1; its beam and curve twins stay the kernels they were): the exponent terms of
   // log10's tail are read from a table (gm::Log10Exp, 17 KB) that each block fills here with the multiplications the table
   // replaces -- per band six FP64-rate instructions less and two integer ones more -- and the four registers that the two
   // pairs need come from the cell's denominators, which wait in LDS (below)
   constexpr bool ISO1 = !HEAT && !MULTI && !BEAM;
+  // ... and, with all axes periodic (FOLD), its log table holds the reciprocal with the power of two folded in as well
+  // (gm::LogFold: the same pitch, no kshift) and its split hands down the exponent table's byte offset (gm::LogFoldExp).
+  // The open-boundary twin stays the kernel it was: the same route brings it from 92 to 94 registers, with or without the
+  // select's constants pinned, past the budget of 93 (tests/test_rates_registers.py).
+  constexpr bool FOLD = ISO1 && !OPEN;
+  // the (invc, logc) table of the bit-exact log in LDS, with the log's power of two folded in (gm::LogEntry, 8 KB): two
+  // gathers per band iteration that no longer queue behind the photo-table gathers in the vector memory path
+  using LogTab = std::conditional_t<FOLD, gm::LogFold, gm::LogEntry>;
+  __shared__ LogTab s_logtab[256];
+  if constexpr (FOLD) s_logtab[threadIdx.x] = gm::make_log_fold((int)threadIdx.x);
+  else s_logtab[threadIdx.x] = gm::make_log_entry((int)threadIdx.x);
+  // (what every other kernel hands down)
+  [[maybe_unused]] const gm::LogEntry *const logtab4 = [&]() -> const gm::LogEntry * {
+    if constexpr (FOLD) return nullptr;
+    else return &s_logtab[0];
+  }();
   constexpr bool EXPT = ISO1;
   // ... and k_rates with one SED and all axes periodic reads the shell volume of a cell.source from a table (below)
   constexpr bool SHELLTAB = !MULTI && !BEAM && !OPEN;
@@ -32,7 +44,14 @@
     for (int e = (int)threadIdx.x; e < gm::LOG10_NEXP; e += BLOCK) s_exptab[e] = gm::make_log10_exp(gm::LOG10_KY_LO + e);
   }
   __syncthreads();
-  [[maybe_unused]] const gm::LogEntryExp logx = {&s_logtab[0], &s_exptab[0]};
+  // the two exponent fields of the split's select, in vector registers for the whole kernel (gm::FoldPins)
+  [[maybe_unused]] gm::FoldPins fold_ = {0u, 0u};
+  if constexpr (FOLD) fold_ = gm::pin_fold_constants();
+  [[maybe_unused]] const auto logx = [&]() {
+    if constexpr (FOLD) return gm::LogFoldExp{&s_logtab[0], &s_exptab[EXPT ? -gm::LOG10_KY_LO : 0], &fold_};
+    else if constexpr (EXPT) return gm::LogEntryExp{&s_logtab[0], &s_exptab[0]};
+    else return 0;
+  }();
   // the band data as uploaded (a BandDataByRow: the plain arrays and, behind them, the same numbers band by band); a kernel
   // chooses its reading of them by the TYPE it hands down -- the base for the array form (an upcast, not a reinterpretation)
   const BandData *const bd = bdr;
@@ -229,22 +248,22 @@
             volatile __attribute__((address_space(3))) double *const pf = (volatile __attribute__((address_space(3))) double *)&s_flux[threadIdx.x];
             *pf = cf;
             photoion_rates_multi<HEAT>(*bdr, ss, cin_HI, cout_HI, cin_HeI, cout_HeI, cin_HeII, cout_HeII,
-                                       vol_ph, LaneFlux{S, pf}, ric, o, &s_logtab[0], pins);
+                                       vol_ph, LaneFlux{S, pf}, ric, o, logtab4, pins);
           } else if constexpr (HEAT) // this kernel reads cross sections and factors band by band (BandDataByRow)
             photoion_rates_multi<HEAT>(*bdr, ss, cin_HI, cout_HI, cin_HeI, cout_HeI, cin_HeII, cout_HeII,
-                                       vol_ph, nf, ric, o, &s_logtab[0], pins);
+                                       vol_ph, nf, ric, o, logtab4, pins);
           else
-            photoion_rates_multi<HEAT>(*bd, ss, cin_HI, cout_HI, cin_HeI, cout_HeI, cin_HeII, cout_HeII, vol_ph, nf, ric, o, &s_logtab[0], pins);
+            photoion_rates_multi<HEAT>(*bd, ss, cin_HI, cout_HI, cin_HeI, cout_HeI, cin_HeII, cout_HeII, vol_ph, nf, ric, o, logtab4, pins);
         } else {
           // gathers first (band_positions_gathers_first) where the registers allow it: the isothermal kernel
           // (... which then read the table's pair copy, rt.pairs, in the table's place: band_positions_gathers_first)
           const double *const thick = !HEAT ? (const double *)rt.pairs : ss.photo_thick[0];
           if constexpr (EXPT)
-            photoion_rates<HEAT, gm::LogEntryExp, BandData, !HEAT>(*bd, thick, ss.photo_thin[0], ss.heat_thick[0], ss.heat_thin[0], cin_HI, cout_HI,
+            photoion_rates<HEAT, std::conditional_t<FOLD, gm::LogFoldExp, gm::LogEntryExp>, BandData, !HEAT>(*bd, thick, ss.photo_thin[0], ss.heat_thick[0], ss.heat_thin[0], cin_HI, cout_HI,
                                                                       cin_HeI, cout_HeI, cin_HeII, cout_HeII, vol_ph, flux(S.nflux), ric, o, &logx, pins, rvol);
           else
             photoion_rates<HEAT, gm::LogEntry, BandData, !HEAT>(*bd, thick, ss.photo_thin[0], ss.heat_thick[0], ss.heat_thin[0], cin_HI, cout_HI,
-                                                                     cin_HeI, cout_HeI, cin_HeII, cout_HeII, vol_ph, flux(S.nflux), ric, o, &s_logtab[0], pins, rvol);
+                                                                     cin_HeI, cout_HeI, cin_HeII, cout_HeII, vol_ph, flux(S.nflux), ric, o, logtab4, pins, rvol);
         }
         if (PARK) { // (volatile: read here, not hoisted back into registers)
           volatile __attribute__((address_space(3))) double *dn = (volatile __attribute__((address_space(3))) double *)&s_den[threadIdx.x];
