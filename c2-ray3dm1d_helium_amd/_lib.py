@@ -164,6 +164,12 @@ SYMBOLS = {
     "c2r_download_plane_exit_flux": (C.c_int, [C.c_void_p, C.c_int, _dp]),
     "c2r_set_plane_curve": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(PlaneCurve)]),
     "c2r_get_plane_curve": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(PlaneCurve)]),
+    "c2r_set_plane_side_entry": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, _dp]),
+    "c2r_enable_plane_side_exit": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "c2r_download_plane_side_exit": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, _dp]),
+    "c2r_enable_plane_side_loss": (C.c_int, [C.c_void_p, C.c_int]),
+    "c2r_get_plane_side_loss_enabled": (C.c_int, [C.c_void_p]),
+    "c2r_get_plane_side_loss": (C.c_int, [C.c_void_p, C.c_int, _dp]),
     "c2r_enable_face_loss": (C.c_int, [C.c_void_p, C.c_int]),
     "c2r_get_face_loss_enabled": (C.c_int, [C.c_void_p]),
     "c2r_download_face_loss": (C.c_int, [C.c_void_p, C.c_int, _dp]),

@@ -16,6 +16,7 @@
 //   tables         k_build_tables  spec_integration: the photo-ionisation / heating tables of one SED
 //   plane sources  k_plane_columns, k_plane_layer, k_plane_rates, k_plane_exit   a plane wave entering through an open mesh
 //                                  face (c2ray_planes.inc): the march along the axis, its rates, what leaves through the far face
+//                                  (and, k_pside_loss, through the open side faces of a tilted plane)
 //   escape maps    k_face_loss     the kept loss of an open box per cell of the mesh face it leaves through
 //                                  (c2r_enable_face_loss): a gather, one lane per face cell, the sources in source order
 //   horizon loss   k_horizon_rim   what crosses the photon horizon of each source that has one (c2r_enable_horizon_loss): one
@@ -47,6 +48,7 @@
 #include "c2ray_rim.hpp"
 #include "c2ray_plane.hpp"
 #include "c2ray_pcurve.hpp"
+#include "c2ray_pside.hpp"
 #include "c2ray_shell.hpp"
 
 using namespace c2r;
@@ -1799,6 +1801,21 @@ struct c2r_ctx {
     bool curve_set = false;
     double loss = 0.0;                // the term the plane added to photon_loss(1) in the last pass that ran it
     long long stamp = 0;              // ... and which pass that was (as trace_stamp)
+    // side entry (c2r_set_plane_side_entry): the ghost strips of side 0, side 1 and the corner line, na slots of 3 x L each
+    // (L = fb, fa, 1); made by the call that sets a strip first, never inside a pass
+    double *d_side_in[3] = {}, *d_side_inf[3] = {}; // columns, fluxes
+    bool side_in_set[3] = {false, false, false}, side_inf_set[3] = {false, false, false};
+    bool side_inf_uses[3][2] = {};    // some entry of SED 1 / SED 2 of that flux strip is non-zero
+    // side exit (c2r_enable_plane_side_exit): the strips of side 0 and side 1 in the entry layout, made by the enabling call
+    bool side_out_on = false;
+    double *d_side_out[2] = {}, *d_side_outf[2] = {};
+    bool side_out_valid = false;      // a pass has run the plane with the strips enabled ...
+    bool side_out_live[2] = {false, false}; // ... with these sides live ...
+    bool side_out_mapped = false;     // ... and with a map (the flux strips hold that pass's)
+    // side loss (c2r_enable_plane_side_loss): what the plane added to photon_loss(1) through side 0 and side 1 in the last
+    // pass that ran it; side_ran: the side was live in the pass in flight (its sum is on its way to h_side_loss)
+    double side_loss[2] = {0.0, 0.0};
+    bool side_ran[2] = {false, false};
   };
   int nplane = 0;
   Plane plane[PLANE_MAX];
@@ -1810,6 +1827,10 @@ struct c2r_ctx {
   double *d_plane_partial = nullptr; // block sums of the exit loss
   double *d_plane_loss = nullptr, *h_plane_loss = nullptr; // PLANE_MAX each (h: pinned): the exit loss of the pass in flight
   std::vector<int> pass_planes;     // planes (0-based) of the pass in flight, in order
+  // side loss of tilted planes (c2r_enable_plane_side_loss; the rule is c2ray_pside.hpp): made by the enabling call
+  bool side_loss_on = false;
+  double *d_side_partial = nullptr; // block sums of one side's terms (the largest mesh face)
+  double *d_side_loss = nullptr, *h_side_loss = nullptr; // 2 PLANE_MAX each (h: pinned): [2 p + side] of the pass in flight
 
   // escape maps (c2r_enable_face_loss): the maps of the open faces one behind the other, in face order (face_map_offset,
   // c2ray_face.hpp); made by c2r_enable_face_loss and made anew by a change of boundary mode: never allocated inside a pass
@@ -2203,6 +2224,7 @@ static void free_horizon_loss(c2r_ctx *c) {
 }
 
 static void free_plane_buffers(c2r_ctx *c); // c2ray_planes.inc
+static void free_side_loss(c2r_ctx *c);     // c2ray_planes.inc
 
 extern "C" void c2r_destroy(c2r_ctx *c) {
   if (!c) return;
@@ -2258,6 +2280,7 @@ extern "C" void c2r_destroy(c2r_ctx *c) {
       if (q) (void)hipHostFree(q);
   }
   free_plane_buffers(c);
+  free_side_loss(c);
   free_face_maps(c);
   free_horizon_loss(c);
   if (c->h_conv) (void)hipHostFree(c->h_conv);
@@ -4223,6 +4246,11 @@ static int pass_finish(c2r_ctx *c) {
   for (int p : c->pass_planes) { // the planes came first
     c->plane[p].loss = c->h_plane_loss[p];
     c->photon_loss[0] = c->photon_loss[0] + c->plane[p].loss;
+    if (c->side_loss_on) // behind the far loss: side 0, then side 1 (0.0 for a side that was not live)
+      for (int s = 0; s < 2; s++) {
+        c->plane[p].side_loss[s] = c->plane[p].side_ran[s] ? c->h_side_loss[2 * p + s] : 0.0;
+        c->photon_loss[0] = c->photon_loss[0] + c->plane[p].side_loss[s];
+      }
   }
   c->pass_planes.clear();
   for (const c2r_ctx::BatchTail &bt : c->tails)

@@ -195,4 +195,49 @@ C2R_HD void plane_layer_flux(const PlaneTilt &T, int fa, int fb, int u, int v, c
   }
 }
 
+// Side entry (c2r_set_plane_side_entry, include/c2ray_hip.h): what a corner that falls outside an open side face reads
+// instead of 0.0 -- the ghost cells of the layer before, handed in by the mesh that stands there.  One slot of the strips:
+// side[0]: 3 x fb values at the corner's index along g (outside along f only), side[1]: 3 x fa values at its index along f
+// (outside along g only), corner: 3 values (outside along both); the species or the SED slowest.  A null pointer is a strip
+// that is not set, or whose side is not live in this pass: 0.0, as ever.
+struct PlaneGhost {
+  const double *side[2];
+  const double *corner;
+};
+
+// the value of species or SED k at the corner (uu, vv) of plane_layer_in (-1: outside an open side face); `prev` null: zero
+C2R_HD double plane_corner_value(const double *prev, const PlaneGhost &gh, int k, int fa, int fb, int uu, int vv) {
+  if (uu >= 0 && vv >= 0) return prev ? prev[k * (fa * fb) + uu + fa * vv] : 0.0;
+  if (vv >= 0) return gh.side[0] ? gh.side[0][k * fb + vv] : 0.0;
+  if (uu >= 0) return gh.side[1] ? gh.side[1][k * fa + uu] : 0.0;
+  return gh.corner ? gh.corner[k] : 0.0;
+}
+
+// plane_layer_in with ghost cells: the same four corners, the same plane_interp
+C2R_HD void plane_layer_in(const PlaneTilt &T, int fa, int fb, int u, int v, const double *prev, const PlaneGhost &gh, double &c_HI,
+                           double &c_HeI, double &c_HeII) {
+  const int uu = plane_upstream(u, T.e_f, fa, T.wrap_f), vv = plane_upstream(v, T.e_g, fb, T.wrap_g);
+  double c[3][4];
+  for (int k = 0; k < 3; k++) {
+    c[k][0] = plane_corner_value(prev, gh, k, fa, fb, uu, vv);
+    c[k][1] = plane_corner_value(prev, gh, k, fa, fb, u, vv);
+    c[k][2] = plane_corner_value(prev, gh, k, fa, fb, uu, v);
+    c[k][3] = plane_corner_value(prev, gh, k, fa, fb, u, v);
+  }
+  c_HI = plane_interp(T.s, c[0][0], c[0][1], c[0][2], c[0][3], sigma_HI_at_ion_freq);
+  c_HeI = plane_interp(T.s, c[1][0], c[1][1], c[1][2], c[1][3], sigma_HeI_at_ion_freq);
+  c_HeII = plane_interp(T.s, c[2][0], c[2][1], c[2][2], c[2][3], sigma_HeII_at_ion_freq);
+}
+
+// plane_layer_flux with ghost cells (`gh`: the flux strips)
+C2R_HD void plane_layer_flux(const PlaneTilt &T, int fa, int fb, int u, int v, const double *fprev, const PlaneGhost &gh,
+                             double (&nf)[NSED]) {
+  const int uu = plane_upstream(u, T.e_f, fa, T.wrap_f), vv = plane_upstream(v, T.e_g, fb, T.wrap_g);
+  for (int k = 0; k < NSED; k++) {
+    const double F1 = plane_corner_value(fprev, gh, k, fa, fb, uu, vv), F2 = plane_corner_value(fprev, gh, k, fa, fb, u, vv),
+                 F3 = plane_corner_value(fprev, gh, k, fa, fb, uu, v), F4 = plane_corner_value(fprev, gh, k, fa, fb, u, v);
+    nf[k] = F1 * T.s[0] + F2 * T.s[1] + F3 * T.s[2] + F4 * T.s[3];
+  }
+}
+
 } // namespace c2r

@@ -5,10 +5,13 @@
 // face and travels along one axis, every line of cells a 1-D problem of its own.  Three stages per plane and pass, all on
 // the sweep stream, one kernel each:
 //   the march   k_plane_columns   one lane per line of cells, or for a tilted plane (c2r_set_plane_tilt)
-//               k_plane_layer     one launch per layer; <true> carries the flux of a map along (c2r_set_plane_flux_map)
+//               k_plane_layer     one launch per layer; <true> carries the flux of a map along (c2r_set_plane_flux_map);
+//               k_pside_layer     in its place where the plane reads the ghost strips of a neighbouring mesh or stores its edge
+//                                 cells for the next one (c2r_set_plane_side_entry, c2r_enable_plane_side_exit)
 //   the rates   k_plane_rates     no dependencies, one lane per cell; the flux uniform, by face cell or by cell (PlaneFlux)
 //   the loss    k_plane_exit      what leaves through the far face; the flux of a map or uniform (MAPPED), the per-line
 //                                 term also kept in the escape map of that face (KEEP, c2r_enable_face_loss)
+//               k_pside_loss      what a tilted plane loses through its live open side faces (c2r_enable_plane_side_loss)
 // A plane with a light curve (c2r_set_plane_curve, c2ray_pcurve.hpp) runs k_pcurve_rates and k_pcurve_exit for the last two.
 namespace {
 
@@ -79,6 +82,56 @@ k_plane_layer(PlaneGeom G, PlaneTilt T, StepScalars sc, int m, size_t nc, const 
   const size_t q = (size_t)u * G.sf + (size_t)v * G.sg + (size_t)along * G.sa;
   double c_HI, c_HeI, c_HeII;
   plane_layer_in(T, G.fa, G.fb, u, v, prev, c_HI, c_HeI, c_HeII);
+  const double lls = sc.use_lls ? (lls_grid ? (double)lls_grid[q] : sc.coldensh_lls) : 0.0;
+  double o_HI, o_HeI, o_HeII;
+  plane_cell_columns(ndens[q], xh_av[q], xhe_av[q], xhe_av[q + nc], T.path, sc.dr1, sc.use_lls, lls, c_HI, c_HeI, c_HeII, o_HI, o_HeI,
+                     o_HeII);
+  cin_out[3 * q] = c_HI;
+  cin_out[3 * q + 1] = c_HeI;
+  cin_out[3 * q + 2] = c_HeII;
+  next[f] = o_HI;
+  next[face + f] = o_HeI;
+  next[2 * face + f] = o_HeII;
+  if constexpr (FLUX)
+    for (int k = 0; k < NSED; k++) {
+      cell_flux[3 * q + k] = nf[k];
+      fnext[k * face + f] = nf[k];
+    }
+}
+
+// k_plane_layer for a plane that reads or writes side strips (side entry and side exit, c2r_set_plane_side_entry /
+// c2r_enable_plane_side_exit): the same launch, the same statements, and two differences.  A corner outside an open side face
+// reads the ghost strips of this layer's slot instead of 0.0 (the ghost-aware plane_layer_in / plane_layer_flux), and the lanes
+// on the downstream edge of a live side store the corner c4 / F4 they have just loaded -- their own cell of the layer before --
+// into the exit strips' slot m.  A kernel of its own, as the curved plane's are: a plane without strips runs k_plane_layer.
+struct PlaneSideDev {
+  PlaneGhost gc, gf;     // the ghost columns and ghost fluxes of slot m (null: 0.0)
+  double *xc[2], *xf[2]; // the exit strips of side 0 / 1 at slot m: 3 x fb / 3 x fa columns, fluxes (null: not stored)
+  int edge_f, edge_g;    // the downstream edge index of each side
+};
+template <bool FLUX>
+__global__ void __launch_bounds__(PLANE_LAYER_BX * PLANE_LAYER_BY)
+k_pside_layer(PlaneGeom G, PlaneTilt T, StepScalars sc, int m, size_t nc, const double *__restrict__ ndens,
+              const double *__restrict__ xh_av, const double *__restrict__ xhe_av, const float *__restrict__ lls_grid,
+              const double *__restrict__ prev, double *__restrict__ cin_out, double *__restrict__ next,
+              const double *__restrict__ fprev, double *__restrict__ cell_flux, double *__restrict__ fnext, PlaneSideDev sd) {
+  const int u = (int)blockIdx.x * PLANE_LAYER_BX + (int)threadIdx.x, v = (int)blockIdx.y * PLANE_LAYER_BY + (int)threadIdx.y;
+  if (u >= G.fa || v >= G.fb) return;
+  [[maybe_unused]] double nf[NSED];
+  if constexpr (FLUX) plane_layer_flux(T, G.fa, G.fb, u, v, fprev, sd.gf, nf);
+  const int face = G.fa * G.fb, f = u + G.fa * v;
+  const int along = G.from_high ? G.na - 1 - m : m;
+  const size_t q = (size_t)u * G.sf + (size_t)v * G.sg + (size_t)along * G.sa;
+  double c_HI, c_HeI, c_HeII;
+  plane_layer_in(T, G.fa, G.fb, u, v, prev, sd.gc, c_HI, c_HeI, c_HeII);
+  for (int k = 0; k < 3; k++) { // the edge lanes hand on their own cell of the layer before
+    if (u == sd.edge_f && sd.xc[0]) sd.xc[0][k * G.fb + v] = prev ? prev[k * face + f] : 0.0;
+    if (v == sd.edge_g && sd.xc[1]) sd.xc[1][k * G.fa + u] = prev ? prev[k * face + f] : 0.0;
+    if constexpr (FLUX) {
+      if (u == sd.edge_f && sd.xf[0]) sd.xf[0][k * G.fb + v] = fprev[k * face + f];
+      if (v == sd.edge_g && sd.xf[1]) sd.xf[1][k * G.fa + u] = fprev[k * face + f];
+    }
+  }
   const double lls = sc.use_lls ? (lls_grid ? (double)lls_grid[q] : sc.coldensh_lls) : 0.0;
   double o_HI, o_HeI, o_HeII;
   plane_cell_columns(ndens[q], xh_av[q], xhe_av[q], xhe_av[q + nc], T.path, sc.dr1, sc.use_lls, lls, c_HI, c_HeI, c_HeII, o_HI, o_HeI,
@@ -324,6 +377,58 @@ k_pcurve_exit(PlaneGeom G, StepScalars sc, double path, PlaneDev pl, const doubl
   if (threadIdx.x == 0) partial[blockIdx.x] = bs;
 }
 
+// Side loss (c2r_enable_plane_side_loss; the rule is c2ray_pside.hpp): what a tilted plane loses through the open side face
+// `side` leaves through.  One lane per cell of that mesh face, in the order of its escape map: the lane's mesh cell is the
+// downstream edge cell behind the face cell, its layer m the cell's place along the plane's axis.  A cell of the layers
+// m <= na - 2 gives plane_exit_term of its own columns (the incoming ones from cin, the outgoing ones formed again by
+// plane_cell_out) and of the flux it used (uniform, or what the layers left per cell; times the curve factor of its layer),
+// times the side's weight; the last layer gives 0.0 (its whole term is the far face's).  The sum as in k_plane_exit: the
+// block's 256 terms in block_sum's tree, the block sums in order by k_loss_finish.  KEEP: map = map + term at the face cell.
+template <bool MULTI, bool MAPPED, bool CURVED, bool KEEP>
+__global__ void __launch_bounds__(BLOCK)
+k_pside_loss(Grid g, PlaneGeom G, PlaneTilt T, StepScalars sc, int side, PlaneDev pl, const double *__restrict__ cell_flux,
+             PlaneCurveDev cv, const double *__restrict__ ndens, const double *__restrict__ xh_av, const double *__restrict__ xhe_av,
+             const BandData *__restrict__ bd, SedSet ss, const double *__restrict__ cin, double *__restrict__ partial,
+             double *__restrict__ map) {
+  __shared__ double sh[BLOCK / 64];
+  const int n[3] = {g.n1, g.n2, g.n3};
+  const int f_ax = face_axis_a(G.axis), g_ax = face_axis_b(G.axis);
+  const int s_ax = side == 0 ? f_ax : g_ax;
+  const int face = pside_face(s_ax, side == 0 ? T.e_f : T.e_g);
+  const int sf = (int)blockIdx.x * BLOCK + (int)threadIdx.x;
+  double term = 0.0;
+  if (sf < face_cells(n, s_ax)) {
+    int mc[3];
+    face_cell_decode(n, face, sf, mc);
+    const int along = face_pick(G.axis, mc[0], mc[1], mc[2]);
+    const int m = G.from_high ? G.na - 1 - along : along;
+    if (m < G.na - 1) {
+      const int u = face_pick(f_ax, mc[0], mc[1], mc[2]), v = face_pick(g_ax, mc[0], mc[1], mc[2]);
+      const size_t q = (size_t)mc[0] + (size_t)g.n1 * ((size_t)mc[1] + (size_t)g.n2 * (size_t)mc[2]);
+      double w0, w1;
+      pside_weights(T, G.fa, G.fb, u, v, w0, w1);
+      double nfu[NSED];
+      for (int s = 0; s < NSED; s++) nfu[s] = MAPPED ? cell_flux[3 * q + s] : pl.nf[s];
+      const double cf = CURVED ? pcurve_factor(cv, m, T.path) : 1.0;
+      if (cf != 0.0 && !plane_dark(nfu)) {
+        double nf[NSED];
+        if constexpr (CURVED) pcurve_fluxes(nfu, cf, nf);
+        else
+          for (int s = 0; s < NSED; s++) nf[s] = nfu[s];
+        double u_HI, u_HeI, u_HeII, o_HI, o_HeI, o_HeII;
+        plane_cell_state(ndens[q], xh_av[q], xhe_av[q], xhe_av[q + g.ncell], u_HI, u_HeI, u_HeII);
+        const double c_HI = cin[3 * q], c_HeI = cin[3 * q + 1], c_HeII = cin[3 * q + 2];
+        plane_cell_out(c_HI, c_HeI, c_HeII, u_HI, u_HeI, u_HeII, T.path, o_HI, o_HeI, o_HeII);
+        const double base = plane_exit_term<MULTI>(*bd, ss, c_HI, o_HI, c_HeI, o_HeI, c_HeII, o_HeII, nf, sc.vol, T.path);
+        term = pside_term(base, side == 0 ? w0 : w1);
+      }
+    }
+    if constexpr (KEEP) map[sf] = map[sf] + term;
+  }
+  const double bs = block_sum(term, sh);
+  if (threadIdx.x == 0) partial[blockIdx.x] = bs;
+}
+
 } // namespace
 
 // ---------------------------------------------------------------------------------------------
@@ -372,7 +477,10 @@ static int run_planes(PassCtx &P, const std::vector<int> &planes) {
     PlaneDev pd;
     for (int s = 0; s < NSED; s++) pd.nf[s] = pl.normflux[s];
     const bool mapped = pn.fmap_set; // a flux map replaces normflux[] (c2r_set_plane_flux_map)
-    const bool uses[2] = {mapped ? pn.fmap_uses[0] : pd.nf[1] != 0.0, mapped ? pn.fmap_uses[1] : pd.nf[2] != 0.0};
+    bool uses[2] = {mapped ? pn.fmap_uses[0] : pd.nf[1] != 0.0, mapped ? pn.fmap_uses[1] : pd.nf[2] != 0.0};
+    if (mapped) // ... or a set side-entry flux strip has a flux of that SED (c2r_set_plane_side_entry)
+      for (int s = 0; s < 3; s++)
+        for (int k = 0; k < 2; k++) uses[k] = uses[k] || (pn.side_inf_set[s] && pn.side_inf_uses[s][k]);
     const bool multi = uses[0] || uses[1];
     for (int k = 0; k < 2; k++) {
       if (uses[k] && !c->have_sed[k]) return fail(c, "plane %d: flux of SED %d without c2r_set_sed_tables(%d)", p + 1, k + 1, k + 1);
@@ -393,14 +501,46 @@ static int run_planes(PassCtx &P, const std::vector<int> &planes) {
     const float *lls = c->lls_on_grid ? c->d_lls : nullptr;
     const double *entry = pn.entry_set ? pn.d_entry : nullptr;
     const double *exit_flux = nullptr; // 3 x face: the flux of the last cell of every line of a plane with a map
+    pn.side_out_valid = pn.side_out_on; // (c2r_download_plane_side_exit: no side is live at normal incidence)
+    pn.side_out_live[0] = pn.side_out_live[1] = false;
+    pn.side_out_mapped = mapped;
     if (tilted) { // one launch per layer, in travel order; with a map the flux is carried along, the last layer's is the exit flux
       const dim3 lgrid((unsigned)((G.fa + PLANE_LAYER_BX - 1) / PLANE_LAYER_BX), (unsigned)((G.fb + PLANE_LAYER_BY - 1) / PLANE_LAYER_BY));
       const double *prev = entry, *fprev = mapped ? pn.d_fmap : nullptr;
+      // side entry and side exit: only a live side's strips are read or written; the corner line needs both sides live.  A plane
+      // that uses neither runs the instances it always ran.
+      const bool live[2] = {pside_live(pn.tilt[0], T.wrap_f), pside_live(pn.tilt[1], T.wrap_g)};
+      const bool ghost_live[3] = {live[0], live[1], live[0] && live[1]};
+      const size_t slot[3] = {3 * (size_t)G.fb, 3 * (size_t)G.fa, 3};
+      bool sides = pn.side_out_on && (live[0] || live[1]);
+      for (int s = 0; s < 3; s++) sides = sides || (ghost_live[s] && pn.side_in_set[s]);
       for (int m = 0; m < G.na; m++) {
         const bool last = m == G.na - 1;
         double *next = last ? pn.d_exit : c->d_plane_layer[m & 1];
         double *fnext = mapped ? (last ? pn.d_fexit : c->d_pflux_layer[m & 1]) : nullptr;
+        PlaneSideDev sd = {};
+        if (sides) {
+          const double *gc[3], *gf[3];
+          for (int s = 0; s < 3; s++) {
+            gc[s] = ghost_live[s] && pn.side_in_set[s] ? pn.d_side_in[s] + (size_t)m * slot[s] : nullptr;
+            gf[s] = mapped && ghost_live[s] && pn.side_inf_set[s] ? pn.d_side_inf[s] + (size_t)m * slot[s] : nullptr;
+          }
+          sd.gc = PlaneGhost{{gc[0], gc[1]}, gc[2]};
+          sd.gf = PlaneGhost{{gf[0], gf[1]}, gf[2]};
+          for (int s = 0; s < 2; s++) {
+            sd.xc[s] = pn.side_out_on && live[s] ? pn.d_side_out[s] + (size_t)m * slot[s] : nullptr;
+            sd.xf[s] = pn.side_out_on && live[s] && mapped ? pn.d_side_outf[s] + (size_t)m * slot[s] : nullptr;
+          }
+          sd.edge_f = pside_edge(T.e_f, G.fa);
+          sd.edge_g = pside_edge(T.e_g, G.fb);
+        }
         with_flag(mapped, [&](auto flux) {
+          if (sides) {
+            hipLaunchKernelGGL(k_pside_layer<decltype(flux)::value>, lgrid, dim3(PLANE_LAYER_BX, PLANE_LAYER_BY), 0, c->stream, G, T, P.sc, m,
+                               g.ncell, c->d_ndens, c->d_xh_av, c->d_xhe_av, lls, prev, c->d_plane_cin, next, fprev,
+                               mapped ? c->d_pflux_cell : nullptr, fnext, sd);
+            return;
+          }
           hipLaunchKernelGGL(k_plane_layer<decltype(flux)::value>, lgrid, dim3(PLANE_LAYER_BX, PLANE_LAYER_BY), 0, c->stream, G, T, P.sc, m,
                              g.ncell, c->d_ndens, c->d_xh_av, c->d_xhe_av, lls, prev, c->d_plane_cin, next, fprev,
                              mapped ? c->d_pflux_cell : nullptr, fnext);
@@ -408,6 +548,8 @@ static int run_planes(PassCtx &P, const std::vector<int> &planes) {
         prev = next;
         fprev = fnext;
       }
+      pn.side_out_live[0] = pn.side_out_on && live[0];
+      pn.side_out_live[1] = pn.side_out_on && live[1];
       c->tm.sweep_launches += G.na;
       if (mapped) exit_flux = pn.d_fexit;
     } else {
@@ -468,6 +610,30 @@ static int run_planes(PassCtx &P, const std::vector<int> &planes) {
                          pn.d_exit, c->d_plane_partial, map);
     }); }); });
     hipLaunchKernelGGL(k_loss_finish, dim3(1), dim3(BLOCK), 0, c->stream, c->d_plane_partial, fblk, fblk, c->d_plane_loss + p);
+    // the side loss (c2r_enable_plane_side_loss): one sum per live side, side 0 first; with escape maps every term kept at the
+    // side face the beam leaves through
+    pn.side_ran[0] = pn.side_ran[1] = false;
+    if (c->side_loss_on && tilted) {
+      const int side_axis[2] = {face_axis_a(pl.axis), face_axis_b(pl.axis)};
+      const int e[2] = {T.e_f, T.e_g}, wrap[2] = {T.wrap_f, T.wrap_g};
+      const FaceLayout L = face_layout(c);
+      for (int s = 0; s < 2; s++) {
+        if (!pside_live(pn.tilt[s], wrap[s])) continue;
+        const int cells = face_cells(L.n, side_axis[s]), sblk = (cells + BLOCK - 1) / BLOCK;
+        double *smap = c->d_face_maps ? c->d_face_maps + face_map_offset(L.n, L.open, pside_face(side_axis[s], e[s])) : nullptr;
+        with_flag(multi, [&](auto three) { with_flag(mapped, [&](auto from_map) { with_flag(curved, [&](auto with_curve) {
+          with_flag(smap != nullptr, [&](auto keep) {
+            const auto kernel = k_pside_loss<decltype(three)::value, decltype(from_map)::value, decltype(with_curve)::value, decltype(keep)::value>;
+            hipLaunchKernelGGL(kernel, dim3(sblk), dim3(BLOCK), 0, c->stream, g, G, T, P.sc, s, pd, mapped ? c->d_pflux_cell : nullptr, cv,
+                               c->d_ndens, c->d_xh_av, c->d_xhe_av, c->d_bands, ss, c->d_plane_cin, c->d_side_partial, smap);
+          });
+        }); }); });
+        hipLaunchKernelGGL(k_loss_finish, dim3(1), dim3(BLOCK), 0, c->stream, c->d_side_partial, sblk, sblk, c->d_side_loss + 2 * p + s);
+        HIPCHK(c, hipMemcpyAsync(c->h_side_loss + 2 * p + s, c->d_side_loss + 2 * p + s, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        pn.side_ran[s] = true;
+        c->tm.rates_launches += 2;
+      }
+    }
     HIPCHK(c, hipGetLastError());
     c->tm.rates_launches += 3;
     if (c->timing) {
@@ -487,7 +653,8 @@ static int run_planes(PassCtx &P, const std::vector<int> &planes) {
 // them), and every plane's record back to what a new context has
 static void free_plane_buffers(c2r_ctx *c) {
   for (c2r_ctx::Plane &pn : c->plane) {
-    for (double *b : {pn.d_entry, pn.d_exit, pn.d_fmap, pn.d_fexit})
+    for (double *b : {pn.d_entry, pn.d_exit, pn.d_fmap, pn.d_fexit, pn.d_side_in[0], pn.d_side_in[1], pn.d_side_in[2], pn.d_side_inf[0],
+                      pn.d_side_inf[1], pn.d_side_inf[2], pn.d_side_out[0], pn.d_side_out[1], pn.d_side_outf[0], pn.d_side_outf[1]})
       if (b) (void)hipFree(b);
     pn = c2r_ctx::Plane{};
   }
@@ -770,5 +937,169 @@ extern "C" int c2r_get_plane_loss(c2r_ctx *c, int plane, double *loss) {
   if (plane < 1 || plane > c->nplane || !loss) return fail(c, "c2r_get_plane_loss: plane %d not in [1,%d], or null argument", plane, c->nplane);
   if (c->pass_open) return fail(c, "c2r_get_plane_loss: a pass opened by c2r_pass_sources_begin is still open");
   *loss = plane_owner(c, plane - 1)->plane[plane - 1].loss;
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------------
+// side faces of a tilted plane: side entry, side exit, side loss (include/c2ray_hip.h; the rule is c2ray_pside.hpp)
+
+// cells along a line of `side` of a plane along `axis` (L_0 = fb, L_1 = fa, 1 for the corner line) and layers of the plane
+static void plane_strip_shape(const c2r_ctx *c, int axis, int side, size_t &line, size_t &na) {
+  const PlaneGeom G = plane_geometry(c->g.n1, c->g.n2, c->g.n3, axis, 0);
+  line = side == 0 ? (size_t)G.fb : (side == 1 ? (size_t)G.fa : 1);
+  na = (size_t)G.na;
+}
+
+// c2r_set_plane_side_entry on one device: everything is checked before anything changes
+static int set_plane_side_entry_one(c2r_ctx *c, int plane, int side, const double *cols, const double *flux) {
+  if (!c) return 1;
+  if (plane < 1 || plane > c->nplane) return fail(c, "c2r_set_plane_side_entry: plane %d not in [1,%d]", plane, c->nplane);
+  if (side < 0 || side > 2) return fail(c, "c2r_set_plane_side_entry: side %d, expected 0, 1 or 2 (the corner line)", side);
+  if (c->pass_open) return fail(c, "c2r_set_plane_side_entry: a pass opened by c2r_pass_sources_begin is still open");
+  if (!cols && flux) return fail(c, "c2r_set_plane_side_entry: plane %d, side %d: a flux strip without a column strip", plane, side);
+  c2r_ctx::Plane &pn = c->plane[plane - 1];
+  size_t line, na;
+  plane_strip_shape(c, pn.src.axis, side, line, na);
+  const size_t n = na * 3 * line;
+  bool uses[2] = {false, false};
+  if (flux)
+    for (size_t i = 0; i < n; i++) {
+      const int sed = (int)((i / line) % 3);
+      if (!(flux[i] >= 0.0) || !std::isfinite(flux[i]))
+        return fail(c, "c2r_set_plane_side_entry: plane %d, side %d: flux entry %zu of SED %d in slot %zu is %g (a flux is finite and not "
+                    "negative)", plane, side, i % line, sed, i / (3 * line), flux[i]);
+      if (sed > 0 && flux[i] != 0.0) uses[sed - 1] = true;
+    }
+  for (int k = 0; k < 2; k++)
+    if (uses[k] && !c->have_sed[k])
+      return fail(c, "c2r_set_plane_side_entry: plane %d, side %d: the strip has a flux of SED %d, whose tables have not been set "
+                  "(c2r_set_sed_tables(%d))", plane, side, k + 1, k + 1);
+  if (!cols) { // the side reads 0.0 again
+    pn.side_in_set[side] = pn.side_inf_set[side] = pn.side_inf_uses[side][0] = pn.side_inf_uses[side][1] = false;
+    return 0;
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  if (!pn.d_side_in[side]) HIPCHK(c, hipMalloc(&pn.d_side_in[side], sizeof(double) * n));
+  if (flux && !pn.d_side_inf[side]) HIPCHK(c, hipMalloc(&pn.d_side_inf[side], sizeof(double) * n));
+  pn.side_in_set[side] = pn.side_inf_set[side] = pn.side_inf_uses[side][0] = pn.side_inf_uses[side][1] = false;
+  HIPCHK(c, hipMemcpyAsync(pn.d_side_in[side], cols, sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
+  if (flux) HIPCHK(c, hipMemcpyAsync(pn.d_side_inf[side], flux, sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  pn.side_in_set[side] = true;
+  pn.side_inf_set[side] = flux != nullptr;
+  pn.side_inf_uses[side][0] = uses[0];
+  pn.side_inf_uses[side][1] = uses[1];
+  return 0;
+}
+
+extern "C" int c2r_set_plane_side_entry(c2r_ctx *c, int plane, int side, const double *cols, const double *flux) {
+  if (int e_ = set_plane_side_entry_one(c, plane, side, cols, flux)) return e_;
+  return for_replicas(c, [&](c2r_ctx *r) { return set_plane_side_entry_one(r, plane, side, cols, flux); });
+}
+
+static int enable_plane_side_exit_one(c2r_ctx *c, int plane, int on) {
+  if (!c) return 1;
+  if (plane < 1 || plane > c->nplane) return fail(c, "c2r_enable_plane_side_exit: plane %d not in [1,%d]", plane, c->nplane);
+  if (c->pass_open) return fail(c, "c2r_enable_plane_side_exit: a pass opened by c2r_pass_sources_begin is still open");
+  c2r_ctx::Plane &pn = c->plane[plane - 1];
+  HIPCHK(c, hipSetDevice(c->device));
+  if (!on) {
+    HIPCHK(c, hipStreamSynchronize(c->stream)); // nothing queued may still write them
+    for (int s = 0; s < 2; s++) {
+      if (pn.d_side_out[s]) (void)hipFree(pn.d_side_out[s]);
+      if (pn.d_side_outf[s]) (void)hipFree(pn.d_side_outf[s]);
+      pn.d_side_out[s] = pn.d_side_outf[s] = nullptr;
+      pn.side_out_live[s] = false;
+    }
+    pn.side_out_on = pn.side_out_valid = pn.side_out_mapped = false;
+    return 0;
+  }
+  if (pn.side_out_on) return 0;
+  for (int s = 0; s < 2; s++) {
+    size_t line, na;
+    plane_strip_shape(c, pn.src.axis, s, line, na);
+    if (!pn.d_side_out[s]) HIPCHK(c, hipMalloc(&pn.d_side_out[s], sizeof(double) * na * 3 * line));
+    if (!pn.d_side_outf[s]) HIPCHK(c, hipMalloc(&pn.d_side_outf[s], sizeof(double) * na * 3 * line));
+  }
+  pn.side_out_on = true;
+  pn.side_out_valid = false;
+  return 0;
+}
+
+extern "C" int c2r_enable_plane_side_exit(c2r_ctx *c, int plane, int on) {
+  if (int e_ = enable_plane_side_exit_one(c, plane, on)) return e_;
+  return for_replicas(c, [&](c2r_ctx *r) { return enable_plane_side_exit_one(r, plane, on); });
+}
+
+extern "C" int c2r_download_plane_side_exit(c2r_ctx *c, int plane, int side, double *cols, double *flux) {
+  if (!c) return 1;
+  if (plane < 1 || plane > c->nplane || !cols)
+    return fail(c, "c2r_download_plane_side_exit: plane %d not in [1,%d], or null argument", plane, c->nplane);
+  if (side < 0 || side > 1) return fail(c, "c2r_download_plane_side_exit: side %d, expected 0 or 1", side);
+  if (c->pass_open) return fail(c, "c2r_download_plane_side_exit: a pass opened by c2r_pass_sources_begin is still open");
+  c2r_ctx *d = plane_owner(c, plane - 1);
+  const c2r_ctx::Plane &pn = d->plane[plane - 1];
+  if (!pn.side_out_on || !pn.side_out_valid)
+    return fail(c, "c2r_download_plane_side_exit: no pass has run plane %d with the side exit enabled yet (c2r_enable_plane_side_exit, then "
+                "a pass)", plane);
+  if (!pn.side_out_live[side])
+    return fail(c, "c2r_download_plane_side_exit: side %d of plane %d was not live in the last pass that ran it (its tilt component is "
+                "zero or its axis periodic)", side, plane);
+  if (flux && !pn.side_out_mapped)
+    return fail(c, "c2r_download_plane_side_exit: plane %d ran without a flux map: it has no flux strips (pass flux = NULL)", plane);
+  size_t line, na;
+  plane_strip_shape(d, pn.src.axis, side, line, na);
+  HIPCHK(c, hipSetDevice(d->device));
+  HIPCHK(c, hipMemcpyAsync(cols, pn.d_side_out[side], sizeof(double) * na * 3 * line, hipMemcpyDeviceToHost, d->stream));
+  if (flux) HIPCHK(c, hipMemcpyAsync(flux, pn.d_side_outf[side], sizeof(double) * na * 3 * line, hipMemcpyDeviceToHost, d->stream));
+  HIPCHK(c, hipStreamSynchronize(d->stream));
+  return 0;
+}
+
+// the buffers of the side loss of one device (c2r_enable_plane_side_loss, c2r_destroy)
+static void free_side_loss(c2r_ctx *c) {
+  if (c->d_side_partial) (void)hipFree(c->d_side_partial);
+  if (c->d_side_loss) (void)hipFree(c->d_side_loss);
+  if (c->h_side_loss) (void)hipHostFree(c->h_side_loss);
+  c->d_side_partial = c->d_side_loss = c->h_side_loss = nullptr;
+}
+
+static int enable_plane_side_loss_one(c2r_ctx *c, int on) {
+  if (!c) return 1;
+  if (c->pass_open) return fail(c, "c2r_enable_plane_side_loss: a pass opened by c2r_pass_sources_begin is still open (close it with c2r_pass_sources_end first)");
+  HIPCHK(c, hipSetDevice(c->device));
+  if (!on) {
+    if (c->side_loss_on) HIPCHK(c, hipStreamSynchronize(c->stream));
+    free_side_loss(c);
+    c->side_loss_on = false;
+    return 0;
+  }
+  if (c->side_loss_on) return 0;
+  const int n[3] = {c->g.n1, c->g.n2, c->g.n3};
+  int most = 0;
+  for (int d = 0; d < 3; d++) most = std::max(most, face_cells(n, d));
+  HIPCHK(c, hipMalloc(&c->d_side_partial, sizeof(double) * (size_t)((most + BLOCK - 1) / BLOCK)));
+  HIPCHK(c, hipMalloc(&c->d_side_loss, sizeof(double) * 2 * PLANE_MAX));
+  HIPCHK(c, hipHostMalloc(&c->h_side_loss, sizeof(double) * 2 * PLANE_MAX));
+  for (c2r_ctx::Plane &pn : c->plane) pn.side_loss[0] = pn.side_loss[1] = 0.0;
+  c->side_loss_on = true;
+  return 0;
+}
+
+extern "C" int c2r_enable_plane_side_loss(c2r_ctx *c, int on) {
+  if (int e_ = enable_plane_side_loss_one(c, on)) return e_;
+  return for_replicas(c, [&](c2r_ctx *r) { return enable_plane_side_loss_one(r, on); });
+}
+
+extern "C" int c2r_get_plane_side_loss_enabled(const c2r_ctx *c) { return c && c->side_loss_on ? 1 : 0; }
+
+extern "C" int c2r_get_plane_side_loss(c2r_ctx *c, int plane, double out2[2]) {
+  if (!c) return 1;
+  if (!c->side_loss_on) return fail(c, "c2r_get_plane_side_loss: the side loss is off (c2r_enable_plane_side_loss)");
+  if (plane < 1 || plane > c->nplane || !out2) return fail(c, "c2r_get_plane_side_loss: plane %d not in [1,%d], or null argument", plane, c->nplane);
+  if (c->pass_open) return fail(c, "c2r_get_plane_side_loss: a pass opened by c2r_pass_sources_begin is still open");
+  const c2r_ctx::Plane &pn = plane_owner(c, plane - 1)->plane[plane - 1];
+  out2[0] = pn.side_loss[0];
+  out2[1] = pn.side_loss[1];
   return 0;
 }

@@ -667,6 +667,59 @@ class HipEngine:
         self._chk(self.lib.c2r_get_plane_tilt(self.h, int(p), out))
         return (out[0], out[1])
 
+    # -- side faces of a tilted plane (c2r_set_plane_side_entry ..; include/c2ray_hip.h has the rule) ----------
+    def plane_strip_shape(self, p, side):
+        """(na, 3, L) of a strip of plane p (1-based): na slots of 3 x L values; L = the extent of the other face axis for side
+        0 and 1, 1 for the corner line (side 2).  None for a plane or side the library will refuse."""
+        axes = getattr(self, "_plane_axes", [])
+        if not 1 <= int(p) <= len(axes) or int(side) not in (0, 1, 2):
+            return None
+        axis = axes[int(p) - 1]
+        f, g = [d for d in range(3) if d != axis]
+        return (self.mesh[axis], 3, (self.mesh[g], self.mesh[f], 1)[int(side)])
+
+    def set_plane_side_entry(self, p, side, cols=None, flux=None):
+        """Side entry of plane p (1-based): the ghost cells a neighbouring mesh hands in through side 0 (face axis f), side 1
+        (face axis g) or the corner line (side 2).  cols, flux: (na, 3, L) -- slot m holds the layer before layer m, species
+        or SED next, the index along the other face axis fastest -- e.g. the neighbour's plane_side_exit.  cols None: the side
+        reads 0.0 again; flux None: a ghost flux of 0.  set_plane_sources drops every strip."""
+        shape = self.plane_strip_shape(p, side)
+        arrs = []
+        for name, a in (("cols", cols), ("flux", flux)):
+            if a is not None:
+                a = _f64(a).reshape(-1)
+                if shape is not None and a.size != int(np.prod(shape)):
+                    raise ValueError(f"set_plane_side_entry: {name} has {a.size} values, expected {shape}")
+            arrs.append(a)
+        self._chk(self.lib.c2r_set_plane_side_entry(self.h, int(p), int(side), _dp(arrs[0]), _dp(arrs[1])))
+
+    def enable_plane_side_exit(self, p, on=True):
+        """Keep what the downstream edge cells of plane p's live sides hand on, layer by layer (plane_side_exit)."""
+        self._chk(self.lib.c2r_enable_plane_side_exit(self.h, int(p), int(on)))
+
+    def plane_side_exit(self, p, side, flux=True):
+        """(cols, flux) of side 0 or 1 of plane p from the last pass that ran it, each (na, 3, L) in the layout of
+        set_plane_side_entry; flux=False (a plane without a map): (cols, None)."""
+        shape = self.plane_strip_shape(p, side) or (0, 3, 0)
+        cols = np.empty(shape)
+        fl = np.empty(shape) if flux else None
+        self._chk(self.lib.c2r_download_plane_side_exit(self.h, int(p), int(side), _dp(cols), _dp(fl)))
+        return cols, fl
+
+    def enable_plane_side_loss(self, on=True):
+        """Count what tilted planes lose through open side faces: in photon_loss(1), plane_side_loss and the escape maps."""
+        self._chk(self.lib.c2r_enable_plane_side_loss(self.h, int(on)))
+
+    @property
+    def plane_side_loss_enabled(self):
+        return bool(self.lib.c2r_get_plane_side_loss_enabled(self.h))
+
+    def plane_side_loss(self, p):
+        """(side 0, side 1): what plane p added to photon_loss(1) through its side faces in the last pass that ran it."""
+        out = (C.c_double * 2)()
+        self._chk(self.lib.c2r_get_plane_side_loss(self.h, int(p), out))
+        return (out[0], out[1])
+
     # -- escape maps (c2r_enable_face_loss; include/c2ray_hip.h has the rule) ---------------------------------
     def enable_face_loss(self, on=True):
         """Keep the kept photon loss of open boxes per cell of the open mesh face it leaves through (off by default)."""

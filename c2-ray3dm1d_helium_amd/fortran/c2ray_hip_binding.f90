@@ -706,6 +706,48 @@ module c2ray_hip
        type(c_ptr), value :: curve
      end function c2r_set_plane_curve
 
+     !> side faces of a tilted plane (include/c2ray_hip.h): side entry -- the ghost strips a neighbouring mesh hands in;
+     !> side = 0, 1, or 2 for the corner line; cols / flux: c_loc of na x 3 x L doubles, or c_null_ptr
+     integer(c_int) function c2r_set_plane_side_entry(ctx, plane, side, cols, flux) bind(C, name="c2r_set_plane_side_entry")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: ctx
+       integer(c_int), value :: plane, side
+       type(c_ptr), value :: cols, flux
+     end function c2r_set_plane_side_entry
+
+     integer(c_int) function c2r_enable_plane_side_exit(ctx, plane, on) bind(C, name="c2r_enable_plane_side_exit")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: ctx
+       integer(c_int), value :: plane, on
+     end function c2r_enable_plane_side_exit
+
+     !> cols / flux: c_loc of na x 3 x L doubles; flux = c_null_ptr for a plane without a map
+     integer(c_int) function c2r_download_plane_side_exit(ctx, plane, side, cols, flux) bind(C, name="c2r_download_plane_side_exit")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: ctx
+       integer(c_int), value :: plane, side
+       type(c_ptr), value :: cols, flux
+     end function c2r_download_plane_side_exit
+
+     !> side loss: what a tilted plane loses through its open side faces; off by default
+     integer(c_int) function c2r_enable_plane_side_loss(ctx, on) bind(C, name="c2r_enable_plane_side_loss")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: ctx
+       integer(c_int), value :: on
+     end function c2r_enable_plane_side_loss
+
+     integer(c_int) function c2r_get_plane_side_loss_enabled(ctx) bind(C, name="c2r_get_plane_side_loss_enabled")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: ctx
+     end function c2r_get_plane_side_loss_enabled
+
+     integer(c_int) function c2r_get_plane_side_loss(ctx, plane, out2) bind(C, name="c2r_get_plane_side_loss")
+       import :: c_int, c_ptr, c_double
+       type(c_ptr), value :: ctx
+       integer(c_int), value :: plane
+       real(c_double), intent(out) :: out2(2)
+     end function c2r_get_plane_side_loss
+
      !> the curve of plane `plane` (1-based) as it was set; nstep = 0 and factor(1) = 1 while it has none
      integer(c_int) function c2r_get_plane_curve(ctx, plane, curve) bind(C, name="c2r_get_plane_curve")
        import :: c_int, c_ptr, c2r_plane_curve

@@ -567,7 +567,8 @@ int c2r_get_plane_loss(c2r_ctx *ctx, int plane, double *loss);
  *   1. the four upstream cells c1..c4 are (u - e_f, v - e_g), (u, v - e_g), (u - e_f, v), (u, v): for m > 0 cells of
  *      layer m - 1 with that layer's outgoing columns, for m = 0 cells of the plane's entry columns (zero when not set);
  *   2. an index outside 1..mesh along a face axis wraps where that axis is periodic; where it is open that corner's three
- *      columns are 0 (the ray came in through the side of the mesh, and outside is empty);
+ *      columns are 0 (the ray came in through the side of the mesh, and outside is empty) unless a side-entry strip of that
+ *      side has been set (c2r_set_plane_side_entry below);
  *   3. per species, sig = sigma_HI / HeI / HeII at the species' threshold as weightf takes them for point sources:
  *        w_i = s_i * (1.0 / max(0.6, c_i*sig)),   N_in = (c1*w1 + c2*w2 + c3*w3 + c4*w4) / (w1 + w2 + w3 + w4),
  *      the sums from the left; no factor sqrt2 / sqrt3 (that belongs to cells adjacent to a source);
@@ -578,8 +579,9 @@ int c2r_get_plane_loss(c2r_ctx *ctx, int plane, double *loss);
  *      perpendicular to the beam;
  *   5. the exit columns are the outgoing columns of the last layer; the loss term of a line is photo_out*vol/path of its
  *      last cell, added to photon_loss(1), to c2r_get_plane_loss and to the escape map of the far face at the line's face
- *      cell exactly as for the normal plane.  What crosses an open SIDE face, in or out, is in no loss and no map; the
- *      loss identity of the escape maps therefore holds for a tilted plane only when the tilted face axes are periodic.
+ *      cell exactly as for the normal plane.  What crosses an open SIDE face, in or out, is in no loss and no map unless
+ *      c2r_enable_plane_side_loss (below) is on; without it the loss identity of the escape maps holds for a tilted plane
+ *      only when the tilted face axes are periodic.
  * Two slabs stacked along the axis with the same tilt, the upstream slab's exit columns given to the downstream slab as
  * entry columns, reproduce one mesh of the combined depth bit for bit.
  * Refused, each with an error text: a non-finite tilt; a_f > 1 or a_g > 1 with the current dr (the axis would no longer be
@@ -606,7 +608,7 @@ int c2r_get_plane_tilt(const c2r_ctx *ctx, int plane, double tilt[2]);
  *        F[k] = F1[k]*s_1 + F2[k]*s_2 + F3[k]*s_3 + F4[k]*s_4,
  *     every product rounded, the sums from the left; Fi is the flux of that corner in the layer before, for m = 0 the map
  *     itself.  A corner outside an OPEN side face carries flux 0 (a map describes a finite beam: no flux enters through
- *     the side of the mesh); a periodic face axis wraps, and the face total is then conserved up to rounding (exactly,
+ *     the side of the mesh) unless a side-entry flux strip of that side has been set; a periodic face axis wraps, and the face total is then conserved up to rounding (exactly,
  *     where the products are exact).  The cell (u, v) of layer m uses nf = F.
  *   Dark cells.  A cell whose three fluxes are all == 0.0 adds nothing to any rate grid, and its line's loss term is 0.0:
  *     it is skipped, no per-cell function is evaluated.  Everything else about a cell -- fog, columns, max_coldensh guard,
@@ -694,6 +696,72 @@ typedef struct {
 } c2r_plane_curve;
 int c2r_set_plane_curve(c2r_ctx *ctx, int plane, const c2r_plane_curve *curve);
 int c2r_get_plane_curve(const c2r_ctx *ctx, int plane, c2r_plane_curve *out);
+
+/* Side faces of a tilted plane: hand-over to the mesh that stands beside this one, and the loss through open side faces.
+ * Notation: the plane travels along axis a; the face axes are f < g with extents fa, fb; na = mesh[a] layers m = 0 .. na-1 in
+ * travel order; s_1..s_4, e_f, e_g and path are those of the tilted march above.  SIDE 0 is face axis f, SIDE 1 face axis g;
+ * L_0 = fb and L_1 = fa are the lengths of a side's lines.  A side is LIVE in a pass iff its tilt component is non-zero and
+ * its axis is open in that pass.  The upstream ghost index of a live side is -1 for e = +1 and n for e = -1 (where step 2
+ * of the march finds a corner outside); its DOWNSTREAM EDGE is the cell index n-1 for e = +1 and 0 for e = -1.
+ * All three parts are per plane; c2r_set_plane_sources drops them, c2r_set_plane_tilt, c2r_set_plane_flux_map,
+ * c2r_set_plane_curve, c2r_set_plane_entry_columns, c2r_set_boundaries* and c2r_set_sources keep them; they are refused
+ * between c2r_pass_sources_begin and c2r_pass_sources_end, act on every device of a multi-device context, and every route that
+ * runs a plane honours them.  A plane that uses none of them runs the kernels it ran before, with the same bits.
+ *
+ * 1. Side entry: what a neighbouring mesh hands in.  side = 0, 1, or 2 for the corner line.  A strip has na SLOTS; slot m
+ *    holds the ghost cells of the layer BEFORE layer m: for m = 0 the entry layer in front of the mesh (where the entry
+ *    columns and the map live), for m >= 1 layer m-1.  Sides 0 and 1: cols[(m*3 + k)*L_s + t], k the species (HI, HeI, HeII),
+ *    t the 0-based index along the OTHER face axis; flux has the same layout with k the SED.  The corner line (side 2):
+ *    cols[m*3 + k] and flux[m*3 + k].  cols = NULL clears that side (flux must then be NULL too); flux = NULL with cols given
+ *    is a ghost flux of 0.
+ *    Steps 1-2 of the tilted march change in one place only: where a corner index falls outside an OPEN face axis on a LIVE
+ *    side (an index that wraps still wraps).  Outside along f only: side 0's strip, slot m, at the corner's own index along g
+ *    (after any wrap); outside along g only: side 1's strip, slot m, at the corner's own index along f; outside along both:
+ *    the corner line, slot m; a strip that is not set: 0.0, as before.  The ghost values go through the weighted mean of step
+ *    3 and the flux rule of c2r_set_plane_flux_map as in-mesh corners do.  The flux strips are read only while the plane has a
+ *    map (a uniform plane's flux is normflux everywhere, ghost or not).  A strip of a side that is not live in a pass is kept
+ *    and not read.  The plane takes the three-SED routine iff some entry of SED 1 or 2 of the map, or of a set side-entry flux
+ *    strip, is non-zero.
+ *    Refused, each with an error text and leaving everything unchanged: a bad plane or side; flux without cols; a negative or
+ *    non-finite flux entry; a non-zero flux of SED 1 or 2 without that SED's tables.  Columns are taken as given.
+ * 2. Side exit: what this mesh hands on.  c2r_enable_plane_side_exit allocates (on != 0) or frees the strips of a plane;
+ *    c2r_download_plane_side_exit (side 0 or 1) fills the layout above from the last pass that ran the plane, for the
+ *    downstream edge cells of a live side: slot m at t is the value of the layer before layer m at the edge cell whose other
+ *    index is t -- slot 0 the plane's entry columns there (0 when none) and the map there, slot m >= 1 the outgoing columns
+ *    of layer m-1 and the flux that cell saw (unscaled by any curve, as the exit flux is).  Each value is the corner c4 / F4
+ *    the edge cell of layer m loads.  The last layer's edge is in no strip: it is in the exit columns and the exit flux, which
+ *    a slab stacked downstream takes its slot 0 from.  flux must be NULL for a plane without a map.  The downstream corner
+ *    cell is in both strips: a diagonal neighbour's corner line is read out of either.
+ *    Refused: before any pass ran the plane with the strips enabled; a side that was not live in that pass; a non-NULL flux
+ *    without a map.
+ *    Hand-over identity.  Let mesh B be the downstream neighbour of mesh A along a face axis, with the same tilt, cell sizes
+ *    and plane record (a curve shared with its layer0 and depth0).  With A's side exit given to B as side entry, and B's
+ *    corner line taken from the diagonal neighbour's strip, B reproduces its part of one mesh of the combined width (open
+ *    along that axis) bit for bit -- incoming columns, rate grids, exit columns, exit flux, per-line far-face terms -- and A
+ *    reproduces its own part unaided, since the beam never comes back.
+ * 3. Side loss: closing the photon budget.  Off by default; while off nothing is allocated, launched or added.  The rule
+ *    (csrc/c2ray_pside.hpp) covers a tilted plane in a pass, every layer m = 0 .. na-2 and every cell (u, v) of it (the last
+ *    layer gives its whole term to the far face).  The cell hands its outgoing beam to three displaced targets in layer m+1:
+ *    (u+e_f, v+e_g) with weight s_1, (u, v+e_g) with s_2, (u+e_f, v) with s_3.  A target's index wraps on a periodic face
+ *    axis; a target that then lies outside the mesh gives its weight to one side: outside along f only, side 0; outside along
+ *    g only, side 1; outside along both, side 0 (the lowest axis, the escape maps' tie rule).  So w_0 = s_3 + s_1, and
+ *    w_1 = s_2 + s_1, or s_2 alone on the line where side 0 takes the diagonal -- host doubles, one rounded sum each; only
+ *    cells on a live side's downstream edge have a non-zero weight.  The term of a cell for side s is base * w_s, one rounded
+ *    product, where base is photo_out*vol/path of that cell from its own incoming and outgoing columns and the flux it used
+ *    (uniform, or the carried flux of a mapped plane, times the curve factor of layer m where the plane has a curve); base is
+ *    0.0 for a dark cell, an unlit cell and where N_in(HI) >= max_coldensh.  A side's terms are added in the fixed order of
+ *    the other loss sums (blocks of 256 by a tree, the block sums in order), the cells in the order of the side face's map.
+ *    While enabled the sums go into photon_loss(1) (behind the plane's far loss: side 0, then side 1), into
+ *    c2r_get_plane_side_loss (out2[0], out2[1]: the last pass that ran the plane) and, with c2r_enable_face_loss on, into the
+ *    escape map of the side face the beam leaves through, 2*axis + (e > 0), at the edge cell's face cell, map = map + term, the
+ *    planes in plane order.  c2r_get_plane_loss stays the far face's alone.  A plane at normal incidence, or with no live
+ *    side, loses nothing through sides. */
+int c2r_set_plane_side_entry(c2r_ctx *ctx, int plane, int side, const double *cols, const double *flux);
+int c2r_enable_plane_side_exit(c2r_ctx *ctx, int plane, int on);
+int c2r_download_plane_side_exit(c2r_ctx *ctx, int plane, int side, double *cols, double *flux);
+int c2r_enable_plane_side_loss(c2r_ctx *ctx, int on);
+int c2r_get_plane_side_loss_enabled(const c2r_ctx *ctx);                /* 1 / 0 */
+int c2r_get_plane_side_loss(c2r_ctx *ctx, int plane, double out2[2]);
 
 /* Escape maps: WHERE the photons that photon_loss(1) counts left an open box -- the kept loss per cell of the open mesh
  * face it leaves through.  Off by default; with it off nothing is allocated, launched or waited for.
