@@ -3,7 +3,9 @@
 //
 //   column sweep   k_sweep_shell   one launch per L-infinity shell around the sources of a batch:
 //                                  short-characteristics interpolation of the three incoming
-//                                  columns (cinterp) + the cell's own columns (evolve0D, first half)
+//                                  columns (cinterp) + the cell's own columns (evolve0D, first half);
+//                                  k_sweep_shell_ext, k_sweep_shell_fast_ext for a batch with a source outside the mesh
+//                                  (c2r_set_sources_external): cells of its box beyond the mesh are vacuum
 //   rates          k_rates         all cells x all sources of the batch, no dependencies:
 //                                  photoion_rates + accumulation into the rate grids in source order
 //                                  (evolve0D, second half)
@@ -68,7 +70,8 @@ struct Grid {
 
 // One source of the batch in flight, in device memory (read through the scalar cache: uniform per block).
 struct SrcDev {
-  int i0, j0, k0;      // 1-based mesh position (srcpos)
+  int i0, j0, k0;      // 1-based mesh position (srcpos); < 1 or > mesh along an open axis for a source that stands outside the
+                       // mesh (c2r_set_sources_external): an ordinary operand of short_characteristic, vol_ph and the path
   int lo[3], hi[3];    // FINAL sub-box as offsets last_l - srcpos, last_r - srcpos (set before the rates launch)
   double nflux;        // NormFlux(ns)
   double nflux_sed[2]; // NormFluxPL(ns), NormFluxQPL(ns) (-DPL / -DQUASARS builds), else 0
@@ -500,8 +503,13 @@ __device__ __forceinline__ void sweep_cell_state(const SweepArgs &A, int i, int 
 // OPEN: the round's box cut at the source's reach, no modulo: a shell cell outside the reach does not exist, and the
 // upstream cells of a cell in the mesh lie in the mesh (corners of weight exactly 0 may be read from a slot that was
 // never written: finite, as everything in the arena).
-template <bool OPEN>
+// EXT (open and mixed boundaries, a batch with a source outside the mesh, c2r_set_sources_external): the box of such a
+// source is cut at a reach that runs through vacuum up to the source, so a cell of it may lie outside the mesh along an open
+// axis -- a VACUUM cell: neufrac * ndens is exactly 0.0 for the three species and there is no LLS fog, N_out = N_in +
+// 0 * path * abundance, and nothing is loaded from the state grids.  A mesh cell gets the arithmetic it always got.
+template <bool OPEN, bool EXT = false>
 __device__ __forceinline__ void sweep_cell(const SweepArgs &A, const SrcDev &S, int shell, int t) {
+  static_assert(OPEN || !EXT, "a source outside the mesh needs an open axis");
   const Grid &g = A.g;
   const StepScalars &sc = A.sc;
   int di, dj, dk;
@@ -524,8 +532,10 @@ __device__ __forceinline__ void sweep_cell(const SweepArgs &A, const SrcDev &S, 
   const int i = mesh0<OPEN>(S.i0 - 1 + di, g.n1, S.wn[0]), j = mesh0<OPEN>(S.j0 - 1 + dj, g.n2, S.wn[1]),
             k = mesh0<OPEN>(S.k0 - 1 + dk, g.n3, S.wn[2]);
   const int w_ = 2 * shell + 1;
-  double u_HI, u_HeI, u_HeII;
-  sweep_cell_state(A, i, j, k, shell > 0 && t >= (OPEN ? RS.b4 : 2 * w_ * w_ + 2 * (w_ - 2) * w_), u_HI, u_HeI, u_HeII);
+  // (EXT: one unsigned compare per axis, after the wrap -- a periodic axis of a mixed run always passes)
+  const bool in_mesh = !EXT || (axis_in_mesh(i, g.n1) && axis_in_mesh(j, g.n2) && axis_in_mesh(k, g.n3));
+  double u_HI = 0.0, u_HeI = 0.0, u_HeII = 0.0;
+  if (in_mesh) sweep_cell_state(A, i, j, k, shell > 0 && t >= (OPEN ? RS.b4 : 2 * w_ * w_ + 2 * (w_ - 2) * w_), u_HI, u_HeI, u_HeII);
   double cin_HI, cin_HeI, cin_HeII, path;
   if (shell == 0) {
     cin_HI = cin_HeI = cin_HeII = 0.0;
@@ -550,7 +560,7 @@ __device__ __forceinline__ void sweep_cell(const SweepArgs &A, const SrcDev &S, 
     cin_HeII = interp_column(s4, cs[col_out(qc[0], 2, cz)], cs[col_out(qc[1], 2, cz)], cs[col_out(qc[2], 2, cz)],
                              cs[col_out(qc[3], 2, cz)], sigma_HeII_at_ion_freq);
     path = s4.path * sc.dr1;
-    if (sc.use_lls) {
+    if (sc.use_lls && in_mesh) {
       // Lyman-limit-system fog on the incoming HI column (evolve_point.F90:177-180); the per-cell
       // grid is LLS_point of type_of_LLS = 2 (REAL(4), mat_ini_cubep3m.F90:859-870)
       const double coldensh_LLS =
@@ -572,8 +582,10 @@ __device__ __forceinline__ void sweep_cell(const SweepArgs &A, const SrcDev &S, 
 // (corners of weight exactly 0 on the edges of a face are read from the nearest cell of shell s-1).  Bit for bit
 // the columns of sweep_cell (tests/test_gpu_parity.py::test_fast_sweep_equals_the_general_sweep runs that one for every
 // shell, C2R_SWEEP_GENERIC=1, in a process of its own and compares the columns).
-template <bool OPEN>
+// EXT: as in sweep_cell.
+template <bool OPEN, bool EXT = false>
 __device__ __forceinline__ void sweep_cell_fast(const SweepArgs &A, const SrcDev &S, const ShellGeom &G, int t) {
+  static_assert(OPEN || !EXT, "a source outside the mesh needs an open axis");
   const Grid &g = A.g;
   const StepScalars &sc = A.sc;
   int di, dj, dk;
@@ -591,8 +603,9 @@ __device__ __forceinline__ void sweep_cell_fast(const SweepArgs &A, const SrcDev
   global_double *cs = (global_double *)S.cols;
   const int i = mesh0<OPEN>(S.i0 - 1 + di, g.n1, S.wn[0]), j = mesh0<OPEN>(S.j0 - 1 + dj, g.n2, S.wn[1]),
             k = mesh0<OPEN>(S.k0 - 1 + dk, g.n3, S.wn[2]);
-  double u_HI, u_HeI, u_HeII;
-  sweep_cell_state(A, i, j, k, face == 2, u_HI, u_HeI, u_HeII);
+  const bool in_mesh = !EXT || (axis_in_mesh(i, g.n1) && axis_in_mesh(j, g.n2) && axis_in_mesh(k, g.n3));
+  double u_HI = 0.0, u_HeI = 0.0, u_HeII = 0.0;
+  if (in_mesh) sweep_cell_state(A, i, j, k, face == 2, u_HI, u_HeI, u_HeII);
   ShellCorners c4;
   if constexpr (OPEN) reach_short_characteristic(G, reach_shell(S.rl, S.rr, G.sp), S.rl, S.rr, face, S.i0, S.j0, S.k0, di, dj, dk, c4);
   else shell_short_characteristic(G, face, S.i0, S.j0, S.k0, di, dj, dk, c4);
@@ -603,7 +616,7 @@ __device__ __forceinline__ void sweep_cell_fast(const SweepArgs &A, const SrcDev
   const double cin_HeII = interp_column_fast(c4.s, cs[col_out((size_t)c4.p[0], 2, cz)], cs[col_out((size_t)c4.p[1], 2, cz)],
                                              cs[col_out((size_t)c4.p[2], 2, cz)], cs[col_out((size_t)c4.p[3], 2, cz)], sigma_HeII_at_ion_freq);
   const double path = c4.path * sc.dr1;
-  if (sc.use_lls) {
+  if (sc.use_lls && in_mesh) {
     // Lyman-limit-system fog on the incoming HI column (evolve_point.F90:177-180)
     const double coldensh_LLS =
         A.lls_grid ? (double)A.lls_grid[(size_t)i + (size_t)g.n1 * ((size_t)j + (size_t)g.n2 * (size_t)k)] : sc.coldensh_lls;
@@ -670,6 +683,23 @@ k_sweep_shell_fast(SweepArgs A, const SrcDev *__restrict__ src, const int *__res
   const SrcDev &S = src[active[blockIdx.y]];
   const int t = OPEN ? sweep_block_cell_open(sweep_shell_cells<OPEN>(S, G.s)) : sweep_block_cell(24 * G.s * G.s + 2);
   if (t >= 0) sweep_cell_fast<OPEN>(A, S, G, t);
+}
+
+// The two sweep kernels of a batch that holds at least one source outside the mesh (c2r_set_sources_external): the open
+// ones with the in-mesh test of sweep_cell's EXT.  Kernels of their own names, as k_rates_beam is beside k_rates: every
+// batch without such a source launches the kernels it always launched, under the names they always had.
+__global__ void __launch_bounds__(BLOCK, C2R_SWEEP_WAVES)
+k_sweep_shell_ext(SweepArgs A, const SrcDev *__restrict__ src, const int *__restrict__ active, int shell) {
+  const SrcDev &S = src[active[blockIdx.y]];
+  const int t = sweep_block_cell_open(sweep_shell_cells<true>(S, shell));
+  if (t >= 0) sweep_cell<true, true>(A, S, shell, t);
+}
+
+__global__ void __launch_bounds__(BLOCK, C2R_SWEEP_WAVES)
+k_sweep_shell_fast_ext(SweepArgs A, const SrcDev *__restrict__ src, const int *__restrict__ active, ShellGeom G) {
+  const SrcDev &S = src[active[blockIdx.y]];
+  const int t = sweep_block_cell_open(sweep_shell_cells<true>(S, G.s));
+  if (t >= 0) sweep_cell_fast<true, true>(A, S, G, t);
 }
 
 // photon_loss_src_thread(tn) += ... (evolve_point.F90:312): sum the block partials of all shells of
@@ -1662,6 +1692,9 @@ struct c2r_ctx {
   std::vector<int> srcpos;
   std::vector<double> normflux;
   double s_star = 0;
+  // c2r_set_sources_external: the largest shell that a source OUTSIDE the mesh reaches, through the vacuum between it and
+  // the far mesh faces (0: every source of the list stands inside).  The shell bookkeeping is made for it.
+  int ext_smax = 0;
   // -DPL / -DQUASARS: power-law (0) and quasar-like (1) SEDs
   double *d_sed_tab[2][4] = {{nullptr, nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr, nullptr}};
   int sed_lo[2] = {0, 0}, sed_hi[2] = {0, 0}; // 0-based [lo, hi)
@@ -2068,9 +2101,19 @@ static int ensure_pair(c2r_ctx *c, T **d, T **h, size_t *cap, size_t need) {
 // What follows from the largest shell a source of this mesh can reach: mesh/2 with periodic boundaries
 // (evolve_source.F90:105), mesh - 1 with open ones (a source in a corner, :107-108).  Host side only; the device copies
 // are made by the caller.
+// A source outside an open mesh (c2r_set_sources_external) reaches further, through the vacuum up to the far mesh face:
+// c->ext_smax, which set_sources_one has checked against EXTERNAL_REACH_MAX.  Everything that is sized or indexed by shell
+// number follows from smax here: block_base (and with it every row of loss partials, which are sized from block_base
+// differences), shell_geom, the list buffers, the probe results (sweep_batch) and start_over's round limit.
+static long long shell_blocks_upto(int smax) {
+  long long n = 0;
+  for (int s = 0; s <= smax; s++) n += (shell_count(s) + BLOCK - 1) / BLOCK;
+  return n;
+}
 static void shell_bookkeeping(c2r_ctx *c) {
   Grid &g = c->g;
-  g.smax = c->periodic ? std::max(g.l1, std::max(g.l2, g.l3)) : std::min(MAX_SUBBOX, std::max(g.n1, std::max(g.n2, g.n3)) - 1);
+  g.smax = c->periodic ? std::max(g.l1, std::max(g.l2, g.l3))
+                       : std::max(c->ext_smax, std::min(MAX_SUBBOX, std::max(g.n1, std::max(g.n2, g.n3)) - 1));
   g.colsize = (size_t)(2 * g.smax + 1) * (2 * g.smax + 1) * (2 * g.smax + 1);
   // block bookkeeping of the shells 0..smax
   c->block_base.assign(g.smax + 2, 0);
@@ -2506,13 +2549,104 @@ static void forget_horizon_loss(c2r_ctx *c) {
   c->rim_last_stamp = 0;
 }
 
-static int set_sources_one(c2r_ctx *c, int nsrc, const int *srcpos, const double *normflux, double s_star) {
+// Sources outside the mesh (c2r_set_sources_external).  Does the position p stand outside along axis d?
+static bool position_is_external(const Grid &g, const int *p, int d) {
+  const int mesh[3] = {g.n1, g.n2, g.n3};
+  return p[d] < 1 || p[d] > mesh[d];
+}
+static bool axis_is_external(const c2r_ctx *c, int ns, int d) { return position_is_external(c->g, &c->srcpos[3 * (size_t)(ns - 1)], d); }
+static bool source_is_external(const c2r_ctx *c, int ns) {
+  return axis_is_external(c, ns, 0) || axis_is_external(c, ns, 1) || axis_is_external(c, ns, 2);
+}
+// the largest shell within the reach of a source of the list that stands outside the mesh (0: there is none)
+static int external_smax(const c2r_ctx *c, int nsrc, const int *srcpos) {
+  const int mesh[3] = {c->g.n1, c->g.n2, c->g.n3};
+  int m = 0;
+  for (int s = 0; s < nsrc; s++) {
+    const int *p = srcpos + 3 * (size_t)s;
+    if (!(position_is_external(c->g, p, 0) || position_is_external(c->g, p, 1) || position_is_external(c->g, p, 2))) continue;
+    for (int d = 0; d < 3; d++) {
+      int l, r;
+      axis_reach_external(mesh[d], p[d], c->per[d], MAX_SUBBOX, l, r);
+      m = std::max(m, std::max(-l, r));
+    }
+  }
+  return m;
+}
+
+// The shell bookkeeping for the boundaries and the source list in force, and the device buffers sized by it.  The caller has
+// made sure that nothing queued still reads them.
+static int remake_shell_buffers(c2r_ctx *c) {
+  shell_bookkeeping(c);
+  HIPCHK(c, hipFree(c->d_block_base));
+  c->d_block_base = nullptr;
+  HIPCHK(c, hipMalloc(&c->d_block_base, sizeof(int) * c->block_base.size()));
+  HIPCHK(c, hipMemcpy(c->d_block_base, c->block_base.data(), sizeof(int) * c->block_base.size(), hipMemcpyHostToDevice));
+  for (int k = 0; k < 2; k++) {
+    HIPCHK(c, hipFree(c->d_list[k]));
+    HIPCHK(c, hipHostFree(c->h_list[k]));
+    c->d_list[k] = c->h_list[k] = nullptr;
+    HIPCHK(c, hipMalloc(&c->d_list[k], sizeof(int) * c->list_cap));
+    HIPCHK(c, hipHostMalloc(&c->h_list[k], sizeof(int) * c->list_cap));
+  }
+  return 0;
+}
+
+// external: c2r_set_sources_external -- a position may lie outside the mesh along axes that are open; everything is checked
+// before anything is kept
+static int set_sources_one(c2r_ctx *c, int nsrc, const int *srcpos, const double *normflux, double s_star, bool external = false) {
   if (!c) return 1;
-  if (nsrc < 0 || (nsrc > 0 && (!srcpos || !normflux))) return fail(c, "c2r_set_sources: bad arguments");
+  const char *who = external ? "c2r_set_sources_external" : "c2r_set_sources";
+  if (nsrc < 0 || (nsrc > 0 && (!srcpos || !normflux))) return fail(c, "%s: bad arguments", who);
+  const int mesh[3] = {c->g.n1, c->g.n2, c->g.n3};
+  bool any_external = false;
   for (int s = 0; s < nsrc; s++) {
     const int *p = srcpos + 3 * s;
-    if (p[0] < 1 || p[0] > c->g.n1 || p[1] < 1 || p[1] > c->g.n2 || p[2] < 1 || p[2] > c->g.n3)
-      return fail(c, "c2r_set_sources: source %d at (%d,%d,%d) outside the mesh", s + 1, p[0], p[1], p[2]);
+    const bool out[3] = {position_is_external(c->g, p, 0), position_is_external(c->g, p, 1), position_is_external(c->g, p, 2)};
+    if (!(out[0] || out[1] || out[2])) continue;
+    if (!external) return fail(c, "c2r_set_sources: source %d at (%d,%d,%d) outside the mesh", s + 1, p[0], p[1], p[2]);
+    any_external = true;
+    int l[3], r[3];
+    for (int d = 0; d < 3; d++) {
+      if (out[d] && c->per[d])
+        return fail(c, "c2r_set_sources_external: source %d at (%d,%d,%d) stands outside the mesh along axis %d, which is periodic "
+                    "(c2r_set_boundaries_axes opens an axis)", s + 1, p[0], p[1], p[2], d);
+      axis_reach_external(mesh[d], p[d], c->per[d], MAX_SUBBOX, l[d], r[d]);
+      // a reach clamped at max_subbox that ends before the mesh begins: no box of this source ever holds a mesh cell, and a
+      // pass would sweep up to (max_subbox + 1)^3 cells of vacuum for nothing
+      if (out[d] && (p[d] < 1 ? 1 - p[d] : p[d] - mesh[d]) > MAX_SUBBOX)
+        return fail(c, "c2r_set_sources_external: source %d at (%d,%d,%d) stands more than max_subbox = %d cells from the mesh along "
+                    "axis %d: its sub-boxes never reach a mesh cell", s + 1, p[0], p[1], p[2], MAX_SUBBOX, d);
+    }
+    const int refusal = external_reach_refusal(l, r);
+    if (refusal == 1)
+      return fail(c, "c2r_set_sources_external: source %d at (%d,%d,%d) reaches over (%d..%d, %d..%d, %d..%d), more than %d cells to "
+                  "one side", s + 1, p[0], p[1], p[2], l[0], r[0], l[1], r[1], l[2], r[2], EXTERNAL_REACH_MAX);
+    if (refusal == 2)
+      return fail(c, "c2r_set_sources_external: source %d at (%d,%d,%d) reaches over (%d..%d, %d..%d, %d..%d), 2^31 cells or more",
+                  s + 1, p[0], p[1], p[2], l[0], r[0], l[1], r[1], l[2], r[2]);
+  }
+  // What is indexed by mesh faces and mesh cells is not built for a source outside the mesh.
+  if (any_external && c->face_on)
+    return fail(c, "c2r_set_sources_external: the escape maps are on (c2r_enable_face_loss), which are not built for sources outside the mesh");
+  if (any_external && c->rim_on)
+    return fail(c, "c2r_set_sources_external: the horizon loss is on (c2r_enable_horizon_loss), which is not built for sources outside the mesh");
+  const int ext_smax = external ? external_smax(c, nsrc, srcpos) : 0;
+  if (ext_smax != c->ext_smax) {
+    // the shell bookkeeping changes size: nothing queued may still read it, and no pass may be open
+    if (c->pass_open)
+      return fail(c, "%s: a pass opened by c2r_pass_sources_begin is still open (close it with c2r_pass_sources_end first)", who);
+    if (shell_blocks_upto(std::max(ext_smax, c->g.smax)) > (long long)INT32_MAX)
+      return fail(c, "internal: %s: the blocks of the shells 0..%d do not fit 32 bits", who, ext_smax);
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream2));
+    HIPCHK(c, hipStreamSynchronize(c->stream3));
+    HIPCHK(c, hipStreamSynchronize(c->stream_probe));
+    c->ext_smax = ext_smax;
+    if (remake_shell_buffers(c)) return 1;
+  } else if (external && c->pass_open) {
+    return fail(c, "c2r_set_sources_external: a pass opened by c2r_pass_sources_begin is still open (close it with c2r_pass_sources_end first)");
   }
   // What the last pass learnt about each source -- how many sub-boxes it needed: the size of its column block and the
   // rounds that are swept without waiting for a loss probe -- stays valid across time steps as long as the source list
@@ -2526,17 +2660,33 @@ static int set_sources_one(c2r_ctx *c, int nsrc, const int *srcpos, const double
   if (!same_list) {
     // another list (the next redshift slice: sources appear, disappear, change places in the list): what is known about a
     // cell's source goes with the cell.  Sources that share a cell share the larger count.
+    // (the key: three 21-bit fields, each position biased by 2^20 -- a source outside the mesh may stand at a position <= 0;
+    // one beyond the fields, which no box of MAX_SUBBOX cells brings to the mesh, carries nothing over)
+    constexpr long long KEY_BIAS = 1LL << 20, KEY_SPAN = 1LL << 21;
+    auto key = [&](const int *p, long long &k) {
+      k = 0;
+      for (int d = 2; d >= 0; d--) {
+        const long long v = (long long)p[d] + KEY_BIAS;
+        if (v < 0 || v >= KEY_SPAN) return false;
+        k = k * KEY_SPAN + v;
+      }
+      return true;
+    };
     std::unordered_map<long long, int> known;
     if (c->prev_nbox.size() == (size_t)c->nsrc && c->srcpos.size() == 3 * (size_t)c->nsrc)
       for (int s = 0; s < c->nsrc; s++) {
         const int *p = &c->srcpos[3 * (size_t)s];
-        int &v = known[((long long)p[2] * 8192 + p[1]) * 8192 + p[0]];
+        long long k;
+        if (!key(p, k)) continue;
+        int &v = known[k];
         v = std::max(v, c->prev_nbox[(size_t)s]);
       }
     std::vector<int> carried((size_t)nsrc, 0);
     for (int s = 0; s < nsrc; s++) {
       const int *p = srcpos + 3 * (size_t)s;
-      const auto it = known.find(((long long)p[2] * 8192 + p[1]) * 8192 + p[0]);
+      long long k;
+      if (!key(p, k)) continue;
+      const auto it = known.find(k);
       if (it != known.end()) carried[(size_t)s] = it->second;
     }
     c->prev_nbox.swap(carried);
@@ -2985,7 +3135,8 @@ static Reach mesh_reach(const Grid &g) {
 static Reach open_reach(const Grid &g, const bool *per, const int *srcpos) {
   const int mesh[3] = {g.n1, g.n2, g.n3};
   Reach R;
-  for (int d = 0; d < 3; d++) axis_reach(mesh[d], srcpos[d], per[d], MAX_SUBBOX, R.l[d], R.r[d]);
+  // (axis_reach's numbers for a source inside the mesh; one outside along an open axis reaches through the vacuum)
+  for (int d = 0; d < 3; d++) axis_reach_external(mesh[d], srcpos[d], per[d], MAX_SUBBOX, R.l[d], R.r[d]);
   return R;
 }
 static Reach source_reach(const c2r_ctx *c, int ns) {
@@ -3006,7 +3157,8 @@ static int source_smax(const c2r_ctx *c, int ns) {
 }
 
 // entries per column array of source ns's block for the shells 0..cap: the whole shells, or (open boundaries) their cells
-// within the source's reach -- never more than the mesh has cells
+// within the source's reach -- never more than the mesh has cells, unless the source stands outside it (its reach then runs
+// through the vacuum between them: fewer than 2^31 cells, c2r_set_sources_external)
 static size_t source_block_entries(const c2r_ctx *c, int ns, int cap) {
   if (c->periodic) return block_doubles(cap) / 6;
   const Reach R = source_reach(c, ns);
@@ -3283,6 +3435,8 @@ struct Batch {
   int ntiles = 0;                   // tiles in the rates launch's list h_tiles[set] (0: none, every tile of the mesh)
   bool beamed = false;              // some source of the batch has a beam or a finite horizon: its rates launch is k_rates_beam
   bool curved = false;              // some source of the batch has a curve: its rates launch is k_rates_curve
+  bool external = false;            // some source of the batch stands outside the mesh: its shells are k_sweep_shell(_fast)_ext's,
+                                    // and its kept losses are k_loss's (queue_kept_losses)
   std::vector<int> rim_ns;          // horizon loss: the sources (1-based) whose sums queue_horizon_rim has queued, in row order
 };
 
@@ -3408,6 +3562,7 @@ static int place_batch(const PassCtx &P, const std::vector<int> &mine, Batch &B)
   B.run.assign((size_t)B.nb, SrcRun());
   B.beamed = false;
   B.curved = false;
+  B.external = false;
   for (bool released = false;;) {
     c->seg_cur[set] = 0;
     c->seg_used[set] = 0;
@@ -3474,6 +3629,7 @@ static int place_batch(const PassCtx &P, const std::vector<int> &mine, Batch &B)
     source_cut(c, r.ns, S);
     B.beamed = B.beamed || S.cut != CUT_NONE;
     B.curved = B.curved || (S.cut & CUT_CURVE) != 0;
+    B.external = B.external || (c->ext_smax > 0 && source_is_external(c, r.ns));
   }
   // coldensh_out = 0 for every new source (evolve_source.F90:94-95) serves two purposes in the
   // reference: the "already done" marker (replaced here by the shell order: every cell is visited
@@ -3610,16 +3766,22 @@ static int launch_shells(PassCtx &P, Batch &B, const Box &box, int s_lo, int s_h
     const int nlaunch = nblk >= 64 ? ((nblk + 7) & ~7) : nblk;
     for (int a = 0; a < nact; a++)
       if (s <= B.run[act[a]].smax) B.run[act[a]].sweep_threads += (long long)nlaunch * BLOCK;
-    // (open boundaries: positions are below the mesh's cell count, 32 bits hold them in every shell)
+    // (open boundaries: positions are below the cells of the source's reach -- at most the mesh's for a source inside it, and
+    // fewer than 2^31 for one outside, which c2r_set_sources_external refuses otherwise: 32 bits hold them in every shell)
     const bool fast = s >= 2 && (s <= SHELL_FAST_MAX || !c->periodic) && !P.generic_sweep;
     if (fast && c->periodic)
       hipLaunchKernelGGL(k_sweep_shell_fast<false>, dim3(nlaunch, nact), dim3(BLOCK), 0, c->stream, SA, c->d_src[B.set],
+                         c->d_list[B.set] + act_off, c->shell_geom[(size_t)s]);
+    else if (fast && B.external) // (a source outside the mesh in the batch: the kernels that know vacuum cells)
+      hipLaunchKernelGGL(k_sweep_shell_fast_ext, dim3(nlaunch, nact), dim3(BLOCK), 0, c->stream, SA, c->d_src[B.set],
                          c->d_list[B.set] + act_off, c->shell_geom[(size_t)s]);
     else if (fast)
       hipLaunchKernelGGL(k_sweep_shell_fast<true>, dim3(nlaunch, nact), dim3(BLOCK), 0, c->stream, SA, c->d_src[B.set],
                          c->d_list[B.set] + act_off, c->shell_geom[(size_t)s]);
     else if (c->periodic)
       hipLaunchKernelGGL(k_sweep_shell<false>, dim3(nlaunch, nact), dim3(BLOCK), 0, c->stream, SA, c->d_src[B.set], c->d_list[B.set] + act_off, s);
+    else if (B.external)
+      hipLaunchKernelGGL(k_sweep_shell_ext, dim3(nlaunch, nact), dim3(BLOCK), 0, c->stream, SA, c->d_src[B.set], c->d_list[B.set] + act_off, s);
     else
       hipLaunchKernelGGL(k_sweep_shell<true>, dim3(nlaunch, nact), dim3(BLOCK), 0, c->stream, SA, c->d_src[B.set], c->d_list[B.set] + act_off, s);
     c->tm.sweep_launches++;
@@ -3821,7 +3983,9 @@ static int close_boxes(PassCtx &P, Batch &B) {
     // the terms of the kept loss of a round that was the last for geometric reasons come out of the rates launch: the
     // surface cells in the shells of that round (heating kernels do not keep photo_out, see k_rates)
     S.loss_lo = -1;
-    if (r.final_loss_due && c->isothermal)
+    // (a batch with a source outside the mesh: the surface of such a box has vacuum cells, which no rates launch visits --
+    // the kept losses of the whole batch are evaluated by k_loss from the columns, as in a heating run, the same bits)
+    if (r.final_loss_due && c->isothermal && !B.external)
       S.loss_lo = c->periodic && r.nbox > 1 ? box_smax(round_box(P.reach, r.nbox - 1)) + 1 : 0; // (open: every shell of the box)
     // (known0: what was known before this batch -- a batch that started over has raised prev_nbox meanwhile)
     const int known = B.known0[(size_t)b];
@@ -3885,9 +4049,23 @@ static int build_tile_lists(const PassCtx &P, Batch &B) {
   const int nblk = nt1 * nt2 * nt3;
   B.ntiles = 0;
   bool full = false;
+  // The final box of a source as far as it lies in the mesh: along an open axis the box of a source outside the mesh runs
+  // through vacuum, which has no tiles -- cut there at the mesh faces (for a source inside, the box lies in the mesh and the
+  // cut does nothing); false: no cell of the box is a mesh cell
+  auto mesh_box = [&](int b, Box &fb) {
+    fb = round_box(B.run[b].reach, B.run[b].nbox);
+    const int *p = &c->srcpos[3 * (size_t)(B.run[b].ns - 1)];
+    for (int d = 0; d < 3; d++) {
+      if (c->per[d]) continue;
+      fb.lo[d] = std::max(fb.lo[d], 1 - p[d]);
+      fb.hi[d] = std::min(fb.hi[d], mesh[d] - p[d]);
+      if (fb.lo[d] > fb.hi[d]) return false;
+    }
+    return true;
+  };
   for (int b = 0; b < B.nb && !full; b++) {
-    const Box fb = round_box(B.run[b].reach, B.run[b].nbox);
-    full = B.run[b].nbox > 0;
+    Box fb;
+    full = B.run[b].nbox > 0 && mesh_box(b, fb);
     for (int d = 0; d < 3; d++) full = full && (fb.hi[d] - fb.lo[d] + 1 >= mesh[d]);
   }
   // few sources one of which fills the mesh: every cell simply walks all of them
@@ -3897,10 +4075,11 @@ static int build_tile_lists(const PassCtx &P, Batch &B) {
   std::vector<int> cov[3];
   const int tsz[3] = {8, 8, 4}, ntd[3] = {nt1, nt2, nt3};
   auto covered = [&](int b) {
-    const Box fb = round_box(B.run[b].reach, B.run[b].nbox); // (open boundaries: inside the mesh, the modulo below does nothing)
+    Box fb; // (an open axis: cut at the mesh faces, so the modulo below does nothing there)
+    for (int d = 0; d < 3; d++) cov[d].clear();
+    if (!mesh_box(b, fb)) return;
     const int *p = &c->srcpos[3 * (size_t)(B.run[b].ns - 1)];
     for (int d = 0; d < 3; d++) {
-      cov[d].clear();
       int last = -1;
       std::vector<unsigned char> seen((size_t)ntd[d], 0);
       for (int o = fb.lo[d]; o <= fb.hi[d]; o++) {
@@ -4036,7 +4215,7 @@ static int launch_rates(const PassCtx &P, Batch &B, bool last_batch) {
 // The losses that are kept but decided nothing (rounds that were a source's last for geometric reasons), one group of sources
 // per such round (the same for every source of a mesh, so one group).  Isothermal: the rates launch has left their terms in
 // the column blocks; they are added up behind it, on its stream, and the sums go to the host to be resolved later
-// (resolve_tails).  Heating: boundary_loss evaluates them now.  The batch's losses and sub-box counts join c->tails.
+// (resolve_tails).  Heating, and a batch with a source outside the mesh (close_boxes): boundary_loss evaluates them now.  The batch's losses and sub-box counts join c->tails.
 static int queue_kept_losses(const PassCtx &P, Batch &B) {
   c2r_ctx *c = P.c;
   const int set = B.set;
@@ -4067,7 +4246,7 @@ static int queue_kept_losses(const PassCtx &P, Batch &B) {
       f_lo = f_hi = 0;
       for (int j = 0; j < nf; j++) f_hi = std::max(f_hi, box_smax(round_box(B.run[fl[j]].reach, fr)));
     }
-    if (c->isothermal) {
+    if (c->isothermal && !B.external) {
       HIPCHK(c, hipMemcpyAsync(c->d_list[set] + B.list_used, fl, sizeof(int) * nf, hipMemcpyHostToDevice, c->stream2));
       const int nblk = c->block_base[f_hi + 1] - c->block_base[f_lo];
       const size_t need = (size_t)nblk * (size_t)nf;
@@ -4138,7 +4317,8 @@ static int pass_list(c2r_ctx *c, const std::vector<int> &dealt, int nslab = 0) {
   if (!c->periodic) {
     const int mesh[3] = {c->g.n1, c->g.n2, c->g.n3};
     for (int d = 0; d < 3; d++)
-      if (!c->per[d]) { widest.r[d] = std::min(MAX_SUBBOX, mesh[d] - 1); widest.l[d] = -widest.r[d]; }
+      // (... or of a source outside the mesh, through the vacuum: c->ext_smax)
+      if (!c->per[d]) { widest.r[d] = std::max(c->ext_smax, std::min(MAX_SUBBOX, mesh[d] - 1)); widest.l[d] = -widest.r[d]; }
   }
   PassCtx P{c, scalars(c), SedSet(), false, widest, generic_sweep, arena_log};
   P.ss = sedset(c, &P.multi);
@@ -4322,6 +4502,9 @@ extern "C" int c2r_do_source(c2r_ctx *c, int ns) {
   if (check_ready(c, "c2r_do_source")) return 1;
   // (NumSrc < ns <= NumSrc + nplane: plane ns - NumSrc)
   if (ns < 1 || ns > c->nsrc + c->nplane) return fail(c, "c2r_do_source: source %d not in [1,%d]", ns, c->nsrc + c->nplane);
+  if (c->ext_smax > 0 && ns <= c->nsrc && source_is_external(c, ns))
+    return fail(c, "c2r_do_source: source %d stands outside the mesh (c2r_set_sources_external), which the per-point route is not built for "
+                "(c2r_pass_sources sweeps it)", ns);
   return pass_list(c, std::vector<int>{ns});
 }
 
@@ -4439,6 +4622,8 @@ extern "C" int c2r_evolve0d(c2r_ctx *c, const int rtpos[3], int ns, int niter, i
   if (check_ready(c, "c2r_evolve0d")) return 1;
   if (ns < 1 || ns > c->nsrc) return fail(c, "c2r_evolve0d: source %d not in [1,%d]", ns, c->nsrc);
   if (c->pass_open) return fail(c, "c2r_evolve0d: a pass opened by c2r_pass_sources_begin is still open");
+  if (c->ext_smax > 0 && source_is_external(c, ns))
+    return fail(c, "c2r_evolve0d: source %d stands outside the mesh (c2r_set_sources_external), which the per-point route is not built for", ns);
   HIPCHK(c, hipSetDevice(c->device));
   const Grid g = c->g;
   const int *sp = &c->srcpos[3 * (size_t)(ns - 1)];
@@ -4922,6 +5107,10 @@ extern "C" int c2r_set_sources(c2r_ctx *c, int nsrc, const int *srcpos, const do
   if (int e_ = set_sources_one(c, nsrc, srcpos, normflux, s_star)) return e_;
   return for_replicas(c, [&](c2r_ctx *r) { return set_sources_one(r, nsrc, srcpos, normflux, s_star); });
 }
+extern "C" int c2r_set_sources_external(c2r_ctx *c, int nsrc, const int *srcpos, const double *normflux, double s_star) {
+  if (int e_ = set_sources_one(c, nsrc, srcpos, normflux, s_star, true)) return e_;
+  return for_replicas(c, [&](c2r_ctx *r) { return set_sources_one(r, nsrc, srcpos, normflux, s_star, true); });
+}
 
 // ---------------------------------------------------------------------------------------------
 // escape maps
@@ -4936,6 +5125,8 @@ static int enable_face_loss_one(c2r_ctx *c, int on) {
     return 0;
   }
   if (c->face_on) return 0;
+  if (c->ext_smax > 0)
+    return fail(c, "c2r_enable_face_loss: a source of the list stands outside the mesh (c2r_set_sources_external), which the escape maps are not built for");
   if (alloc_face_maps(c)) return 1;
   c->face_on = true;
   return 0;
@@ -5011,6 +5202,8 @@ static int enable_horizon_loss_one(c2r_ctx *c, int on) {
     return 0;
   }
   if (c->rim_on) return 0;
+  if (c->ext_smax > 0)
+    return fail(c, "c2r_enable_horizon_loss: a source of the list stands outside the mesh (c2r_set_sources_external), which the horizon loss is not built for");
   const size_t n0 = (size_t)c->g.n1, n1 = (size_t)c->g.n2, n2 = (size_t)c->g.n3;
   auto allocate = [&]() -> int {
     c->rim_terms_cap = 2 * (n1 * n2 + n0 * n2 + n0 * n1);
@@ -5188,6 +5381,12 @@ static int set_boundaries_one(c2r_ctx *c, const int periodic[3]) {
     if (per[c->plane[p].src.axis])
       return fail(c, "c2r_set_boundaries: plane source %d travels along axis %d, which has to stay open (remove the planes with "
                   "c2r_set_plane_sources(ctx, 0, NULL) first)", p + 1, c->plane[p].src.axis);
+  for (int s = 0; s < c->nsrc; s++)
+    for (int d = 0; d < 3; d++)
+      if (per[d] && axis_is_external(c, s + 1, d))
+        return fail(c, "c2r_set_boundaries: source %d at (%d,%d,%d) stands outside the mesh along axis %d, which has to stay open "
+                    "(replace the source list first)", s + 1, c->srcpos[3 * (size_t)s], c->srcpos[3 * (size_t)s + 1],
+                    c->srcpos[3 * (size_t)s + 2], d);
   if (per[0] == c->per[0] && per[1] == c->per[1] && per[2] == c->per[2]) return 0;
   const bool want = per[0] && per[1] && per[2];
   HIPCHK(c, hipSetDevice(c->device));
@@ -5199,18 +5398,9 @@ static int set_boundaries_one(c2r_ctx *c, const int periodic[3]) {
   c->periodic = want;
   for (int d = 0; d < 3; d++) c->per[d] = per[d];
   if (c->face_on && alloc_face_maps(c)) return 1; // other faces are open now: maps of the new sizes, zeroed
-  shell_bookkeeping(c);
-  HIPCHK(c, hipFree(c->d_block_base));
-  c->d_block_base = nullptr;
-  HIPCHK(c, hipMalloc(&c->d_block_base, sizeof(int) * c->block_base.size()));
-  HIPCHK(c, hipMemcpy(c->d_block_base, c->block_base.data(), sizeof(int) * c->block_base.size(), hipMemcpyHostToDevice));
-  for (int k = 0; k < 2; k++) {
-    HIPCHK(c, hipFree(c->d_list[k]));
-    HIPCHK(c, hipHostFree(c->h_list[k]));
-    c->d_list[k] = c->h_list[k] = nullptr;
-    HIPCHK(c, hipMalloc(&c->d_list[k], sizeof(int) * c->list_cap));
-    HIPCHK(c, hipHostMalloc(&c->h_list[k], sizeof(int) * c->list_cap));
-  }
+  // (an axis that opens shortens the reach of an external source along it from the periodic one to at most mesh - 1)
+  c->ext_smax = external_smax(c, c->nsrc, c->srcpos.data());
+  if (remake_shell_buffers(c)) return 1;
   if (c->d_point_cols) { // c2r_evolve0d's block holds the whole reach of a source: made anew at the next call
     HIPCHK(c, hipFree(c->d_point_cols));
     c->d_point_cols = nullptr;

@@ -348,8 +348,35 @@ C2R_HD void axis_reach(int mesh, int pos, int periodic, int max_subbox, int &l, 
   r = right < max_subbox ? right : max_subbox;
 }
 
+// The same for a source that may stand OUTSIDE the mesh along an open axis (c2r_set_sources_external: pos < 1 or
+// pos > mesh): its mesh is the real one extended by vacuum up to the source, so the reach ends at the far mesh face on
+// the side the mesh lies on and is 0 on the other, l = -min(max_subbox, max(pos - 1, 0)), r = min(max_subbox,
+// max(mesh - pos, 0)).  l <= 0 <= r always; a position inside the mesh gives axis_reach's numbers, a periodic axis too.
+C2R_HD void axis_reach_external(int mesh, int pos, int periodic, int max_subbox, int &l, int &r) {
+  const int in_l = pos - 1 > 0 ? pos - 1 : 0, in_r = mesh - pos > 0 ? mesh - pos : 0;
+  const int left = periodic ? mesh / 2 : in_l, right = periodic ? mesh / 2 - 1 + mesh % 2 : in_r;
+  l = -(left < max_subbox ? left : max_subbox);
+  r = right < max_subbox ? right : max_subbox;
+}
+
+// What c2r_set_sources_external refuses of a reach: 1: max(|l_d|, r_d) > EXTERNAL_REACH_MAX, the bound up to which
+// ShellGeom's (s - 1/2) / s * s is exact; 2: prod_d (r_d - l_d + 1) >= 2^31, the fast sweep's 32-bit positions; 0: neither
+constexpr int EXTERNAL_REACH_MAX = 4096;
+C2R_HD int external_reach_refusal(const int *l, const int *r) {
+  long long cells = 1;
+  for (int d = 0; d < 3; d++) {
+    if (-l[d] > EXTERNAL_REACH_MAX || r[d] > EXTERNAL_REACH_MAX) return 1;
+    cells *= (long long)(r[d] - l[d] + 1);
+  }
+  return cells >= (1LL << 31) ? 2 : 0;
+}
+
 // 0-based mesh index of the cell at offset `off` (within the reach) from a source at the 1-based position pos
 C2R_HD int axis_mesh_index(int pos, int off, int w) { return axis_wrap(pos - 1 + off, w); }
+
+// Does the 0-based index x (after the wrap: axis_mesh_index) lie in a mesh of n cells?  One unsigned compare: a negative
+// index reads as a number beyond any mesh.  Only a box cell of an external source can fail it -- a VACUUM cell.
+C2R_HD bool axis_in_mesh(int x, int n) { return (unsigned)x < (unsigned)n; }
 
 // offset from that source of the cell with the 0-based mesh index `cell`.  Periodic axis: the image in
 // [-w/2, w - w/2 - 1], the reach of max_subbox = infinity -- a cell within a shorter reach [l, r] has its offset there

@@ -363,18 +363,23 @@ class HipEngine:
         """cosmo_evol's ndens = ndens / zfactor3 on the device copy (cosmology.f90:193)."""
         self._chk(self.lib.c2r_scale_ndens(self.h, float(divisor)))
 
-    def set_sources(self, src: SourceProps):
+    def set_sources(self, src: SourceProps, external=False):
         pos = np.ascontiguousarray(src.srcpos, dtype=np.int32).reshape(-1)
         nf = _f64(src.NormFlux).reshape(-1)
         assert pos.size == 3 * nf.size
-        self._chk(self.lib.c2r_set_sources(self.h, int(nf.size), pos.ctypes.data_as(C.POINTER(C.c_int)), _dp(nf),
-                                           float(src.S_star)))
+        call = self.lib.c2r_set_sources_external if external else self.lib.c2r_set_sources
+        self._chk(call(self.h, int(nf.size), pos.ctypes.data_as(C.POINTER(C.c_int)), _dp(nf), float(src.S_star)))
         self.nsrc = int(nf.size)
         for idx, flux, star in ((1, src.NormFluxPL, src.pl_S_star), (2, src.NormFluxQPL, src.qpl_S_star)):
             if flux is not None:
                 f = _f64(flux).reshape(-1)
                 assert f.size == nf.size
                 self._chk(self.lib.c2r_set_sources_sed(self.h, idx, _dp(f), float(star)))
+
+    def set_sources_external(self, src: SourceProps):
+        """c2r_set_sources_external: set_sources for a list in which a source may stand outside the mesh (a position < 1 or
+        > mesh) along axes that are open (set_boundaries); its box runs through vacuum up to the mesh."""
+        self.set_sources(src, external=True)
 
     def set_source_beams(self, beams=None):
         """c2r_set_source_beams: one beam per point source, in source order -- None (no beam), a dict or a tuple

@@ -188,6 +188,17 @@ module c2ray_hip
        real(c_double), value :: s_star
      end function c2r_set_sources
 
+     !> c2r_set_sources for a list in which a source may stand outside the mesh along open axes
+     integer(c_int) function c2r_set_sources_external(ctx, nsrc, srcpos, normflux, s_star) &
+          bind(C, name="c2r_set_sources_external")
+       import :: c_int, c_ptr, c_double
+       type(c_ptr), value :: ctx
+       integer(c_int), value :: nsrc
+       integer(c_int), intent(in) :: srcpos(*)
+       real(c_double), intent(in) :: normflux(*)
+       real(c_double), value :: s_star
+     end function c2r_set_sources_external
+
      integer(c_int) function c2r_set_sed_tables(ctx, sed, photo_thick, photo_thin, heat_thick, heat_thin, &
           lower, upper) bind(C, name="c2r_set_sed_tables")
        import :: c_int, c_ptr, c_double

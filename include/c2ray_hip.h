@@ -113,6 +113,28 @@ int c2r_set_clumping_grid(c2r_ctx *ctx, const float *clumping_grid);
  * radiation_sed_parameters:S_star (sourceprops_test.F90:38-40). */
 int c2r_set_sources(c2r_ctx *ctx, int nsrc, const int *srcpos, const double *normflux, double s_star);
 
+/* Point sources OUTSIDE the mesh: c2r_set_sources with one check replaced -- a position may lie outside the mesh
+ * (srcpos_d < 1 or srcpos_d > mesh_d) along axes that are open (c2r_set_boundaries_axes): a quasar beside a slab, the
+ * bright neighbour of a light-cone strip.  Diverging rays and 1/r^2 dilution, which no plane source can stand in for, and
+ * none of the padding cells a wider mesh would pay for in every grid.  The reference has nothing of the kind.
+ *   The mesh of such a source is the real one extended by vacuum up to the source: along an open axis its reach is
+ * l = -min(max_subbox, max(srcpos - 1, 0)), r = min(max_subbox, max(mesh - srcpos, 0)).  A cell of its sub-box that lies
+ * outside the mesh is a vacuum cell: neufrac * ndens = 0.0 exactly for HI, HeI and HeII, no LLS fog (scalar or grid),
+ * N_out = N_in.  A mesh cell gets the arithmetic it always got, and rates are formed for mesh cells only.  photon_loss(1)
+ * runs over the whole surface of the final sub-box, vacuum cells included -- photons that leave through a face of the
+ * vacuum never meet the mesh --, so emitted = absorbed + lost keeps holding; the loss that decides whether a box grows and
+ * sum_nbox are those of open boundaries.  Cost: the column scratch and the sweep follow the extended box, the rates the
+ * mesh cells in it; c2r_get_source_trace counts the vacuum.
+ *   A list whose sources all stand inside gives the bits, and launches the kernels, of c2r_set_sources, which keeps
+ * refusing a position outside.  Everything is checked before anything is kept; refused, with a message that names the
+ * source: a position outside along a periodic axis (so: any all-periodic context); a position more than max_subbox cells
+ * from the mesh (no sub-box of it ever holds a mesh cell); a reach of more than 4096 cells to one side; a reach of 2^31
+ * cells or more (a thin, long mesh: (2,2,1700) and a source 1149 cells beyond two faces); and a pass that is still open.  c2r_set_boundaries(_axes) refuses to make an axis
+ * periodic while a source stands beyond it.  Beams, horizons, source curves, c2r_set_sources_sed, heating and LLS work
+ * unchanged.  Not built, and refused while a source of the list stands outside: c2r_enable_face_loss,
+ * c2r_enable_horizon_loss (and this call while either is on), and for such a source c2r_evolve0d and c2r_do_source. */
+int c2r_set_sources_external(c2r_ctx *ctx, int nsrc, const int *srcpos, const double *normflux, double s_star);
+
 /* The -DPL / -DQUASARS builds of the reference give every source up to two more SEDs
  * (radiation_photoionrates.f90:215-228, 256-271).  sed = 1: power law (pl_*), sed = 2: quasar-like (qpl_*).
  *   c2r_set_sed_tables   pl_/qpl_photo_thick/thin_table, pl_/qpl_heat_thick/thin_table (heat may be NULL
