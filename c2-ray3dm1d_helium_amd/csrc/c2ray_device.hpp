@@ -131,6 +131,14 @@ constexpr double sigma_H_he2 = 1.230695924714239e-19;
 // radiation_tables.f90:59-61
 constexpr double minlogtau = -20.0;
 constexpr double dlogtau = (4.0 - (-20.0)) / (double)(float)NTAU;
+// 1/dlogtau in two pieces, Ch = RN(1/dlogtau) and Cl = RN(1/dlogtau - Ch): RN(fma(a, Ch, RN(a * Cl))) is the correctly
+// rounded a/dlogtau for EVERY a whose a * Cl does not underflow (division by a constant known in advance: Brisebarre,
+// Muller and Raina 2004; Brisebarre and Muller 2008) -- for this divisor, not for any: the pair has to pass a check of the
+// quotients that lie next to a rounding midpoint, which tests/test_table_step_division_host.py does in exact arithmetic
+// (and derives the two literals from dlogtau).  table_position_of_log is the one user.
+constexpr double rdlogtau_hi = 0x1.4d55555555555p+6;
+constexpr double rdlogtau_lo = 0x1.b0aaaaaaaaaabp-49;
+static_assert(NTAU == 2000 && dlogtau == 0x1.89374bc6a7efap-7, "rdlogtau_hi and rdlogtau_lo are proven for this table step alone");
 // evolve_point.F90:91, radiation_photoionrates.f90:342,482
 constexpr double max_coldensh = C2R_F(2e29);
 constexpr double tau_photo_limit = C2R_F(1.0e-7);
@@ -536,14 +544,15 @@ C2R_HD double dmax_num(double a, double b) { return a > b ? a : b; }
 C2R_HD double dmin_num(double a, double b) { return a < b ? a : b; }
 C2R_HD double dmax_const(double a, double k) { return a > k ? a : k; }
 #endif
+// num/dlogtau, correctly rounded by two roundings with the constant's reciprocal in two pieces (at rdlogtau_hi, above):
+// a product and an fma where Markstein's sequence (div_recip) takes three instructions.  Any num that is 0 or at least
+// 2^-900 in magnitude (the product with rdlogtau_lo must not underflow); +-inf gives +-inf.
+C2R_HD double div_by_table_step(double num) { return __builtin_fma(num, rdlogtau_hi, num * rdlogtau_lo); }
 // the position that belongs to lt = log10(max(1e-20, tau))
 C2R_HD TauPos table_position_of_log(double lt) {
-  // (lt - minlogtau)/dlogtau, correctly rounded through the constant's reciprocal (div_recip);
-  // the numerator lies in [0, 24.5], dlogtau = 0x1.89374bc6a7efap-7
-  const double num = lt - minlogtau;
-  const double rdl = 1.0 / dlogtau;
-  const double q0 = num * rdl;
-  const double quo = __builtin_fma(__builtin_fma(-dlogtau, q0, num), rdl, q0);
+  // (lt - minlogtau)/dlogtau.  The numerator is 0, a few ulp of 20 below 0, or in [2^-48, 24.5] for finite lt; +inf (which
+  // max(tau, 1e-20) lets through) gives +inf where Markstein's sequence gave a NaN, and the min below makes NTAU of either.
+  const double quo = div_by_table_step(lt - minlogtau);
   // max(0, .) of the reference (:299) cannot bind: lt >= log10(1e-20) makes 1 + quo >= 1 - 1e-12
   const double odpos = dmin_num((double)NTAU, 1.0 + quo);
   TauPos p;
