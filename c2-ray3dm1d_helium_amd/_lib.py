@@ -106,6 +106,12 @@ SYMBOLS = {
     "c2r_scale_ndens": (C.c_int, [C.c_void_p, C.c_double]),
     "c2r_set_sources": (C.c_int, [C.c_void_p, C.c_int, _ip, _dp, C.c_double]),
     "c2r_set_sources_external": (C.c_int, [C.c_void_p, C.c_int, _ip, _dp, C.c_double]),
+    "c2r_select_source_face_exit": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _ip]),
+    "c2r_download_source_face_exit": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, _ip, _ip]),
+    "c2r_set_source_face_entry": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, C.c_int]),
+    "c2r_get_source_face_entry": (C.c_int, [C.c_void_p, C.c_int, _ip, _ip]),
+    "c2r_set_mesh_origin": (C.c_int, [C.c_void_p, _ip]),
+    "c2r_get_mesh_origin": (C.c_int, [C.c_void_p, _ip]),
     "c2r_set_sed_tables": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, _dp, _dp, C.c_int, C.c_int]),
     "c2r_set_sources_sed": (C.c_int, [C.c_void_p, C.c_int, _dp, C.c_double]),
     "c2r_set_source_beams": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(SourceBeam)]),

@@ -5,7 +5,10 @@
 //                                  short-characteristics interpolation of the three incoming
 //                                  columns (cinterp) + the cell's own columns (evolve0D, first half);
 //                                  k_sweep_shell_ext, k_sweep_shell_fast_ext for a batch with a source outside the mesh
-//                                  (c2r_set_sources_external): cells of its box beyond the mesh are vacuum
+//                                  (c2r_set_sources_external): cells of its box beyond the mesh are vacuum;
+//                                  k_sweep_shell_entry, k_sweep_shell_fast_entry for a batch with a source that has entry
+//                                  columns (c2r_set_source_face_entry): the ghost layer of its face holds the strip of the
+//                                  mesh upstream; k_source_face_exit gathers the exit strips (c2ray_handover.inc)
 //   rates          k_rates         all cells x all sources of the batch, no dependencies:
 //                                  photoion_rates + accumulation into the rate grids in source order
 //                                  (evolve0D, second half)
@@ -96,6 +99,38 @@ struct SrcDev {
   double cR2[CURVE_MAX_STEPS];      // curve_fill: the squared radii of its steps, +infinity behind the last
   double cfac[CURVE_MAX_STEPS + 1]; // ... and the factor of each shell
 };
+// Entry columns of one source of the batch in flight (c2r_set_source_face_entry), a record beside its SrcDev that only the
+// kernels of a batch with such a source are given (k_sweep_shell_entry, k_sweep_shell_fast_entry, k_loss_entry).
+struct SrcEntry {
+  int on;             // 0: the source has no entry; else 1 + face, face = 2 * axis + high
+  const double *cols; // its strip: 3 F doubles, species slowest, the face cells with the lower of the two other axes fastest
+  int origin[3];      // c2r_set_mesh_origin: the deep mesh's index of this mesh's cell (1,1,1), minus 1, per axis
+};
+// The source's position as cinterp sees it: cinterp forms its crossing points from absolute coordinates, so a part of a deep mesh
+// reproduces the deep mesh's bits only with the deep mesh's coordinates -- the source's own, moved by the mesh's origin
+// (c2r_set_mesh_origin; a context with an origin runs every batch through the kernels that are given these records).  Nothing
+// else reads these three numbers: cells, offsets and blocks stay this mesh's.
+__device__ __forceinline__ void entry_cinterp_position(const SrcEntry &E, int &i0, int &j0, int &k0) {
+  i0 += E.origin[0];
+  j0 += E.origin[1];
+  k0 += E.origin[2];
+}
+// The column that a box cell OUTSIDE the mesh of a source with an entry stores as N_out: the strip's, if the cell lies in
+// the ghost layer of the entry's face (one step outside it), else `vacuum`, its N_in.  (i, j, k): the cell's 0-based mesh
+// index; the source stands beyond that face only, so the cell's two other coordinates lie in the mesh.
+__device__ __forceinline__ void entry_columns(const SrcEntry &E, const Grid &g, int i, int j, int k, double &c_HI, double &c_HeI,
+                                              double &c_HeII) {
+  // (selects on values, as in shell_decode_fast: arrays indexed by the axis would go to scratch memory)
+  const int face = E.on - 1, axis = face >> 1, high = face & 1;
+  const int xc = axis == 0 ? i : (axis == 1 ? j : k), nc = axis == 0 ? g.n1 : (axis == 1 ? g.n2 : g.n3);
+  if (xc != (high ? nc : -1)) return;
+  const int xa = axis == 0 ? j : i, xb = axis == 2 ? j : k;   // the two other axes, the lower one first
+  const int na = axis == 0 ? g.n2 : g.n1, nb = axis == 2 ? g.n2 : g.n3;
+  const size_t F = (size_t)na * (size_t)nb, f = (size_t)xa + (size_t)na * (size_t)xb;
+  c_HI = E.cols[f];
+  c_HeI = E.cols[F + f];
+  c_HeII = E.cols[2 * F + f];
+}
 // Is the cell at offset (di, dj, dk) lit by source S?  Uniform branch on S.cut (a scalar register: the record is read through
 // the scalar cache), so a source with neither beam nor horizon costs a wave one scalar compare; the loss and per-cell kernels
 // ask this beside their in-box test.  (k_rates never asks: batches with such a source run k_rates_beam or k_rates_curve.)
@@ -336,11 +371,13 @@ k_transpose_packed(Grid g, const double *__restrict__ packed, double *__restrict
 // (Inside k_sweep_shell this work sat in a sixteenth of the waves, all of them on two of the eight XCDs: the
 // last shell of every round took twice as long as its neighbours.  Here every lane of every wave has a cell.)
 // OPEN: `box` is the round's box before it is cut at each source's reach; MOVABLE: the sum that decides (on_counted_face).
-template <bool OPEN, bool MOVABLE>
-__global__ void __launch_bounds__(BLOCK)
-k_loss(Grid g, const SrcDev *__restrict__ src, const int *__restrict__ list, int multi, int s_lo, int s_hi, Box box_,
-       StepScalars sc, const BandData *__restrict__ bd, SedSet ss,
-       const int *__restrict__ block_base, double *__restrict__ loss_partial, int pitch, int sample, int first_block) {
+// ENTRY (k_loss_entry, a batch with a source that has entry columns, c2r_set_source_face_entry): of such a source only the
+// surface cells that are mesh cells count -- what its vacuum surface "loses" is the upstream mesh's business.
+template <bool OPEN, bool MOVABLE, bool ENTRY>
+__device__ __forceinline__ void loss_block(const Grid &g, const SrcDev *__restrict__ src, const int *__restrict__ list, int multi, int s_lo,
+                                           int s_hi, const Box &box_, const StepScalars &sc, const BandData *__restrict__ bd,
+                                           const SedSet &ss, const int *__restrict__ block_base, double *__restrict__ loss_partial,
+                                           int pitch, int sample, int first_block, const SrcEntry *__restrict__ ent) {
   // first_block: the blocks before it hold no surface cell (the host has set their partials to zero and does not
   // launch them); block numbers, and with them the order of the sum, stay what they are
   __shared__ double sh[BLOCK / 64];
@@ -367,7 +404,12 @@ k_loss(Grid g, const SrcDev *__restrict__ src, const int *__restrict__ list, int
     else shell_decode(shell, (int)t, di, dj, dk);
     const bool inside = di >= box.lo[0] && di <= box.hi[0] && dj >= box.lo[1] && dj <= box.hi[1] && dk >= box.lo[2] &&
                         dk <= box.hi[2];
-    const bool boundary = on_counted_face<OPEN>(box, S, di, dj, dk, MOVABLE ? 1 : 0);
+    bool boundary = on_counted_face<OPEN>(box, S, di, dj, dk, MOVABLE ? 1 : 0);
+    if constexpr (ENTRY) {
+      if (ent[list[blockIdx.y]].on) // (uniform per block)
+        boundary = boundary && axis_in_mesh(mesh0<OPEN>(S.i0 - 1 + di, g.n1, S.wn[0]), g.n1) &&
+                   axis_in_mesh(mesh0<OPEN>(S.j0 - 1 + dj, g.n2, S.wn[1]), g.n2) && axis_in_mesh(mesh0<OPEN>(S.k0 - 1 + dk, g.n3, S.wn[2]), g.n3);
+    }
     // (an unlit cell of a beamed source loses nothing: its term is 0.0, as beyond max_coldensh)
     // (likewise a cell in a shell of factor 0 of a curved source; any other shell scales the source's fluxes)
     double cf;
@@ -401,6 +443,22 @@ k_loss(Grid g, const SrcDev *__restrict__ src, const int *__restrict__ list, int
   }
   const double bs = block_sum(loss, sh);
   if (threadIdx.x == 0) loss_partial[(size_t)blockIdx.y * pitch + bx] = bs;
+}
+template <bool OPEN, bool MOVABLE>
+__global__ void __launch_bounds__(BLOCK)
+k_loss(Grid g, const SrcDev *__restrict__ src, const int *__restrict__ list, int multi, int s_lo, int s_hi, Box box_,
+       StepScalars sc, const BandData *__restrict__ bd, SedSet ss,
+       const int *__restrict__ block_base, double *__restrict__ loss_partial, int pitch, int sample, int first_block) {
+  loss_block<OPEN, MOVABLE, false>(g, src, list, multi, s_lo, s_hi, box_, sc, bd, ss, block_base, loss_partial, pitch, sample, first_block,
+                                   nullptr);
+}
+// the kept loss of a batch that holds a source with entry columns (ent: one record per source of the batch, beside src)
+__global__ void __launch_bounds__(BLOCK)
+k_loss_entry(Grid g, const SrcDev *__restrict__ src, const int *__restrict__ list, int multi, int s_lo, int s_hi, Box box_,
+             StepScalars sc, const BandData *__restrict__ bd, SedSet ss,
+             const int *__restrict__ block_base, double *__restrict__ loss_partial, int pitch, int sample, int first_block,
+             const SrcEntry *__restrict__ ent) {
+  loss_block<true, false, true>(g, src, list, multi, s_lo, s_hi, box_, sc, bd, ss, block_base, loss_partial, pitch, sample, first_block, ent);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -507,8 +565,12 @@ __device__ __forceinline__ void sweep_cell_state(const SweepArgs &A, int i, int 
 // source is cut at a reach that runs through vacuum up to the source, so a cell of it may lie outside the mesh along an open
 // axis -- a VACUUM cell: neufrac * ndens is exactly 0.0 for the three species and there is no LLS fog, N_out = N_in +
 // 0 * path * abundance, and nothing is loaded from the state grids.  A mesh cell gets the arithmetic it always got.
-template <bool OPEN, bool EXT = false>
-__device__ __forceinline__ void sweep_cell(const SweepArgs &A, const SrcDev &S, int shell, int t) {
+// ENTRY (EXT kernels of a batch with a source that has entry columns, c2r_set_source_face_entry; E: its record): a vacuum cell
+// in the ghost layer of the entry's face stores the strip's columns as N_out instead of N_in (entry_columns) -- the one
+// change to the vacuum rule; every other vacuum cell stays vacuum, and nobody downstream of the ghost layer reads one.
+template <bool OPEN, bool EXT = false, bool ENTRY = false>
+__device__ __forceinline__ void sweep_cell(const SweepArgs &A, const SrcDev &S, int shell, int t, const SrcEntry *E = nullptr) {
+  static_assert(EXT || !ENTRY, "entry columns belong to a source outside the mesh");
   static_assert(OPEN || !EXT, "a source outside the mesh needs an open axis");
   const Grid &g = A.g;
   const StepScalars &sc = A.sc;
@@ -542,7 +604,9 @@ __device__ __forceinline__ void sweep_cell(const SweepArgs &A, const SrcDev &S, 
     path = 0.5 * sc.dr1;
   } else {
     ShortChar s4;
-    short_characteristic(S.i0, S.j0, S.k0, di, dj, dk, s4);
+    int ci0 = S.i0, cj0 = S.j0, ck0 = S.k0;
+    if constexpr (ENTRY) entry_cinterp_position(*E, ci0, cj0, ck0);
+    short_characteristic(ci0, cj0, ck0, di, dj, dk, s4);
     size_t qc[4];
 #pragma unroll
     for (int c = 0; c < 4; c++) {
@@ -569,9 +633,12 @@ __device__ __forceinline__ void sweep_cell(const SweepArgs &A, const SrcDev &S, 
     }
   }
   // coldens (doric.f90:358-372): neufrac * ndens * path * abundance, from the left
-  const double cout_HI = cin_HI + u_HI * path * (1.0 - abu_he);
-  const double cout_HeI = cin_HeI + u_HeI * path * abu_he;
-  const double cout_HeII = cin_HeII + u_HeII * path * abu_he;
+  double cout_HI = cin_HI + u_HI * path * (1.0 - abu_he);
+  double cout_HeI = cin_HeI + u_HeI * path * abu_he;
+  double cout_HeII = cin_HeII + u_HeII * path * abu_he;
+  if constexpr (ENTRY) {
+    if (E->on && !in_mesh) entry_columns(*E, g, i, j, k, cout_HI, cout_HeI, cout_HeII);
+  }
   store_columns(cs, p, cz, cin_HI, cin_HeI, cin_HeII, cout_HI, cout_HeI, cout_HeII);
 }
 
@@ -582,9 +649,10 @@ __device__ __forceinline__ void sweep_cell(const SweepArgs &A, const SrcDev &S, 
 // (corners of weight exactly 0 on the edges of a face are read from the nearest cell of shell s-1).  Bit for bit
 // the columns of sweep_cell (tests/test_gpu_parity.py::test_fast_sweep_equals_the_general_sweep runs that one for every
 // shell, C2R_SWEEP_GENERIC=1, in a process of its own and compares the columns).
-// EXT: as in sweep_cell.
-template <bool OPEN, bool EXT = false>
-__device__ __forceinline__ void sweep_cell_fast(const SweepArgs &A, const SrcDev &S, const ShellGeom &G, int t) {
+// EXT, ENTRY: as in sweep_cell.
+template <bool OPEN, bool EXT = false, bool ENTRY = false>
+__device__ __forceinline__ void sweep_cell_fast(const SweepArgs &A, const SrcDev &S, const ShellGeom &G, int t, const SrcEntry *E = nullptr) {
+  static_assert(EXT || !ENTRY, "entry columns belong to a source outside the mesh");
   static_assert(OPEN || !EXT, "a source outside the mesh needs an open axis");
   const Grid &g = A.g;
   const StepScalars &sc = A.sc;
@@ -607,7 +675,9 @@ __device__ __forceinline__ void sweep_cell_fast(const SweepArgs &A, const SrcDev
   double u_HI = 0.0, u_HeI = 0.0, u_HeII = 0.0;
   if (in_mesh) sweep_cell_state(A, i, j, k, face == 2, u_HI, u_HeI, u_HeII);
   ShellCorners c4;
-  if constexpr (OPEN) reach_short_characteristic(G, reach_shell(S.rl, S.rr, G.sp), S.rl, S.rr, face, S.i0, S.j0, S.k0, di, dj, dk, c4);
+  int ci0 = S.i0, cj0 = S.j0, ck0 = S.k0;
+  if constexpr (ENTRY) entry_cinterp_position(*E, ci0, cj0, ck0);
+  if constexpr (OPEN) reach_short_characteristic(G, reach_shell(S.rl, S.rr, G.sp), S.rl, S.rr, face, ci0, cj0, ck0, di, dj, dk, c4);
   else shell_short_characteristic(G, face, S.i0, S.j0, S.k0, di, dj, dk, c4);
   double cin_HI = interp_column_fast(c4.s, cs[col_out((size_t)c4.p[0], 0, cz)], cs[col_out((size_t)c4.p[1], 0, cz)],
                                      cs[col_out((size_t)c4.p[2], 0, cz)], cs[col_out((size_t)c4.p[3], 0, cz)], sigma_HI_at_ion_freq);
@@ -623,9 +693,12 @@ __device__ __forceinline__ void sweep_cell_fast(const SweepArgs &A, const SrcDev
     cin_HI = cin_HI + coldensh_LLS * path / sc.dr1;
   }
   // coldens (doric.f90:358-372): neufrac * ndens * path * abundance, from the left
-  const double cout_HI = cin_HI + u_HI * path * (1.0 - abu_he);
-  const double cout_HeI = cin_HeI + u_HeI * path * abu_he;
-  const double cout_HeII = cin_HeII + u_HeII * path * abu_he;
+  double cout_HI = cin_HI + u_HI * path * (1.0 - abu_he);
+  double cout_HeI = cin_HeI + u_HeI * path * abu_he;
+  double cout_HeII = cin_HeII + u_HeII * path * abu_he;
+  if constexpr (ENTRY) {
+    if (E->on && !in_mesh) entry_columns(*E, g, i, j, k, cout_HI, cout_HeI, cout_HeII);
+  }
   store_columns(cs, p, cz, cin_HI, cin_HeI, cin_HeII, cout_HI, cout_HeI, cout_HeII);
 }
 
@@ -700,6 +773,49 @@ k_sweep_shell_fast_ext(SweepArgs A, const SrcDev *__restrict__ src, const int *_
   const SrcDev &S = src[active[blockIdx.y]];
   const int t = sweep_block_cell_open(sweep_shell_cells<true>(S, G.s));
   if (t >= 0) sweep_cell_fast<true, true>(A, S, G, t);
+}
+
+// ... and of a batch that holds a source with entry columns (c2r_set_source_face_entry): the two above with the ghost layer of
+// sweep_cell's ENTRY.  ent: one record per source of the batch, beside src.  Launched for such a batch only.
+__global__ void __launch_bounds__(BLOCK, C2R_SWEEP_WAVES)
+k_sweep_shell_entry(SweepArgs A, const SrcDev *__restrict__ src, const int *__restrict__ active, int shell, const SrcEntry *__restrict__ ent) {
+  const int b = active[blockIdx.y];
+  const SrcDev &S = src[b];
+  const int t = sweep_block_cell_open(sweep_shell_cells<true>(S, shell));
+  if (t >= 0) sweep_cell<true, true, true>(A, S, shell, t, ent + b);
+}
+
+__global__ void __launch_bounds__(BLOCK, C2R_SWEEP_WAVES)
+k_sweep_shell_fast_entry(SweepArgs A, const SrcDev *__restrict__ src, const int *__restrict__ active, ShellGeom G,
+                         const SrcEntry *__restrict__ ent) {
+  const int b = active[blockIdx.y];
+  const SrcDev &S = src[b];
+  const int t = sweep_block_cell_open(sweep_shell_cells<true>(S, G.s));
+  if (t >= 0) sweep_cell_fast<true, true, true>(A, S, G, t, ent + b);
+}
+
+// Exit strips (c2r_select_source_face_exit): N_out of the cells in the layer of `face` from the shell-ordered blocks of the
+// selected sources of a batch whose final boxes are in their records, one thread per face cell (blockIdx.x) and source
+// (blockIdx.y).  pairs[2 y], pairs[2 y + 1]: the source's place in the batch and its strip among the face's strips (3 F
+// doubles each, species slowest).  A periodic lateral axis maps the mesh index to the image within the reach (axis_offset);
+// a layer cell outside the final box gets +0.0.
+__global__ void __launch_bounds__(BLOCK)
+k_source_face_exit(Grid g, const SrcDev *__restrict__ src, const int *__restrict__ pairs, int face, double *__restrict__ strips) {
+  const SrcDev &S = src[pairs[2 * blockIdx.y]];
+  const int axis = face >> 1, high = face & 1;
+  const int na = axis == 0 ? g.n2 : g.n1, nb = axis == 2 ? g.n2 : g.n3, nc = axis == 0 ? g.n1 : (axis == 1 ? g.n2 : g.n3);
+  const size_t F = (size_t)na * (size_t)nb, f = (size_t)blockIdx.x * BLOCK + threadIdx.x;
+  if (f >= F) return;
+  // the layer cell of face cell f: the lower of the two other axes fastest
+  const int xa = (int)(f % (size_t)na), xb = (int)(f / (size_t)na), xc = high ? nc - 1 : 0;
+  const int i = axis == 0 ? xc : xa, j = axis == 0 ? xa : (axis == 1 ? xc : xb), k = axis == 2 ? xc : xb;
+  const int di = axis_offset(i, S.i0, S.wn[0]), dj = axis_offset(j, S.j0, S.wn[1]), dk = axis_offset(k, S.k0, S.wn[2]);
+  const bool inside = di >= S.lo[0] && di <= S.hi[0] && dj >= S.lo[1] && dj <= S.hi[1] && dk >= S.lo[2] && dk <= S.hi[2];
+  // (only a cell of the box, which lies within the reach, has a position)
+  const size_t p = inside ? reach_position(S.rl, S.rr, di, dj, dk) : 0;
+  double *out = strips + (size_t)pairs[2 * blockIdx.y + 1] * 3 * F;
+  const global_double *cs = (const global_double *)S.cols;
+  for (int c = 0; c < 3; c++) out[(size_t)c * F + f] = inside ? cs[col_out(p, c, S.cz)] : 0.0;
 }
 
 // photon_loss_src_thread(tn) += ... (evolve_point.F90:312): sum the block partials of all shells of
@@ -1695,6 +1811,25 @@ struct c2r_ctx {
   // c2r_set_sources_external: the largest shell that a source OUTSIDE the mesh reaches, through the vacuum between it and
   // the far mesh faces (0: every source of the list stands inside).  The shell bookkeeping is made for it.
   int ext_smax = 0;
+  // Point-source hand-over between stacked meshes (c2ray_handover.inc).
+  // c2r_set_source_face_entry: per source (empty: no source has one) the face its entry columns come through (-1: none), the
+  // rounds it is traced for and its strip on the device; the records of a batch in flight, per scratch set.
+  struct FaceEntry {
+    int face = -1, rounds = 0;
+    double *d_cols = nullptr;
+  };
+  std::vector<FaceEntry> src_entry;
+  // c2r_set_mesh_origin: where this mesh lies in the deep mesh it is a part of (0: it is the deep mesh, or begins at its cell 1)
+  int origin[3] = {0, 0, 0};
+  SrcEntry *d_ent[2] = {nullptr, nullptr}, *h_ent[2] = {nullptr, nullptr};
+  // c2r_select_source_face_exit: per face the selected sources (1-based), their strips on the device (3 F doubles each), and
+  // per strip nbox of the pass that filled it last, whether its final box met the layer, and that pass's stamp (0: none yet)
+  struct FaceExit {
+    std::vector<int> sources, rounds, reached;
+    std::vector<long long> stamp;
+    double *d_cols = nullptr;
+  };
+  FaceExit face_exit[6];
   // -DPL / -DQUASARS: power-law (0) and quasar-like (1) SEDs
   double *d_sed_tab[2][4] = {{nullptr, nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr, nullptr}};
   int sed_lo[2] = {0, 0}, sed_hi[2] = {0, 0}; // 0-based [lo, hi)
@@ -2123,7 +2258,9 @@ static void shell_bookkeeping(c2r_ctx *c) {
   c->shell_geom.clear();
   for (int s = 0; s <= g.smax; s++) c->shell_geom.push_back(shell_geometry(s));
   // active lists of all rounds of a batch, one after another (two per round at most, plus the final losses)
-  c->list_cap = (size_t)(2 * (g.smax / SUBBOXSIZE + 2) + 4) * BATCH_MAX;
+  // (per round: the active list, the undecided, and the probed ones where a source with entry columns is left out; behind
+  // the rounds, the kept losses' lists and the pairs of the exit strips of up to six faces, c2ray_handover.inc)
+  c->list_cap = (size_t)(3 * (g.smax / SUBBOXSIZE + 2) + 4 + 12) * BATCH_MAX;
 }
 
 extern "C" int c2r_create(c2r_ctx **out, int device, const int mesh[3]) {
@@ -2300,6 +2437,14 @@ extern "C" void c2r_destroy(c2r_ctx *c) {
   for (auto &list : c->segs)
     for (auto &sg : list)
       if (sg.p) (void)hipFree(sg.p);
+  for (c2r_ctx::FaceEntry &e : c->src_entry)
+    if (e.d_cols) (void)hipFree(e.d_cols);
+  for (c2r_ctx::FaceExit &x : c->face_exit)
+    if (x.d_cols) (void)hipFree(x.d_cols);
+  for (int k = 0; k < 2; k++) {
+    if (c->d_ent[k]) (void)hipFree(c->d_ent[k]);
+    if (c->h_ent[k]) (void)hipHostFree(c->h_ent[k]);
+  }
   if (c->h_loss) (void)hipHostFree(c->h_loss);
   if (c->h_probe) (void)hipHostFree(c->h_probe);
   if (c->h_tail) (void)hipHostFree(c->h_tail);
@@ -2549,6 +2694,24 @@ static void forget_horizon_loss(c2r_ctx *c) {
   c->rim_last_stamp = 0;
 }
 
+// Point-source hand-over (c2ray_handover.inc): a new source list drops the entry columns and the exit selections, as it drops
+// the beams.  The strips are read by launches of the sweep stream only.
+static int forget_source_handover(c2r_ctx *c) {
+  bool any = !c->src_entry.empty();
+  for (const c2r_ctx::FaceExit &x : c->face_exit) any = any || !x.sources.empty();
+  if (!any) return 0;
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  for (c2r_ctx::FaceEntry &e : c->src_entry)
+    if (e.d_cols) HIPCHK(c, hipFree(e.d_cols));
+  c->src_entry.clear();
+  for (c2r_ctx::FaceExit &x : c->face_exit) {
+    if (x.d_cols) HIPCHK(c, hipFree(x.d_cols));
+    x = c2r_ctx::FaceExit();
+  }
+  return 0;
+}
+
 // Sources outside the mesh (c2r_set_sources_external).  Does the position p stand outside along axis d?
 static bool position_is_external(const Grid &g, const int *p, int d) {
   const int mesh[3] = {g.n1, g.n2, g.n3};
@@ -2706,7 +2869,7 @@ static int set_sources_one(c2r_ctx *c, int nsrc, const int *srcpos, const double
   c->horizon_r2.clear();
   c->curves.clear();
   forget_horizon_loss(c);
-  return 0;
+  return forget_source_handover(c);
 }
 
 static int set_sed_tables_one(c2r_ctx *c, int sed, const double *photo_thick, const double *photo_thin,
@@ -3306,6 +3469,8 @@ struct SrcRun {
   Reach reach{};          // how far its box can go: the mesh's with periodic boundaries, its own with open ones
   int smax = 0;           // the largest shell within that reach
   long long sweep_threads = 0; // threads of the shell launches spent on it (c2r_get_source_trace)
+  int entry_rounds = 0;   // > 0: the source has entry columns (c2r_set_source_face_entry) and is traced for that many rounds
+                          // (fewer where its box cannot grow any more): no loss decides for it, and no probe looks at it
 };
 
 // the sub-box after `nbox` rounds (evolve_source.F90:141-144)
@@ -3363,7 +3528,8 @@ static int blocks_before_surface(const c2r_ctx *c, const Box &box, int s_lo, int
 // Open boundaries: `box` is the round's box before it is cut at each source's reach; deciding: the sum over the faces that
 // can still move (the while-test), else the sum over the whole surface (the loss that is kept).
 static int boundary_loss(c2r_ctx *c, int set, size_t list_off, int n, int s_lo, int s_hi, const Box &box,
-                         const StepScalars &sc, const SedSet &ss, bool multi, bool deciding) {
+                         const StepScalars &sc, const SedSet &ss, bool multi, bool deciding, const SrcEntry *ent = nullptr) {
+  // ent: the kept loss of a batch that holds a source with entry columns (k_loss_entry; its records, one per source)
   const int nblk = c->block_base[s_hi + 1] - c->block_base[s_lo];
   const size_t need = (size_t)nblk * n;
   if (c->loss_partial_cap < need) {
@@ -3378,7 +3544,10 @@ static int boundary_loss(c2r_ctx *c, int set, size_t list_off, int n, int s_lo, 
                        multi ? 1 : 0, s_lo, s_hi, box, sc, c->d_bands, ss, c->d_block_base, c->d_loss_partial, nblk,
                        1, first_block);
   };
-  if (c->periodic) go(k_loss<false, false>);
+  if (ent)
+    hipLaunchKernelGGL(k_loss_entry, dim3(nblk - first_block, n), dim3(BLOCK), 0, c->stream, c->g, c->d_src[set], c->d_list[set] + list_off,
+                       multi ? 1 : 0, s_lo, s_hi, box, sc, c->d_bands, ss, c->d_block_base, c->d_loss_partial, nblk, 1, first_block, ent);
+  else if (c->periodic) go(k_loss<false, false>);
   else if (deciding) go(k_loss<true, true>);
   else go(k_loss<true, false>);
   hipLaunchKernelGGL(k_loss_finish, dim3(n), dim3(BLOCK), 0, c->stream, c->d_loss_partial, nblk, nblk, c->d_loss_acc);
@@ -3437,6 +3606,9 @@ struct Batch {
   bool curved = false;              // some source of the batch has a curve: its rates launch is k_rates_curve
   bool external = false;            // some source of the batch stands outside the mesh: its shells are k_sweep_shell(_fast)_ext's,
                                     // and its kept losses are k_loss's (queue_kept_losses)
+  bool entry = false;               // some source of the batch has entry columns (c2r_set_source_face_entry), or the mesh has an
+                                    // origin (c2r_set_mesh_origin): the shells are
+                                    // k_sweep_shell(_fast)_entry's, the kept losses k_loss_entry's; d_ent[set] holds the records
   std::vector<int> rim_ns;          // horizon loss: the sources (1-based) whose sums queue_horizon_rim has queued, in row order
 };
 
@@ -3563,6 +3735,7 @@ static int place_batch(const PassCtx &P, const std::vector<int> &mine, Batch &B)
   B.beamed = false;
   B.curved = false;
   B.external = false;
+  B.entry = false;
   for (bool released = false;;) {
     c->seg_cur[set] = 0;
     c->seg_used[set] = 0;
@@ -3630,7 +3803,16 @@ static int place_batch(const PassCtx &P, const std::vector<int> &mine, Batch &B)
     B.beamed = B.beamed || S.cut != CUT_NONE;
     B.curved = B.curved || (S.cut & CUT_CURVE) != 0;
     B.external = B.external || (c->ext_smax > 0 && source_is_external(c, r.ns));
+    const bool placed_in_deep = c->origin[0] != 0 || c->origin[1] != 0 || c->origin[2] != 0;
+    if (placed_in_deep || !c->src_entry.empty()) { // (either exists: the pinned records do too)
+      const c2r_ctx::FaceEntry e = c->src_entry.empty() ? c2r_ctx::FaceEntry() : c->src_entry[(size_t)r.ns - 1];
+      c->h_ent[set][b] = SrcEntry{e.face >= 0 ? 1 + e.face : 0, e.d_cols, {c->origin[0], c->origin[1], c->origin[2]}};
+      r.entry_rounds = e.face >= 0 ? e.rounds : 0;
+      // (a mesh with an origin: every batch through the kernels that move cinterp's coordinates, entry or not)
+      B.entry = B.entry || e.face >= 0 || placed_in_deep;
+    }
   }
+  if (B.entry) HIPCHK(c, hipMemcpyAsync(c->d_ent[set], c->h_ent[set], sizeof(SrcEntry) * B.nb, hipMemcpyHostToDevice, c->stream));
   // coldensh_out = 0 for every new source (evolve_source.F90:94-95) serves two purposes in the
   // reference: the "already done" marker (replaced here by the shell order: every cell is visited
   // once) and finite values for corners whose interpolation weight is exactly 0.  The arena is
@@ -3681,7 +3863,7 @@ static int settle_rounds(const PassCtx &P, Batch &B) {
 // every source still active reached at least round `round` in the previous pass
 static bool all_reached(const c2r_ctx *c, const Batch &B, int round) {
   for (const SrcRun &r : B.run)
-    if (r.active && c->prev_nbox[(size_t)r.ns - 1] < round) return false;
+    if (r.active && r.entry_rounds == 0 && c->prev_nbox[(size_t)r.ns - 1] < round) return false; // (entry columns: its rounds are given)
   return true;
 }
 
@@ -3772,6 +3954,9 @@ static int launch_shells(PassCtx &P, Batch &B, const Box &box, int s_lo, int s_h
     if (fast && c->periodic)
       hipLaunchKernelGGL(k_sweep_shell_fast<false>, dim3(nlaunch, nact), dim3(BLOCK), 0, c->stream, SA, c->d_src[B.set],
                          c->d_list[B.set] + act_off, c->shell_geom[(size_t)s]);
+    else if (fast && B.entry) // (a source with entry columns in the batch: the kernels that know vacuum cells and the ghost layer)
+      hipLaunchKernelGGL(k_sweep_shell_fast_entry, dim3(nlaunch, nact), dim3(BLOCK), 0, c->stream, SA, c->d_src[B.set],
+                         c->d_list[B.set] + act_off, c->shell_geom[(size_t)s], c->d_ent[B.set]);
     else if (fast && B.external) // (a source outside the mesh in the batch: the kernels that know vacuum cells)
       hipLaunchKernelGGL(k_sweep_shell_fast_ext, dim3(nlaunch, nact), dim3(BLOCK), 0, c->stream, SA, c->d_src[B.set],
                          c->d_list[B.set] + act_off, c->shell_geom[(size_t)s]);
@@ -3780,6 +3965,9 @@ static int launch_shells(PassCtx &P, Batch &B, const Box &box, int s_lo, int s_h
                          c->d_list[B.set] + act_off, c->shell_geom[(size_t)s]);
     else if (c->periodic)
       hipLaunchKernelGGL(k_sweep_shell<false>, dim3(nlaunch, nact), dim3(BLOCK), 0, c->stream, SA, c->d_src[B.set], c->d_list[B.set] + act_off, s);
+    else if (B.entry)
+      hipLaunchKernelGGL(k_sweep_shell_entry, dim3(nlaunch, nact), dim3(BLOCK), 0, c->stream, SA, c->d_src[B.set], c->d_list[B.set] + act_off, s,
+                         c->d_ent[B.set]);
     else if (B.external)
       hipLaunchKernelGGL(k_sweep_shell_ext, dim3(nlaunch, nact), dim3(BLOCK), 0, c->stream, SA, c->d_src[B.set], c->d_list[B.set] + act_off, s);
     else
@@ -3829,7 +4017,9 @@ static int sweep_batch(PassCtx &P, Batch &B) {
     for (int b = 0; b < B.nb; b++) {
       SrcRun &r = B.run[b];
       if (!r.active) continue;
-      if (!can_grow(c, r.reach, round_box(r.reach, r.nbox)) || !(ahead || r.loss > C2R_F(1e-10) * r.total_flux)) {
+      // (entry columns: exactly the rounds given, as far as the box can grow; r.loss stays the flux, no probe ever writes it)
+      if (!can_grow(c, r.reach, round_box(r.reach, r.nbox)) || (r.entry_rounds > 0 && r.nbox >= r.entry_rounds) ||
+          !(ahead || r.loss > C2R_F(1e-10) * r.total_flux)) {
         r.active = false;
         continue;
       }
@@ -3866,8 +4056,10 @@ static int sweep_batch(PassCtx &P, Batch &B) {
     for (int a = 0; a < nact; a++) {
       SrcRun &r = B.run[hl[act_off + a]];
       r.smax_prev = std::min(s_hi, r.smax);
-      any_can_grow = any_can_grow || can_grow(c, r.reach, round_box(r.reach, round));
-      any_can_grow_twice = any_can_grow_twice || can_grow(c, r.reach, round_box(r.reach, round + 1));
+      // (a source with entry columns goes on while it has rounds left)
+      const bool more = r.entry_rounds == 0 || round < r.entry_rounds, more2 = r.entry_rounds == 0 || round + 1 < r.entry_rounds;
+      any_can_grow = any_can_grow || (more && can_grow(c, r.reach, round_box(r.reach, round)));
+      any_can_grow_twice = any_can_grow_twice || (more2 && can_grow(c, r.reach, round_box(r.reach, round + 1)));
     }
     if (!any_can_grow) {
       // The while-test after this round fails whatever the loss: the round is every active source's last, and
@@ -3885,7 +4077,20 @@ static int sweep_batch(PassCtx &P, Batch &B) {
     // The loss of this round decides whether a source goes on.
     RoundRec R;
     R.round = round; R.nact = nact; R.s_lo = s_lo; R.s_hi = s_hi; R.off = act_off; R.acc_off = acc_used; R.box = box;
-    acc_used += (size_t)nact;
+    if (B.entry) {
+      // no loss decides for a source with entry columns, and no probe is launched for it: the round's record lists the others
+      int *pl = hl + B.list_used, np = 0;
+      for (int a = 0; a < nact; a++)
+        if (B.run[hl[act_off + a]].entry_rounds == 0) pl[np++] = hl[act_off + a];
+      if (np == 0) continue; // (nobody to decide about)
+      if (np < nact) {
+        HIPCHK(c, hipMemcpyAsync(c->d_list[B.set] + B.list_used, pl, sizeof(int) * np, hipMemcpyHostToDevice, c->stream));
+        R.off = B.list_used;
+        R.nact = np;
+        B.list_used += (size_t)np;
+      }
+    }
+    acc_used += (size_t)R.nact;
     B.recs.push_back(R);
     // Its probe goes out now if the next round needs the answer before it can start (somebody may stop here) or if
     // the next round is the last for geometric reasons (the probes then run beside its shells, and the answers
@@ -3964,6 +4169,60 @@ static int queue_horizon_rim(const PassCtx &P, Batch &B) {
   return 0;
 }
 
+// Exit strips (c2r_select_source_face_exit).  Does the batch hold a selected source?
+static bool batch_has_face_exit(const c2r_ctx *c, const Batch &B) {
+  for (const c2r_ctx::FaceExit &x : c->face_exit)
+    for (int ns : x.sources)
+      for (const SrcRun &r : B.run)
+        if (r.ns == ns) return true;
+  return false;
+}
+// The strips of the batch's selected sources, face by face: one gather launch per face (k_source_face_exit) on the sweep
+// stream, behind the upload of the records with the final boxes; and what the host knows of each strip -- the rounds, whether
+// the final box met the layer, the pass.
+static int queue_source_face_exit(const PassCtx &P, Batch &B) {
+  c2r_ctx *c = P.c;
+  const int mesh[3] = {c->g.n1, c->g.n2, c->g.n3};
+  for (int face = 0; face < 6; face++) {
+    c2r_ctx::FaceExit &x = c->face_exit[face];
+    if (x.sources.empty()) continue;
+    const int axis = face >> 1, high = face & 1;
+    int *pairs = c->h_list[B.set] + B.list_used, np = 0;
+    for (size_t k = 0; k < x.sources.size(); k++)
+      for (int b = 0; b < B.nb; b++) {
+        const SrcRun &r = B.run[b];
+        if (r.ns != x.sources[k]) continue;
+        pairs[2 * np] = b;
+        pairs[2 * np + 1] = (int)k;
+        np++;
+        // does the final box hold a cell of the layer?  Along the face's axis the layer's offset; across it any mesh cell
+        const Box fb = round_box(r.reach, r.nbox);
+        const int *p = &c->srcpos[3 * (size_t)(r.ns - 1)];
+        bool met = r.nbox > 0;
+        for (int d = 0; d < 3 && met; d++) {
+          if (d == axis) {
+            const int off = (high ? mesh[d] : 1) - p[d];
+            met = off >= fb.lo[d] && off <= fb.hi[d];
+          } else if (!c->per[d]) {
+            met = std::max(fb.lo[d], 1 - p[d]) <= std::min(fb.hi[d], mesh[d] - p[d]);
+          }
+        }
+        x.rounds[k] = r.nbox;
+        x.reached[k] = met ? 1 : 0;
+        x.stamp[k] = P.stamp;
+      }
+    if (np == 0) continue;
+    HIPCHK(c, hipMemcpyAsync(c->d_list[B.set] + B.list_used, pairs, sizeof(int) * 2 * np, hipMemcpyHostToDevice, c->stream));
+    const size_t F = (size_t)c->g.ncell / (size_t)mesh[axis];
+    hipLaunchKernelGGL(k_source_face_exit, dim3((unsigned)((F + BLOCK - 1) / BLOCK), (unsigned)np), dim3(BLOCK), 0, c->stream, c->g,
+                       c->d_src[B.set], c->d_list[B.set] + B.list_used, face, x.d_cols);
+    HIPCHK(c, hipGetLastError());
+    c->tm.sweep_launches++;
+    B.list_used += (size_t)(2 * np);
+  }
+  return 0;
+}
+
 // Final sub-boxes for the rates launch, what the next pass learns from this one (prev_nbox, prev_grow), the upload of the
 // SrcDev entries; then the rates stream takes the batch over.
 static int close_boxes(PassCtx &P, Batch &B) {
@@ -4012,7 +4271,10 @@ static int close_boxes(PassCtx &P, Batch &B) {
   if (c->rim_on)
     for (int b = 0; b < B.nb && !rim; b++) rim = (c->h_src[B.set][b].cut & CUT_HORIZON) && B.run[b].nbox > 0;
   const bool maps = c->d_face_maps != nullptr;
-  if (maps || rim) {
+  // Exit strips (c2r_select_source_face_exit): likewise, for the selected sources of the batch -- after their last round, with
+  // the final boxes in the records, before the column blocks are given back.
+  const bool exits = batch_has_face_exit(c, B);
+  if (maps || rim || exits) {
     if (c->timing && !B.sweep_started) {
       HIPCHK(c, hipEventRecord(B.ev[0], c->stream));
       B.sweep_started = true;
@@ -4020,12 +4282,13 @@ static int close_boxes(PassCtx &P, Batch &B) {
     HIPCHK(c, hipMemcpyAsync(c->d_src[B.set], c->h_src[B.set], sizeof(SrcDev) * B.nb, hipMemcpyHostToDevice, c->stream));
     if (maps && queue_face_loss(P, B)) return 1;
     if (rim && queue_horizon_rim(P, B)) return 1;
+    if (exits && queue_source_face_exit(P, B)) return 1;
   }
   if (c->timing) { // the sweep's span: from the first shell launch to the last, record uploads on either side left out
     if (!B.sweep_started) HIPCHK(c, hipEventRecord(B.ev[0], c->stream));
     HIPCHK(c, hipEventRecord(B.ev[1], c->stream));
   }
-  if (!maps && !rim) HIPCHK(c, hipMemcpyAsync(c->d_src[B.set], c->h_src[B.set], sizeof(SrcDev) * B.nb, hipMemcpyHostToDevice, c->stream));
+  if (!maps && !rim && !exits) HIPCHK(c, hipMemcpyAsync(c->d_src[B.set], c->h_src[B.set], sizeof(SrcDev) * B.nb, hipMemcpyHostToDevice, c->stream));
   if (!P.transposed_seen) {
     // small boxes only: nobody needed the copies, but whatever follows this sweep (the global pass rewrites the
     // state) has to come after the kernel that reads it
@@ -4269,7 +4532,7 @@ static int queue_kept_losses(const PassCtx &P, Batch &B) {
       nslot += nf;
     } else {
       HIPCHK(c, hipMemcpyAsync(c->d_list[set] + B.list_used, fl, sizeof(int) * nf, hipMemcpyHostToDevice, c->stream));
-      if (boundary_loss(c, set, B.list_used, nf, f_lo, f_hi, fb, P.sc, P.ss, P.multi, false)) return 1;
+      if (boundary_loss(c, set, B.list_used, nf, f_lo, f_hi, fb, P.sc, P.ss, P.multi, false, B.entry ? c->d_ent[set] : nullptr)) return 1;
       for (int j = 0; j < nf; j++) bt.loss[(size_t)fl[j]] = c->h_loss[j];
     }
     B.list_used += (size_t)nf;
@@ -5112,6 +5375,8 @@ extern "C" int c2r_set_sources_external(c2r_ctx *c, int nsrc, const int *srcpos,
   return for_replicas(c, [&](c2r_ctx *r) { return set_sources_one(r, nsrc, srcpos, normflux, s_star, true); });
 }
 
+#include "c2ray_handover.inc" // exit strips and entry columns of point sources: the c2r_*source_face* entry points
+
 // ---------------------------------------------------------------------------------------------
 // escape maps
 static int enable_face_loss_one(c2r_ctx *c, int on) {
@@ -5387,6 +5652,13 @@ static int set_boundaries_one(c2r_ctx *c, const int periodic[3]) {
         return fail(c, "c2r_set_boundaries: source %d at (%d,%d,%d) stands outside the mesh along axis %d, which has to stay open "
                     "(replace the source list first)", s + 1, c->srcpos[3 * (size_t)s], c->srcpos[3 * (size_t)s + 1],
                     c->srcpos[3 * (size_t)s + 2], d);
+  for (int d = 0; d < 3; d++)
+    if (per[d] && c->origin[d] != 0)
+      return fail(c, "c2r_set_boundaries: the mesh has an origin along axis %d (c2r_set_mesh_origin), which has to stay open", d);
+  for (int f = 0; f < 6; f++)
+    if (per[f >> 1] && !c->face_exit[f].sources.empty())
+      return fail(c, "c2r_set_boundaries: exit strips are selected through face %d of axis %d, which has to stay open (free them with "
+                  "c2r_select_source_face_exit(ctx, %d, 0, NULL) first)", f, f >> 1, f);
   if (per[0] == c->per[0] && per[1] == c->per[1] && per[2] == c->per[2]) return 0;
   const bool want = per[0] && per[1] && per[2];
   HIPCHK(c, hipSetDevice(c->device));

@@ -381,6 +381,57 @@ class HipEngine:
         > mesh) along axes that are open (set_boundaries); its box runs through vacuum up to the mesh."""
         self.set_sources(src, external=True)
 
+    # -- point-source hand-over between meshes stacked along an open axis (include/c2ray_hip.h) ------------------------------
+    def _source_face_cells(self, face):
+        if not 0 <= int(face) <= 5:
+            raise C2RayHipError(f"face {face} not in 0..5")
+        return self.ncell // self.mesh[int(face) >> 1]
+
+    def select_source_face_exit(self, face, sources=()):
+        """c2r_select_source_face_exit: keep, in every pass that sweeps them, the exit strips through `face` (2 * axis + high)
+        of the point sources `sources` (1-based); none frees the face's strips.  set_sources drops the selection."""
+        s = np.ascontiguousarray(sources, dtype=np.int32).reshape(-1)
+        self._chk(self.lib.c2r_select_source_face_exit(self.h, int(face), int(s.size), s.ctypes.data_as(C.POINTER(C.c_int))))
+
+    def download_source_face_exit(self, face, ns):
+        """c2r_download_source_face_exit: (strip, rounds, reached) of source ns from the last pass that swept it -- N_out of the
+        cells in the layer of `face` as (3, face cells), species slowest, the lower of the two other axes fastest, +0.0 outside the
+        final box; nbox of that pass; whether the final box held a cell of the layer."""
+        out = np.empty((3, self._source_face_cells(face)))
+        rounds, reached = C.c_int(0), C.c_int(0)
+        self._chk(self.lib.c2r_download_source_face_exit(self.h, int(face), int(ns), _dp(out), C.byref(rounds), C.byref(reached)))
+        return out, rounds.value, bool(reached.value)
+
+    def set_source_face_entry(self, ns, face=0, cols3=None, rounds=0):
+        """c2r_set_source_face_entry: source ns (1-based), which stands outside the mesh beyond `face` only, sees the columns
+        cols3 -- the exit strip of the mesh next door -- in the ghost layer of that face and is traced for exactly `rounds`
+        rounds.  cols3 = None clears the entry.  set_sources clears every entry."""
+        a = None
+        if cols3 is not None:
+            a = _f64(cols3).reshape(-1)
+            if a.size != 3 * self._source_face_cells(face):
+                raise ValueError(f"set_source_face_entry: {a.size} values, expected 3 x {self._source_face_cells(face)}")
+        self._chk(self.lib.c2r_set_source_face_entry(self.h, int(ns), int(face), _dp(a), int(rounds)))
+
+    def set_mesh_origin(self, origin=(0, 0, 0)):
+        """c2r_set_mesh_origin: this mesh is a part of a deep mesh, whose index along each axis is this mesh's index + origin.
+        cinterp then forms its crossing points from the deep mesh's coordinates, and the part has the deep mesh's bits wherever
+        it lies.  Non-zero along open axes only; kept across source lists."""
+        o = (C.c_int * 3)(*[int(v) for v in origin])
+        self._chk(self.lib.c2r_set_mesh_origin(self.h, o))
+
+    @property
+    def mesh_origin(self):
+        o = (C.c_int * 3)()
+        self._chk(self.lib.c2r_get_mesh_origin(self.h, o))
+        return tuple(int(v) for v in o)
+
+    def source_face_entry(self, ns):
+        """c2r_get_source_face_entry: (face, rounds) of source ns; face = -1 while no entry is set."""
+        face, rounds = C.c_int(0), C.c_int(0)
+        self._chk(self.lib.c2r_get_source_face_entry(self.h, int(ns), C.byref(face), C.byref(rounds)))
+        return face.value, rounds.value
+
     def set_source_beams(self, beams=None):
         """c2r_set_source_beams: one beam per point source, in source order -- None (no beam), a dict or a tuple
         (kind, axis, cos_half) with kind 0 / "none", 1 / "cone" or 2 / "bicone", axis three numbers (any length), cos_half the

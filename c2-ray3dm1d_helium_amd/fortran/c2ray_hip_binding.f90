@@ -199,6 +199,59 @@ module c2ray_hip
        real(c_double), value :: s_star
      end function c2r_set_sources_external
 
+     !> point-source hand-over between meshes stacked along an open axis; face = 2 * axis + high.
+     !> Keep the exit strips through `face` of the sources sources(1:nsel) (1-based); nsel = 0 frees them
+     integer(c_int) function c2r_select_source_face_exit(ctx, face, nsel, sources) &
+          bind(C, name="c2r_select_source_face_exit")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: ctx
+       integer(c_int), value :: face, nsel
+       integer(c_int), intent(in) :: sources(*)
+     end function c2r_select_source_face_exit
+
+     !> the strip of source ns (3 x face cells, species slowest), nbox of the pass that filled it, and whether its
+     !> final box held a cell of the face's layer
+     integer(c_int) function c2r_download_source_face_exit(ctx, face, ns, cols3, rounds, reached) &
+          bind(C, name="c2r_download_source_face_exit")
+       import :: c_int, c_ptr, c_double
+       type(c_ptr), value :: ctx
+       integer(c_int), value :: face, ns
+       real(c_double), intent(out) :: cols3(*)
+       integer(c_int), intent(out) :: rounds, reached
+     end function c2r_download_source_face_exit
+
+     !> entry columns of source ns, which stands beyond `face` only: cols3 = c_loc of the upstream strip, or
+     !> c_null_ptr to clear the entry; the source is traced for exactly `rounds` rounds
+     integer(c_int) function c2r_set_source_face_entry(ctx, ns, face, cols3, rounds) &
+          bind(C, name="c2r_set_source_face_entry")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: ctx, cols3
+       integer(c_int), value :: ns, face, rounds
+     end function c2r_set_source_face_entry
+
+     !> face = -1 while source ns has no entry
+     integer(c_int) function c2r_get_source_face_entry(ctx, ns, face, rounds) &
+          bind(C, name="c2r_get_source_face_entry")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: ctx
+       integer(c_int), value :: ns
+       integer(c_int), intent(out) :: face, rounds
+     end function c2r_get_source_face_entry
+
+     !> this mesh's index + origin = the deep mesh's index, per axis: cinterp then forms its crossing points from
+     !> the deep mesh's coordinates (non-zero along open axes only)
+     integer(c_int) function c2r_set_mesh_origin(ctx, origin) bind(C, name="c2r_set_mesh_origin")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: ctx
+       integer(c_int), intent(in) :: origin(3)
+     end function c2r_set_mesh_origin
+
+     integer(c_int) function c2r_get_mesh_origin(ctx, origin) bind(C, name="c2r_get_mesh_origin")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: ctx
+       integer(c_int), intent(out) :: origin(3)
+     end function c2r_get_mesh_origin
+
      integer(c_int) function c2r_set_sed_tables(ctx, sed, photo_thick, photo_thin, heat_thick, heat_thin, &
           lower, upper) bind(C, name="c2r_set_sed_tables")
        import :: c_int, c_ptr, c_double

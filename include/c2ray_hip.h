@@ -135,6 +135,76 @@ int c2r_set_sources(c2r_ctx *ctx, int nsrc, const int *srcpos, const double *nor
  * c2r_enable_horizon_loss (and this call while either is on), and for such a source c2r_evolve0d and c2r_do_source. */
 int c2r_set_sources_external(c2r_ctx *ctx, int nsrc, const int *srcpos, const double *normflux, double s_star);
 
+/* Point-source HAND-OVER between meshes stacked along one open axis: a quasar or galaxy in the slab next door of a
+ * light-cone strip.  The mesh that holds (or is nearer to) the source writes out the columns at its face, the next mesh takes
+ * them in as a ghost layer and reproduces its part of one deep mesh.  (Planes have the same pair: c2r_download_plane_exit_columns
+ * -> c2r_set_plane_entry_columns.)  The reference has nothing of the kind.
+ *   Notation.  face = 2 * axis + high, as for the escape maps.  A face has F cells, in the order of
+ * c2r_set_plane_entry_columns (the lower of the two remaining axes fastest); a STRIP is 3 F doubles, the species (HI, HeI, HeII)
+ * slowest.  The LAYER of a face: the mesh cells with index 1 (high = 0) or mesh[axis] (high = 1) along the axis; its GHOST
+ * LAYER: the cells one step outside, index 0 or mesh[axis] + 1.
+ *
+ * EXIT.  c2r_select_source_face_exit names the point sources (1-based) whose exit strip through `face` is kept: 3 F nsel
+ * doubles per device; nsel = 0 frees everything of that face.  Every pass that sweeps a selected source -- c2r_pass_sources
+ * and its slab-wise form, c2r_pass_allreduce_chemistry, c2r_iteration, c2r_evolve3d (its last iteration's pass), c2r_do_source
+ * for a source inside the mesh -- fills the strip after the source's last round, before its column block is given back: N_out
+ * of each layer cell (one more launch per face, k_source_face_exit; a periodic lateral axis maps the mesh index to the image
+ * within the reach), +0.0 for a layer cell outside the source's final box.  It works for a source inside the mesh and for one
+ * outside, with or without entry columns, so that a chain A -> B -> C passes the columns on.  Refused, with a message: a
+ * face of a periodic axis, a face outside 0..5, a source number outside 1..NumSrc, a source named twice, a call between
+ * c2r_pass_sources_begin and _end.  c2r_set_sources* drops the selection, as it drops beams; c2r_set_boundaries(_axes) refuses
+ * to make the axis periodic while a selection exists.
+ *   c2r_download_source_face_exit returns the strip, nbox of that pass for ns (rounds) and reached = 1 iff the final box held
+ * at least one cell of the layer.  Refused before any pass swept ns with the selection in place, and while a slab-wise pass
+ * is open; a multi-device context answers from the device that swept ns.
+ *
+ * ENTRY.  c2r_set_source_face_entry gives source ns, which must stand outside the mesh beyond `face` along that axis only
+ * (its other two coordinates inside the mesh; a neighbour across an edge or a corner is refused), the strip cols3 of the mesh
+ * upstream and the rounds that mesh traced; cols3 = NULL clears the entry.
+ *   Ghost layer: the vacuum rule of c2r_set_sources_external changes in one place for this source -- a cell of its box in the
+ * ghost layer of `face` stores N_out = cols3[species][face cell] instead of N_in.  Every other vacuum cell stays vacuum
+ * (nobody downstream of the ghost layer reads one: every upstream corner of a mesh cell lies in the mesh or in the ghost
+ * layer); no LLS fog is added in the ghost layer (the upstream mesh added its own); mesh cells get the arithmetic they always
+ * got.
+ *   Rounds: the source is traced for exactly `rounds` rounds (>= 1; fewer where no face of its reach can move any more).  No
+ * deciding loss is formed for it and no probe is launched for it: the mesh that holds the source decides how far it is traced,
+ * every mesh downstream covers the same cube cut at its own reach, so every ghost cell that is read was inside the upstream
+ * box.  (A mesh upstream whose box ended at its own reach has decided nothing -- its trace says so, box == reach --: the host
+ * then hands down at least the rounds the mesh downstream needs to run to its reach.)  sum_nbox counts the rounds traced.
+ *   Kept loss: photon_loss(1) receives, for such a source, only the terms of the surface cells of the final box that are mesh
+ * cells; what the vacuum surface "loses" is the upstream mesh's business.  (Upstream, the mesh's own photon_loss(1) still
+ * counts what crosses the interface: the combined budget of a stack is not closed.)
+ *   Kernels: a batch that holds a source with an entry runs k_sweep_shell_entry, k_sweep_shell_fast_entry and k_loss_entry;
+ * every other batch launches what it always launched, with the same bits.
+ *   Identities.  ZERO STRIP: an all-zero strip with `rounds` equal to the rounds the source takes without an entry gives the
+ * rate grids of the run without an entry, bit for bit (vacuum columns are exactly 0).  HAND-OVER: let W be one mesh open along
+ * the axis, A and B its two parts, the source in A, both traced as far as W traces it; with A's exit strip and W's rounds B has
+ * W's incoming and outgoing columns and rate grids on its cells bit for bit where B keeps W's absolute indices (B begins at W's
+ * index 1: the source beyond B's HIGH face), and to rounding where B's indices are shifted: cinterp forms its crossing points
+ * from absolute coordinates.  The shift matters in the cells that lie on a face of their shell across another axis than the
+ * stack's (their crossing points use the source's coordinate along the stack's axis); a part, or a strip, all of whose cells and
+ * their ancestors lie further from the source along the stack's axis than across it has W's bits although it is shifted.
+ *   c2r_set_mesh_origin removes the rounding for parts that lie anywhere in W: origin_d = W's index of the part's cell 1
+ * along axis d, minus 1 (W's index = the part's + origin).  cinterp then forms its crossing points from W's coordinates -- every
+ * source's position moved by the origin, in the sweep kernels only; cells, offsets, reaches and blocks stay the part's -- and
+ * the part has W's bits: in a chain A -> B -> C = W's 25..36, 13..24, 1..12 with the origins 24, 12 and 0 along z, B and C
+ * equal W bit for bit.  A context with a non-zero origin runs every batch through k_sweep_shell_entry and
+ * k_sweep_shell_fast_entry, a source with an entry or not; with the origin 0 it launches what it always launched.  Refused: a
+ * non-zero origin along a periodic axis, |origin_d| > 2^20, an open slab-wise pass; c2r_set_boundaries(_axes) refuses to make an
+ * axis periodic while the origin along it is not 0.  The origin belongs to the mesh: source lists come and go, it stays.
+ *   Refused, with a message and leaving everything unchanged: a bad ns or face, a source that does not stand beyond exactly
+ * that face, rounds < 1, a negative or non-finite column, a call inside an open slab-wise pass.  c2r_set_sources* clears the
+ * entries; c2r_set_boundaries*, beams, horizons and curves keep them.  The call acts on every device of a multi-device
+ * context.  c2r_get_source_face_entry returns face = -1 (and rounds = 0) while none is set.  c2r_get_source_trace keeps
+ * counting the vacuum.  Still refused for a source outside the mesh: the escape maps, the horizon loss, c2r_do_source and
+ * c2r_evolve0d. */
+int c2r_select_source_face_exit(c2r_ctx *ctx, int face, int nsel, const int *sources);
+int c2r_download_source_face_exit(c2r_ctx *ctx, int face, int ns, double *cols3, int *rounds, int *reached);
+int c2r_set_source_face_entry(c2r_ctx *ctx, int ns, int face, const double *cols3, int rounds);
+int c2r_get_source_face_entry(c2r_ctx *ctx, int ns, int *face, int *rounds);
+int c2r_set_mesh_origin(c2r_ctx *ctx, const int origin[3]);
+int c2r_get_mesh_origin(c2r_ctx *ctx, int origin[3]);
+
 /* The -DPL / -DQUASARS builds of the reference give every source up to two more SEDs
  * (radiation_photoionrates.f90:215-228, 256-271).  sed = 1: power law (pl_*), sed = 2: quasar-like (qpl_*).
  *   c2r_set_sed_tables   pl_/qpl_photo_thick/thin_table, pl_/qpl_heat_thick/thin_table (heat may be NULL
