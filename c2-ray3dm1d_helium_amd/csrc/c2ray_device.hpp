@@ -600,6 +600,13 @@ C2R_HD gm::Log10Arg log10_split_of(double x, const LT *) { return gm::log10_spli
 C2R_HD gm::Log10ArgFold log10_split_of(double x, const gm::LogFoldExp *tab) { return gm::log10_split_fold(x, tab->fold); }
 C2R_HD double log_table_path_of(const gm::Log10ArgFold &a, const gm::LogFoldExp *tab, const gm::LogPins *pins) { return gm::log_table_path_fold(a, tab->tab, pins); }
 C2R_HD double log10_finish_of(const gm::Log10ArgFold &a, double lg, const gm::LogFoldExp *tab) { return gm::log10_finish(a, lg, tab->exp0); }
+// (... and the table path with the near-1 test: by the limit of the entry it read, gm::LogFold::lim)
+C2R_HD double log_table_path_of(const gm::Log10ArgFold &a, const gm::LogFoldExp *tab, const gm::LogPins *pins, bool &near1) {
+  uint32_t lim;
+  const double lg = gm::log_table_path_fold(a, tab->tab, pins, &lim);
+  near1 = gm::log10_near1(a, lim);
+  return lg;
+}
 
 template <class LT>
 C2R_HD void tau_table_positions(double tau_a, double tau_b, const LT *logtab, TauPos &pa, TauPos &pb,
@@ -607,6 +614,22 @@ C2R_HD void tau_table_positions(double tau_a, double tau_b, const LT *logtab, Ta
   const auto a = log10_split_of(dmax_const(tau_a, 1.0e-20), logtab), b = log10_split_of(dmax_const(tau_b, 1.0e-20), logtab);
   double lga = log_table_path_of(a, logtab, pins), lgb = log_table_path_of(b, logtab, pins);
   const bool na = gm::log10_near1(a), nb = gm::log10_near1(b);
+  C2R_COUNT_LANES(12, na || nb);
+  C2R_COUNT_LANES(15, na && nb);
+  C2R_COUNT_LANES(18, any_lane(na) && any_lane(nb));
+  if (na || nb) {
+    if (na) lga = gm::log_near1(gm::log10_arg_value(a));
+    if (nb) lgb = gm::log_near1(gm::log10_arg_value(b));
+  }
+  pa = table_position_of_log(log10_finish_of(a, lga, logtab));
+  pb = table_position_of_log(log10_finish_of(b, lgb, logtab));
+}
+// the same for the folded table, whose near-1 test comes from the entry that the table path reads (chosen by the table's type)
+C2R_HD void tau_table_positions(double tau_a, double tau_b, const gm::LogFoldExp *logtab, TauPos &pa, TauPos &pb,
+                                const gm::LogPins *pins = nullptr) {
+  const auto a = log10_split_of(dmax_const(tau_a, 1.0e-20), logtab), b = log10_split_of(dmax_const(tau_b, 1.0e-20), logtab);
+  bool na, nb;
+  double lga = log_table_path_of(a, logtab, pins, na), lgb = log_table_path_of(b, logtab, pins, nb);
   C2R_COUNT_LANES(12, na || nb);
   C2R_COUNT_LANES(15, na && nb);
   C2R_COUNT_LANES(18, any_lane(na) && any_lane(nb));
@@ -652,6 +675,32 @@ static_assert(TABLE_PAIR_PITCH * sizeof(TablePair) < ((size_t)1 << 32), "load_ro
 C2R_HD TableRows load_rows(const TablePair *col, const TauPos &p) {
   return *(const TablePair *)((const char *)col + ((unsigned)p.ipos << 4));
 }
+// The same rows of the pair copy by an index-scaled buffer load (the all-periodic isothermal one-SED k_rates alone): the
+// descriptor of the copy has a stride of one pair, so the load takes the position itself as its index (idxen) and the unit that
+// forms the address multiplies -- no shift per position.  The band's column is chosen by a scalar byte offset, which the
+// range check does not see: with num_records = NTAUP the check covers exactly one column, whichever band it is.  A position
+// reaches rows 0 .. NumTau (ipos <= NumTau, table_position_of_log; row NumTau + 1 is the duplicate that no position reads), all
+// within the column; an index outside it would read zeros, not fault.
+#if defined(__HIP_DEVICE_COMPILE__)
+typedef int BufferDwords4 __attribute__((ext_vector_type(4)));
+__device__ BufferDwords4 struct_buffer_load_dwordx4(__amdgpu_buffer_rsrc_t rsrc, int vindex, int voffset, int soffset, int aux) __asm("llvm.amdgcn.struct.ptr.buffer.load.v4i32");
+// word 3 of a GFX9 buffer descriptor (LLVM's AMDGPU usage document): DATA_FORMAT = 32 (bits 15-18), everything else 0 --
+// no swizzle, no added thread id; an untyped load reads neither the format nor the destination selects
+constexpr int BUFFER_RSRC_FLAGS = 0x00020000;
+C2R_HD TableRows load_rows(const TablePair *pairs, uint32_t band_offset, const TauPos &p) {
+  const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc((void *)pairs, (short)sizeof(TablePair), NTAUP, BUFFER_RSRC_FLAGS);
+  const BufferDwords4 v = struct_buffer_load_dwordx4(rsrc, p.ipos, 0, (int)band_offset, 0);
+  TableRows r;
+  r.c = __hiloint2double(v.y, v.x);
+  r.d = __hiloint2double(v.w, v.z);
+  return r;
+}
+#else
+C2R_HD TableRows load_rows(const TablePair *pairs, uint32_t band_offset, const TauPos &p) {
+  return (unsigned)p.ipos < (unsigned)NTAUP ? *(const TablePair *)((const char *)(pairs + p.ipos) + band_offset) : TableRows{0.0, 0.0};
+}
+#endif
+static_assert(table_pair_index(NFREQ, 0) * sizeof(TablePair) < ((size_t)1 << 31), "load_rows: a band's byte offset is a 32-bit scalar");
 C2R_HD double interpolate_rows(const TableRows &r, const TauPos &p) { return r.c + r.d * p.residual; }
 
 // Heating tables as the rates kernels read them: INTERLEAVED by band.  The reference keeps one column of 0:NumTau
@@ -1061,9 +1110,15 @@ C2R_HD void band_positions_gathers_first(const LT *logtab, const CellSrc &c, dou
     }
   }
   // (gathers first: `photo_thick` is the table's pair copy, RatesTables::pairs, handed down under the table's name)
-  const TablePair *tk = (const TablePair *)photo_thick + table_pair_index(b, 0);
-  R.in = load_rows(tk, B.pin);
-  R.out = load_rows(tk, B.pout);
+  if constexpr (std::is_same_v<LT, gm::LogFoldExp>) { // (the all-periodic kernel: by the position as an index, above load_rows)
+    const uint32_t band_offset = (uint32_t)(table_pair_index(b, 0) * sizeof(TablePair));
+    R.in = load_rows((const TablePair *)photo_thick, band_offset, B.pin);
+    R.out = load_rows((const TablePair *)photo_thick, band_offset, B.pout);
+  } else {
+    const TablePair *tk = (const TablePair *)photo_thick + table_pair_index(b, 0);
+    R.in = load_rows(tk, B.pin);
+    R.out = load_rows(tk, B.pout);
+  }
   if (CLS >= 1 && c.recip_safe) {
     forscaleing = recip_nr(den);
     pin_here(forscaleing);

@@ -321,14 +321,23 @@ struct LogEntryExp {
 // 1. The power of two folded into the reciprocal.  log_table_path4 uses z = x' * 2^-k (k in {-1, 0, 1}, LogEntry::kshift) in
 //    one place, r = fma(z, invc, -1).  invc * 2^-k is exact, so fma(x', invc * 2^-k, -1) is the same real number rounded
 //    once: the same bits, without kshift, its read and the subtraction.  A LogFold entry holds {invc * 2^-k, w, c} at the
-//    pitch of LogEntry (the index arithmetic stays), read as one 16-byte and one 8-byte piece.
+//    pitch of LogEntry (the index arithmetic stays), read as two pieces: {invc, w} and c (with the limit of 3. behind it).
 // 2. hx by a select, and the exponent table's offset from the same subtraction.  hx of log10_split is the mantissa of x
 //    under the exponent field of [0.5, 1) for x < 1 and of [1, 2) otherwise; hi - hx is then ky << 20, and its arithmetic
 //    shift by 16 the byte offset ky << 4 into the exponent table, counted from the entry of ky = 0.  ky itself is not formed.
-struct LogFold {
+// 3. The near-1 test from the table.  log10_near1's window [0x3FEE0000, 0x3FF10900) of hx starts on the boundary of entry 112
+//    and ends inside entry 136, so a limit per entry -- 0 outside the window, all ones for the entries wholly inside it,
+//    the window's end for entry 136 -- makes the test hx < lim: one compare, without the subtraction.  The limit stands in
+//    the entry's spare bytes behind c and is read with it.
+struct alignas(16) LogFold {
   double invc, w, c; // invc * 2^-k; w and c as in LogEntry
-  uint64_t pad;
+  uint32_t lim, pad; // hx is within log10_near1's window if and only if hx < lim
 };
+static_assert(sizeof(LogFold) == 32, "LogFold: the pitch of LogEntry");
+constexpr uint32_t LOG_NEAR1_LO = 0x3FEE0000u, LOG_NEAR1_HI = 0x3FF10900u; // log10_near1's window of hx
+constexpr int LOG_NEAR1_E0 = (int)((LOG_NEAR1_LO - 0x3FE00000u) >> 13), LOG_NEAR1_E1 = (int)((LOG_NEAR1_HI - 0x3FE00000u) >> 13);
+static_assert(LOG_NEAR1_LO == 0x3FE00000u + ((uint32_t)LOG_NEAR1_E0 << 13) && LOG_NEAR1_E0 == 112 && LOG_NEAR1_E1 == 136,
+              "LogFold::lim: the window starts with an entry");
 C2R_MHD LogFold make_log_fold(int E) { // E in [0, 256)
   const LogEntry e = make_log_entry(E);
   const int k = (E - 0x30) >> 7; // as make_log_entry has it
@@ -336,6 +345,7 @@ C2R_MHD LogFold make_log_fold(int E) { // E in [0, 256)
   f.invc = e.invc * (k < 0 ? 2.0 : (k > 0 ? 0.5 : 1.0)); // exact
   f.w = e.w;
   f.c = e.c;
+  f.lim = E < LOG_NEAR1_E0 || E > LOG_NEAR1_E1 ? 0u : (E < LOG_NEAR1_E1 ? 0xFFFFFFFFu : LOG_NEAR1_HI);
   f.pad = 0;
   return f;
 }
@@ -376,15 +386,27 @@ C2R_MHD Log10ArgFold log10_split_fold(double x, const FoldPins *fp = nullptr) { 
   return a;
 }
 C2R_MHD bool log10_near1(const Log10ArgFold &a) { return a.hx - 0x3FEE0000u < 0x00030900u; }
+// the same test by the limit of hx's own table entry (LogFold::lim)
+C2R_MHD bool log10_near1(const Log10ArgFold &a, uint32_t lim) { return a.hx < lim; }
 C2R_MHD double log10_arg_value(const Log10ArgFold &a) { return asdouble(((uint64_t)a.hx << 32) | a.lo); }
-// log_table_path4 with z = x' and no kshift
-C2R_MHD double log_table_path_fold(const Log10ArgFold &a, const LogFold *tab, const LogPins *pins = nullptr) {
+// log_table_path4 with z = x' and no kshift; `lim`, where given, receives the entry's near-1 limit, read in one piece with c
+C2R_MHD double log_table_path_fold(const Log10ArgFold &a, const LogFold *tab, const LogPins *pins = nullptr, uint32_t *lim = nullptr) {
   const double *A = GMT(log_hdr) + 2;
   const double A1 = pins ? pins->a1 : A[1], A3 = pins ? pins->a3 : A[3];
   const uint32_t T = a.hx - 0x3FE00000u;  // [0, 0x200000)
   const uint32_t off = (T >> 8) & 0x1FE0u; // entry T >> 13 of 32-byte entries
   const LogFold *e = (const LogFold *)((const char *)tab + off);
-  const double invc = e->invc, w = e->w, c = e->c;
+  const double invc = e->invc, w = e->w;
+#if defined(__HIP_DEVICE_COMPILE__)
+  // c and the limit as the one 16-byte piece they are (two reads per entry, as without the limit)
+  typedef uint32_t LogFoldTail __attribute__((ext_vector_type(4)));
+  const LogFoldTail t = *(const LogFoldTail *)&e->c;
+  const double c = asdouble(((uint64_t)t.y << 32) | t.x);
+  if (lim) *lim = t.z;
+#else
+  const double c = e->c;
+  if (lim) *lim = e->lim;
+#endif
   const double r = fma_(log10_arg_value(a), invc, -1.0);
   const double t1 = fma_kc(r, A[2], A1);
   const double hi_ = r + w;

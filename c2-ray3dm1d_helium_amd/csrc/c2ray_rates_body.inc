@@ -22,6 +22,8 @@
   constexpr bool ISO1 = !HEAT && !MULTI && !BEAM;
   // ... and, with all axes periodic (FOLD), its log table holds the reciprocal with the power of two folded in as well
   // (gm::LogFold: the same pitch, no kshift) and its split hands down the exponent table's byte offset (gm::LogFoldExp).
+  // By the same type it takes the near-1 test of a logarithm from the table entry (gm::LogFold::lim) and fetches a band's two
+  // rows of the pair copy by index-scaled buffer loads (load_rows with a band offset, c2ray_device.hpp).
   // The open-boundary twin stays the kernel it was: the same route brings it from 92 to 94 registers, with or without the
   // select's constants pinned, past the budget of 93 (tests/test_rates_registers.py).
   constexpr bool FOLD = ISO1 && !OPEN;
