@@ -32,6 +32,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <cerrno>
 #include <chrono>
 #include <cmath>
 #include <cstdarg>
@@ -1018,6 +1019,9 @@ k_rates_curve(Grid g, const SrcDev *__restrict__ src, int nsrc, StepScalars sc, 
 // ---------------------------------------------------------------------------------------------
 // evolve0D_global + do_chemistry (files_for_3D/evolve_point.F90:325-440, :444-646), one cell per lane.
 constexpr int CHEM_HIST = 24; // buckets of the histogram of thermal sub-steps per cell (powers of two)
+// deferred cells that fit the device all at once, two waves per SIMD ("Heating global pass in tiers"); a context's own value:
+// c2r_ctx::chem_resident
+constexpr int CHEM_RESIDENT_CELLS = 131072;
 // The counters of a pass -- cells not converged, the histogram, the two longest chains -- are one atomic per wave each,
 // and atomics of device scope on ONE address are served one after the other, some 6 ns apiece: with the 262 144
 // single-wave blocks of 256^3 every such counter cost 1.6 ms of a 5 ms heating launch (measured: 6.7 ms with three of
@@ -1930,6 +1934,7 @@ struct c2r_ctx {
   double *d_iter = nullptr;        // k_iter_stats: STAT_BLOCKS*(ITER_NV+2) partials + 32 results
   double *h_iter = nullptr;        // pinned, 32
   int chem_first = 16;              // first rung of the next heating pass's ladder of sub-step ceilings (CHEM_FIRST_CEILING)
+  long long chem_resident = CHEM_RESIDENT_CELLS; // the ladder ends once no more cells than this are left (C2R_CHEM_RESIDENT_CELLS)
   // c2r_evolve0d: the column block of the source being traced cell by cell, and which source that is
   double *d_point_cols = nullptr;
   int point_ns = 0, point_niter = 0;
@@ -2276,7 +2281,16 @@ extern "C" int c2r_create(c2r_ctx **out, int device, const int mesh[3]) {
     return fail(nullptr, "c2r_create: no HIP device available (%s); this library has no CPU path",
                 e == hipSuccess ? "device count 0" : hipGetErrorString(e));
   if (device < 0 || device >= ndev) return fail(nullptr, "c2r_create: device %d not in [0,%d)", device, ndev);
+  long long chem_resident = CHEM_RESIDENT_CELLS;
+  if (const char *e = getenv("C2R_CHEM_RESIDENT_CELLS")) {
+    char *end = nullptr;
+    errno = 0;
+    chem_resident = strtoll(e, &end, 10);
+    if (end == e || *end != '\0' || errno != 0 || chem_resident < 0)
+      return fail(nullptr, "c2r_create: C2R_CHEM_RESIDENT_CELLS=\"%s\" is not a cell count (a whole number, 0 or more)", e);
+  }
   c2r_ctx *c = new c2r_ctx;
+  c->chem_resident = chem_resident;
   c->device = device;
   c->g.n1 = mesh[0]; c->g.n2 = mesh[1]; c->g.n3 = mesh[2];
   c->g.l1 = mesh[0] / 2; c->g.l2 = mesh[1] / 2; c->g.l3 = mesh[2] / 2;
@@ -4794,7 +4808,9 @@ extern "C" int c2r_do_source(c2r_ctx *c, int ns) {
 // ceiling of 512 while two thirds of its cells needed fewer than 64 sub-steps.)  The last tier is the longest chain
 // of the mesh -- some 14 000 sub-steps, 16 ms, however few cells are left -- and nothing on the device shortens that.
 // Results do not depend on any of this: a dropped cell stores nothing and is recomputed from the same inputs.
-constexpr int CHEM_FIRST_CEILING = 16, CHEM_CEILING_STEP = 4, CHEM_LAST_CEILING = 1024, CHEM_TIERS = 6, CHEM_RESIDENT_CELLS = 131072;
+// C2R_CHEM_RESIDENT_CELLS (environment, read by c2r_create; diagnostic): another residency cut than 131 072 cells, 0 for
+// none, so that small meshes walk the whole ladder.  It changes launches, never results.
+constexpr int CHEM_FIRST_CEILING = 16, CHEM_CEILING_STEP = 4, CHEM_LAST_CEILING = 1024, CHEM_TIERS = 6;
 
 static int launch_chemistry(c2r_ctx *c, hipStream_t st, double dt, size_t first, size_t count, const int *list, int budget,
                             int *deferred, int *ndeferred) {
@@ -4998,7 +5014,7 @@ extern "C" int c2r_global_pass_finish(c2r_ctx *c, int *conv_flag) {
       const int nxt = cur ^ 1;
       ceiling *= CHEM_CEILING_STEP;
       HIPCHK(c, hipMemsetAsync(c->d_chemctl + nxt, 0, sizeof(int), c->stream));
-      const bool last = t == CHEM_TIERS - 1 || n <= CHEM_RESIDENT_CELLS || ceiling > CHEM_LAST_CEILING;
+      const bool last = t == CHEM_TIERS - 1 || n <= c->chem_resident || ceiling > CHEM_LAST_CEILING;
       if (launch_chemistry(c, c->stream, c->chem_dt, 0, (size_t)n, c->d_defer[cur], last ? 0 : (int)ceiling, c->d_defer[nxt],
                            c->d_chemctl + nxt))
         return 1;

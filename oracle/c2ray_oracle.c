@@ -290,11 +290,34 @@ static double cosmo_cool(double e_int, double zred, double H0, double Omega0) {
   return e_int * 2.0 / (1.0 + zred) * dzdt;
 }
 
-/* thermal.f90:22-174 (cosmological = .true., c2ray_parameters.f90:84) */
-void orc_thermal(const orc_tables *tb, double dt, double *end_temper, double *avg_temper,
-                 double ndens_electron, double ndens_atom, const orc_ionstates *ion,
-                 const orc_photrates *phi, double zred, double H0, double Omega0) {
+/* what the counting entry points (orc_thermal_work, orc_global_pass_work) collect: trips through thermal's loop, and
+ * how often {the minitemp floor was applied, the i_heating > 10000 exit was taken, a cell left do_chemistry by
+ * nit > 400, a call skipped the sub-cycle because end_temper <= minitemp}.  Integers beside the arithmetic: no
+ * result depends on them. */
+typedef struct {
+  long long trips;
+  long long events[4];
+  /* orc_cell_thermal_calls: the arguments of every thermal call, ORC_TAP_ROW doubles each (see the header) */
+  double *tap;
+  int tap_cap, tap_n;
+} workstats;
+
+/* thermal.f90:22-174 (cosmological = .true., c2ray_parameters.f90:84); ws may be NULL */
+static void thermal_counted(const orc_tables *tb, double dt, double *end_temper, double *avg_temper,
+                            double ndens_electron, double ndens_atom, const orc_ionstates *ion,
+                            const orc_photrates *phi, double zred, double H0, double Omega0, workstats *ws) {
   double heating = phi->heat;
+  workstats before;
+  double *row = NULL;
+  if (ws) {
+    before = *ws;
+    if (ws->tap && ws->tap_n < ws->tap_cap) {
+      row = ws->tap + (size_t)ORC_TAP_ROW * ws->tap_n;
+      row[0] = dt; row[1] = *end_temper; row[2] = ndens_electron; row[3] = ndens_atom; row[4] = heating;
+      memcpy(row + 5, ion, 15 * sizeof(double));
+    }
+    if (ws->tap) ws->tap_n++;
+  }
   double internal_energy =
       temper2pressr(*end_temper, ndens_atom, orc_electrondens(ndens_atom, ion->h_old, ion->he_old)) / gamma1();
   double cosmo_cool_rate = cosmo_cool(internal_energy, zred, H0, Omega0);
@@ -305,6 +328,7 @@ void orc_thermal(const orc_tables *tb, double dt, double *end_temper, double *av
     double initial_temp = *end_temper;
     for (;;) {
       i_heating++;
+      if (ws) ws->trips++;
       double cooling = orc_coolin(tb, ndens_atom, ndens_electron, ion->h_av, ion->he_av, *end_temper) + cosmo_cool_rate;
       double thermal_rate = dmax(1e-50, fabs(cooling - heating));
       double thermal_timescale = internal_energy / fabs(thermal_rate);
@@ -319,15 +343,46 @@ void orc_thermal(const orc_tables *tb, double dt, double *end_temper, double *av
         /* thermal.f90:141 -- no division by gamma1 here, reproduced as is */
         internal_energy = temper2pressr(minitemp, ndens_atom, orc_electrondens(ndens_atom, ion->h_av, ion->he_av));
         *end_temper = minitemp;
+        if (ws) ws->events[0]++;
       }
       cumulative_time = cumulative_time + dt_ODE;
       if (cumulative_time >= dt || fabs(cumulative_time - dt) < F(1e-6) * dt) break;
-      if (i_heating > 10000) break;
+      if (i_heating > 10000) {
+        if (ws) ws->events[1]++;
+        break;
+      }
     }
     if (dt > 0.0) *avg_temper = *avg_temper / dt; else *avg_temper = initial_temp;
     *end_temper = pressr2temper(internal_energy * gamma1(), ndens_atom,
                                 orc_electrondens(ndens_atom, ion->h, ion->he));
+  } else if (ws) {
+    ws->events[3]++;
   }
+  if (row) {
+    row[20] = (double)(ws->trips - before.trips);
+    row[21] = (double)(ws->events[0] - before.events[0]);
+    row[22] = (double)(ws->events[1] - before.events[1]);
+    row[23] = (double)(ws->events[3] - before.events[3]);
+  }
+}
+
+void orc_thermal(const orc_tables *tb, double dt, double *end_temper, double *avg_temper,
+                 double ndens_electron, double ndens_atom, const orc_ionstates *ion,
+                 const orc_photrates *phi, double zred, double H0, double Omega0) {
+  thermal_counted(tb, dt, end_temper, avg_temper, ndens_electron, ndens_atom, ion, phi, zred, H0, Omega0, NULL);
+}
+
+/* orc_thermal, and what it did: returns the trips through its loop (0: the sub-cycle was skipped) and adds to
+ * events[4] {floor applied, i_heating > 10000 exit, (unused here), sub-cycle skipped} */
+int orc_thermal_work(const orc_tables *tb, double dt, double *end_temper, double *avg_temper,
+                     double ndens_electron, double ndens_atom, const orc_ionstates *ion,
+                     const orc_photrates *phi, double zred, double H0, double Omega0, long long events[4]) {
+  workstats ws;
+  memset(&ws, 0, sizeof ws);
+  thermal_counted(tb, dt, end_temper, avg_temper, ndens_electron, ndens_atom, ion, phi, zred, H0, Omega0, &ws);
+  if (events)
+    for (int n = 0; n < 4; n++) events[n] += ws.events[n];
+  return (int)ws.trips;
 }
 
 /* ---------------------------------------------------------------------------------------------
@@ -806,7 +861,7 @@ void orc_pass_all_sources(const orc_tables *tb, const orc_step *st, orc_state *s
  * files_for_3D/evolve_point.F90:444-646 do_chemistry (local = .false.) and :325-440 evolve0D_global
  */
 static void do_chemistry(const orc_tables *tb, const orc_step *st, orc_state *s, double dt, double ndens_p,
-                         orc_ionstates *ion, const orc_photrates *phi, size_t q) {
+                         orc_ionstates *ion, const orc_photrates *phi, size_t q, workstats *ws) {
   const size_t ncell = (size_t)st->mesh[0] * st->mesh[1] * st->mesh[2];
   double temper_inter, avg_temper, temper1, temper0, temper2;
   orc_reccoef rc = st->rc;
@@ -864,7 +919,7 @@ static void do_chemistry(const orc_tables *tb, const orc_step *st, orc_state *s,
     de = orc_electrondens(ndens_p, ion->h_av, ion->he_av);
     temper1 = temper0;
     if (!st->isothermal)
-      orc_thermal(tb, dt, &temper1, &avg_temper, de, ndens_p, ion, phi, st->zred, st->H0, st->Omega0);
+      thermal_counted(tb, dt, &temper1, &avg_temper, de, ndens_p, ion, phi, st->zred, st->H0, st->Omega0, ws);
 
     if ((fabs((ion->h_av[0] - yh0_av_old) / ion->h_av[0]) < minimum_fractional_change ||
          ion->h_av[0] < minimum_fraction_of_atoms) &&
@@ -874,7 +929,10 @@ static void do_chemistry(const orc_tables *tb, const orc_step *st, orc_state *s,
          ion->he_av[2] < minimum_fraction_of_atoms) &&
         fabs((temper1 - temper2) / temper1) < minimum_fractional_change)
       break;
-    if (nit > 400) break;
+    if (nit > 400) {
+      if (ws) ws->events[2]++;
+      break;
+    }
   }
   if (!st->isothermal) { /* set_temperature_point, mat_ini_test.F90:491-502 */
     s->temperature[q] = (float)temper1;
@@ -883,7 +941,7 @@ static void do_chemistry(const orc_tables *tb, const orc_step *st, orc_state *s,
 }
 
 static void evolve0D_global(const orc_tables *tb, const orc_step *st, orc_state *s, double dt, size_t q,
-                            int *conv_flag) {
+                            int *conv_flag, workstats *ws) {
   const size_t ncell = (size_t)st->mesh[0] * st->mesh[1] * st->mesh[2];
   orc_ionstates ion;
   orc_photrates phi;
@@ -905,7 +963,7 @@ static void evolve0D_global(const orc_tables *tb, const orc_step *st, orc_state 
   phi.photo_cell_HeII = s->phihe[q + ncell];
   if (!st->isothermal) phi.heat = s->phiheat[q];
 
-  do_chemistry(tb, st, s, dt, ndens_p, &ion, &phi, q);
+  do_chemistry(tb, st, s, dt, ndens_p, &ion, &phi, q, ws);
 
   double yh0_av_old = s->xh_av[q];
   double yhe0_av_old = s->xhe_av[q];
@@ -933,8 +991,40 @@ static void evolve0D_global(const orc_tables *tb, const orc_step *st, orc_state 
 int orc_global_pass(const orc_tables *tb, const orc_step *st, orc_state *s, double dt) {
   const size_t ncell = (size_t)st->mesh[0] * st->mesh[1] * st->mesh[2];
   int conv_flag = 0;
-  for (size_t q = 0; q < ncell; q++) evolve0D_global(tb, st, s, dt, q, &conv_flag);
+  for (size_t q = 0; q < ncell; q++) evolve0D_global(tb, st, s, dt, q, &conv_flag, NULL);
   return conv_flag;
+}
+
+/* orc_global_pass, and what it did: work[q] = trips through thermal's loop summed over cell q's do_chemistry
+ * iterations (what k_chemistry's `work` counts), events[4] = per-pass totals of {floor applied, i_heating > 10000
+ * exit, cells that left by nit > 400, thermal calls that skipped the sub-cycle}.  Same arithmetic, same results. */
+int orc_global_pass_work(const orc_tables *tb, const orc_step *st, orc_state *s, double dt, int *work,
+                         long long events[4]) {
+  const size_t ncell = (size_t)st->mesh[0] * st->mesh[1] * st->mesh[2];
+  int conv_flag = 0;
+  if (events) memset(events, 0, 4 * sizeof(long long));
+  for (size_t q = 0; q < ncell; q++) {
+    workstats ws;
+    memset(&ws, 0, sizeof ws);
+    evolve0D_global(tb, st, s, dt, q, &conv_flag, &ws);
+    if (work) work[q] = (int)ws.trips;
+    if (events)
+      for (int n = 0; n < 4; n++) events[n] += ws.events[n];
+  }
+  return conv_flag;
+}
+
+/* evolve0D_global for the one cell q (0-based), as orc_global_pass applies it (the cell's state is advanced), with the
+ * arguments of its thermal calls written to rows[cap][ORC_TAP_ROW]; returns the number of calls (it may exceed cap) */
+int orc_cell_thermal_calls(const orc_tables *tb, const orc_step *st, orc_state *s, double dt, long long q, double *rows,
+                           int cap) {
+  workstats ws;
+  int conv_flag = 0;
+  memset(&ws, 0, sizeof ws);
+  ws.tap = rows;
+  ws.tap_cap = cap;
+  evolve0D_global(tb, st, s, dt, (size_t)q, &conv_flag, &ws);
+  return ws.tap_n;
 }
 
 /* the same over `nthreads` OpenMP threads: cells are independent, the count is an integer sum */
@@ -945,7 +1035,7 @@ int orc_global_pass_threads(const orc_tables *tb, const orc_step *st, orc_state 
 #pragma omp parallel for schedule(dynamic, 4096) num_threads(nthreads) reduction(+ : conv_flag)
   for (long long q = 0; q < ncell; q++) {
     int c = 0;
-    evolve0D_global(tb, st, s, dt, (size_t)q, &c);
+    evolve0D_global(tb, st, s, dt, (size_t)q, &c, NULL);
     conv_flag += c;
   }
   return conv_flag;

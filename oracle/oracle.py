@@ -258,6 +258,35 @@ def global_pass(tables, step, state, dt):
     return lib().orc_global_pass(C.byref(tables.c), C.byref(step.c), C.byref(state.c), C.c_double(dt))
 
 
+EVENTS = ("floor", "cap", "nit", "cold")
+
+
+def global_pass_work(tables, step, state, dt):
+    """global_pass, and what it did: (conv_flag, work[ncell], events).  work = trips through thermal's loop per
+    cell, summed over its do_chemistry iterations; events = per-pass totals, in the order of EVENTS: the minitemp
+    floor applied, the i_heating > 10000 exit taken, cells that left by nit > 400, thermal calls that skipped the
+    sub-cycle."""
+    l = lib()
+    l.orc_global_pass_work.restype = C.c_int
+    l.orc_global_pass_work.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, _ip, C.POINTER(C.c_longlong)]
+    work = np.zeros(step.ncell, dtype=np.int32)
+    ev = (C.c_longlong * 4)()
+    conv = l.orc_global_pass_work(C.byref(tables.c), C.byref(step.c), C.byref(state.c), float(dt), _p(work, _ip), ev)
+    return int(conv), work, dict(zip(EVENTS, (int(x) for x in ev)))
+
+
+def cell_thermal_calls(tables, step, state, dt, q, cap=1024):
+    """evolve0D_global for the one cell q (0-based; its state is advanced) and the thermal calls it made: (rows, calls), rows
+    (min(calls, cap), 24) = dt, end_temper on entry, ndens_electron, ndens_atom, heating, ion (15), then what the call did:
+    trips through the loop, times the floor was applied, cap exit taken, sub-cycle skipped."""
+    l = lib()
+    l.orc_cell_thermal_calls.restype = C.c_int
+    l.orc_cell_thermal_calls.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_longlong, _dp, C.c_int]
+    rows = np.zeros((cap, 24))
+    n = int(l.orc_cell_thermal_calls(C.byref(tables.c), C.byref(step.c), C.byref(state.c), float(dt), int(q), _p(rows), cap))
+    return rows[:min(n, cap)].copy(), n
+
+
 def global_pass_threads(tables, step, state, dt, nthreads=1):
     l = lib()
     l.orc_global_pass_threads.restype = C.c_int
@@ -315,6 +344,21 @@ def thermal(tables, dt, tend, tavg, de, nd, ion15, heat, zred, H0, Omega0):
                       C.c_double(nd), C.byref(ion), C.byref(phi), C.c_double(zred), C.c_double(H0),
                       C.c_double(Omega0))
     return te.value, ta.value
+
+
+def thermal_work(tables, dt, tend, tavg, de, nd, ion15, heat, zred, H0, Omega0):
+    """thermal, and what it did: (end_temper, avg_temper, trips through its loop, events as in EVENTS)."""
+    l = lib()
+    l.orc_thermal_work.restype = C.c_int
+    ion = IonStates.from_array(ion15)
+    phi = PhotRates()
+    phi.heat = float(heat)
+    te, ta = C.c_double(tend), C.c_double(tavg)
+    ev = (C.c_longlong * 4)()
+    trips = l.orc_thermal_work(C.byref(tables.c), C.c_double(dt), C.byref(te), C.byref(ta), C.c_double(de),
+                               C.c_double(nd), C.byref(ion), C.byref(phi), C.c_double(zred), C.c_double(H0),
+                               C.c_double(Omega0), ev)
+    return te.value, ta.value, int(trips), dict(zip(EVENTS, (int(x) for x in ev)))
 
 
 def constants():

@@ -181,6 +181,16 @@ void hh_thermal(double dt, double *tend, double *tavg, double de, double nd, con
   thermal(cd, dt, *tend, *tavg, de, nd, ion, heat);
 }
 
+// thermal() with the caller's running count of sub-steps and its ceiling, as k_chemistry calls it: returns the flag
+// ("the count passed the ceiling: abandon the cell"); *work comes back as the routine left it
+int hh_thermal_budget(double dt, double *tend, double *tavg, double de, double nd, const double *ion15, double heat,
+                      double zred, double H0, double Omega0, int *work, int budget) {
+  IonStates ion;
+  std::memcpy(&ion, ion15, sizeof ion);
+  CoolData cd{T.cool.data(), T.mintemp, T.dtemp, zred, H0, Omega0, nullptr};
+  return thermal(cd, dt, *tend, *tavg, de, nd, ion, heat, work, budget) ? 1 : 0;
+}
+
 // cinterp (column_density.f90:28-345) assembled from short_characteristic + interp_column the way
 // k_sweep_shell does it; pos/srcpos are 1-based, pos may lie outside the mesh.
 void hh_cinterp(const int *mesh, const double *cH, const double *cHe, const int *pos, const int *src, double *out4) {
