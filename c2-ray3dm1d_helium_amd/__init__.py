@@ -10,7 +10,7 @@ that are not valid in a Python identifier, so load it with
 
 (__graft_entry__.load_package() and tests/conftest.py do exactly that).
 """
-from . import _build, _lib, hostphys, parallel  # noqa: F401
+from . import _build, _lib, handover, hostphys, parallel  # noqa: F401
 from ._lib import C2RayHipError  # noqa: F401
 from .evolve import (Cosmology, Evolve, GridProps, HipEngine, Material, RadiationTables,  # noqa: F401
                      SourceProps)

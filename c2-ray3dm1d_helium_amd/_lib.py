@@ -80,6 +80,11 @@ class PlaneCurve(C.Structure):
                 ("factor", C.c_double * (PLANE_CURVE_MAX_STEPS + 1))]
 
 
+class SourceHalo(C.Structure):
+    """c2r_source_halo (include/c2ray_hip.h)."""
+    _fields_ = [("rounds", C.c_int), ("face", _dp * 3), ("edge", _dp * 3), ("corner", _dp)]
+
+
 class SedSetup(C.Structure):
     """struct c2r_sed_setup (include/c2ray_hip.h)."""
     _fields_ = [("nfreq", C.c_int), ("sed", C.c_int), ("freq_min", _dp), ("delta_freq", _dp), ("xsec_index", _dp),
@@ -110,6 +115,8 @@ SYMBOLS = {
     "c2r_download_source_face_exit": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, _ip, _ip]),
     "c2r_set_source_face_entry": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, C.c_int]),
     "c2r_get_source_face_entry": (C.c_int, [C.c_void_p, C.c_int, _ip, _ip]),
+    "c2r_set_source_halo": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(SourceHalo)]),
+    "c2r_get_source_halo": (C.c_int, [C.c_void_p, C.c_int, _ip, _ip]),
     "c2r_set_mesh_origin": (C.c_int, [C.c_void_p, _ip]),
     "c2r_get_mesh_origin": (C.c_int, [C.c_void_p, _ip]),
     "c2r_set_sed_tables": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, _dp, _dp, C.c_int, C.c_int]),

@@ -1,6 +1,6 @@
 // Point-source hand-over between meshes stacked along an open axis (include/c2ray_hip.h): the entry points of the exit
 // strips (c2r_select_source_face_exit, c2r_download_source_face_exit) and of the entry columns (c2r_set_source_face_entry,
-// c2r_get_source_face_entry) and of the mesh's place in a deep mesh (c2r_set_mesh_origin).  Included by c2ray_hip.hip, which has the kernels (k_source_face_exit, k_sweep_shell_entry,
+// c2r_get_source_face_entry; through several faces, across edges and corners: c2r_set_source_halo, c2r_get_source_halo) and of the mesh's place in a deep mesh (c2r_set_mesh_origin).  Included by c2ray_hip.hip, which has the kernels (k_source_face_exit, k_sweep_shell_entry,
 // k_sweep_shell_fast_entry, k_loss_entry) and the pass's side of both (place_batch, sweep_batch, queue_source_face_exit).
 
 // cells of a face of axis `axis`
@@ -87,19 +87,40 @@ static int ensure_entry_records(c2r_ctx *c) {
   }
   return 0;
 }
+// drops the entry or halo of source ns, if it has one
+static int clear_source_entry(c2r_ctx *c, int ns) {
+  if (c->src_entry.empty() || c->src_entry[(size_t)ns - 1].face < 0) return 0;
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  c2r_ctx::FaceEntry &e = c->src_entry[(size_t)ns - 1];
+  HIPCHK(c, hipFree(e.d_cols));
+  e = c2r_ctx::FaceEntry();
+  return 0;
+}
+// Keeps `fresh` (its faces, offsets and rounds; all arrays checked) as the entry or halo of source ns, with `packed` -- the
+// arrays one behind the other -- as its one allocation; whatever the source had before goes.
+static int keep_source_entry(c2r_ctx *c, int ns, c2r_ctx::FaceEntry fresh, std::vector<double> &packed) {
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipStreamSynchronize(c->stream)); // (nothing queued may still read a strip that is replaced)
+  if (ensure_entry_records(c)) return 1;
+  double *d_new = nullptr;
+  HIPCHK(c, hipMalloc(&d_new, sizeof(double) * packed.size()));
+  // (-0.0 passes the callers' test: stored as +0.0, the vacuum's own column)
+  for (double &v : packed) v = v + 0.0;
+  HIPCHK(c, hipMemcpyAsync(d_new, packed.data(), sizeof(double) * packed.size(), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (c->src_entry.size() != (size_t)c->nsrc) c->src_entry.assign((size_t)c->nsrc, c2r_ctx::FaceEntry());
+  c2r_ctx::FaceEntry &e = c->src_entry[(size_t)ns - 1];
+  if (e.d_cols) HIPCHK(c, hipFree(e.d_cols));
+  e = fresh;
+  e.d_cols = d_new;
+  return 0;
+}
 static int set_source_face_entry_one(c2r_ctx *c, int ns, int face, const double *cols3, int rounds) {
   if (!c) return 1;
   if (ns < 1 || ns > c->nsrc) return fail(c, "c2r_set_source_face_entry: source %d not in [1,%d]", ns, c->nsrc);
   if (c->pass_open) return fail(c, "c2r_set_source_face_entry: a pass opened by c2r_pass_sources_begin is still open (close it with c2r_pass_sources_end first)");
-  if (!cols3) { // clear
-    if (c->src_entry.empty() || c->src_entry[(size_t)ns - 1].face < 0) return 0;
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    c2r_ctx::FaceEntry &e = c->src_entry[(size_t)ns - 1];
-    HIPCHK(c, hipFree(e.d_cols));
-    e = c2r_ctx::FaceEntry();
-    return 0;
-  }
+  if (!cols3) return clear_source_entry(c, ns); // (an entry or a halo)
   if (face < 0 || face > 5) return fail(c, "c2r_set_source_face_entry: face %d, expected 0..5 (2 * axis + high)", face);
   const int axis = face >> 1, high = face & 1;
   const int mesh[3] = {c->g.n1, c->g.n2, c->g.n3};
@@ -116,23 +137,12 @@ static int set_source_face_entry_one(c2r_ctx *c, int ns, int face, const double 
     if (!(cols3[i] >= 0.0) || !std::isfinite(cols3[i]))
       return fail(c, "c2r_set_source_face_entry: source %d: entry %zu of species %d is %g (a column is finite and not negative)", ns,
                   i % (n3 / 3), (int)(i / (n3 / 3)), cols3[i]);
-  HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, hipStreamSynchronize(c->stream)); // (nothing queued may still read a strip that is replaced)
-  if (ensure_entry_records(c)) return 1;
-  double *d_new = nullptr;
-  HIPCHK(c, hipMalloc(&d_new, sizeof(double) * n3));
-  // (-0.0 passes the test above: stored as +0.0, the vacuum's own column)
-  std::vector<double> clean(cols3, cols3 + n3);
-  for (double &v : clean) v = v + 0.0;
-  HIPCHK(c, hipMemcpyAsync(d_new, clean.data(), sizeof(double) * n3, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (c->src_entry.size() != (size_t)c->nsrc) c->src_entry.assign((size_t)c->nsrc, c2r_ctx::FaceEntry());
-  c2r_ctx::FaceEntry &e = c->src_entry[(size_t)ns - 1];
-  if (e.d_cols) HIPCHK(c, hipFree(e.d_cols));
-  e.face = face;
-  e.rounds = rounds;
-  e.d_cols = d_new;
-  return 0;
+  c2r_ctx::FaceEntry fresh;
+  fresh.face = fresh.faces[axis] = face;
+  fresh.rounds = rounds;
+  fresh.off[axis] = 0;
+  std::vector<double> packed(cols3, cols3 + n3);
+  return keep_source_entry(c, ns, fresh, packed);
 }
 extern "C" int c2r_set_source_face_entry(c2r_ctx *c, int ns, int face, const double *cols3, int rounds) {
   if (int e_ = set_source_face_entry_one(c, ns, face, cols3, rounds)) return e_;
@@ -163,6 +173,87 @@ extern "C" int c2r_set_mesh_origin(c2r_ctx *c, const int origin[3]) {
 extern "C" int c2r_get_mesh_origin(c2r_ctx *c, int origin[3]) {
   if (!c || !origin) return 1;
   for (int d = 0; d < 3; d++) origin[d] = c->origin[d];
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------------
+// halo: entry columns through up to three faces, with the edge lines and the corner where their ghost layers meet
+static int set_source_halo_one(c2r_ctx *c, int ns, const c2r_source_halo *halo) {
+  if (!c) return 1;
+  if (ns < 1 || ns > c->nsrc) return fail(c, "c2r_set_source_halo: source %d not in [1,%d]", ns, c->nsrc);
+  if (c->pass_open)
+    return fail(c, "c2r_set_source_halo: source %d: a pass opened by c2r_pass_sources_begin is still open (close it with c2r_pass_sources_end first)", ns);
+  if (!halo) return clear_source_entry(c, ns);
+  const int mesh[3] = {c->g.n1, c->g.n2, c->g.n3};
+  const int *p = &c->srcpos[3 * (size_t)(ns - 1)];
+  c2r_ctx::FaceEntry fresh;
+  int nout = 0;
+  for (int d = 2; d >= 0; d--) {
+    if (p[d] >= 1 && p[d] <= mesh[d]) continue;
+    fresh.faces[d] = 2 * d + (p[d] > mesh[d] ? 1 : 0);
+    fresh.face = fresh.faces[d]; // (the lowest, in the end)
+    nout++;
+  }
+  if (nout == 0)
+    return fail(c, "c2r_set_source_halo: source %d at (%d,%d,%d) stands inside the mesh (a halo belongs to a source beyond one, two or three faces)",
+                ns, p[0], p[1], p[2]);
+  if (halo->rounds < 1) return fail(c, "c2r_set_source_halo: source %d: rounds = %d, expected at least 1", ns, halo->rounds);
+  fresh.rounds = halo->rounds;
+  // a whole halo and nothing else: array a of c2ray_halo.hpp, what it is called, whether the source needs it, its doubles per species
+  const double *given[HALO_ARRAYS];
+  char name[HALO_ARRAYS][16];
+  size_t per[HALO_ARRAYS], total = 0;
+  for (int d = 0; d < 3; d++) {
+    const int a = (d + 1) % 3, b = (d + 2) % 3;
+    given[d] = halo->face[d];
+    given[3 + d] = halo->edge[d];
+    snprintf(name[d], sizeof name[d], "face[%d]", d);
+    snprintf(name[3 + d], sizeof name[3 + d], "edge[%d]", d);
+    per[d] = handover_face_cells(c, d);
+    per[3 + d] = (size_t)mesh[d];
+    const bool need_face = fresh.faces[d] >= 0, need_edge = fresh.faces[a] >= 0 && fresh.faces[b] >= 0;
+    if (need_face != (given[d] != nullptr))
+      return fail(c, need_face ? "c2r_set_source_halo: source %d at (%d,%d,%d) stands outside the mesh along axis %d: %s is missing"
+                               : "c2r_set_source_halo: source %d at (%d,%d,%d) stands inside the mesh along axis %d: %s is superfluous",
+                  ns, p[0], p[1], p[2], d, name[d]);
+    if (need_edge != (given[3 + d] != nullptr))
+      return fail(c, need_edge ? "c2r_set_source_halo: source %d at (%d,%d,%d) stands outside the mesh along both axes other than %d: %s is missing"
+                               : "c2r_set_source_halo: source %d at (%d,%d,%d) does not stand outside the mesh along both axes other than %d: %s is superfluous",
+                  ns, p[0], p[1], p[2], d, name[3 + d]);
+  }
+  given[6] = halo->corner;
+  snprintf(name[6], sizeof name[6], "corner");
+  per[6] = 1;
+  if ((nout == 3) != (given[6] != nullptr))
+    return fail(c, nout == 3 ? "c2r_set_source_halo: source %d at (%d,%d,%d) stands outside the mesh along all three axes: the corner is missing"
+                             : "c2r_set_source_halo: source %d at (%d,%d,%d) does not stand outside the mesh along all three axes: the corner is superfluous",
+                ns, p[0], p[1], p[2]);
+  for (int a = 0; a < HALO_ARRAYS; a++) {
+    if (!given[a]) continue;
+    for (size_t i = 0; i < 3 * per[a]; i++)
+      if (!(given[a][i] >= 0.0) || !std::isfinite(given[a][i]))
+        return fail(c, "c2r_set_source_halo: source %d: %s: entry %zu of species %d is %g (a column is finite and not negative)", ns, name[a],
+                    i % per[a], (int)(i / per[a]), given[a][i]);
+    fresh.off[a] = total;
+    total += 3 * per[a];
+  }
+  std::vector<double> packed;
+  packed.reserve(total);
+  for (int a = 0; a < HALO_ARRAYS; a++)
+    if (given[a]) packed.insert(packed.end(), given[a], given[a] + 3 * per[a]);
+  return keep_source_entry(c, ns, fresh, packed);
+}
+extern "C" int c2r_set_source_halo(c2r_ctx *c, int ns, const c2r_source_halo *halo) {
+  if (int e_ = set_source_halo_one(c, ns, halo)) return e_;
+  return for_replicas(c, [&](c2r_ctx *r) { return set_source_halo_one(r, ns, halo); });
+}
+extern "C" int c2r_get_source_halo(c2r_ctx *c, int ns, int faces[3], int *rounds) {
+  if (!c) return 1;
+  if (ns < 1 || ns > c->nsrc) return fail(c, "c2r_get_source_halo: source %d not in [1,%d]", ns, c->nsrc);
+  const bool set = !c->src_entry.empty() && c->src_entry[(size_t)ns - 1].face >= 0;
+  if (faces)
+    for (int d = 0; d < 3; d++) faces[d] = set ? c->src_entry[(size_t)ns - 1].faces[d] : -1;
+  if (rounds) *rounds = set ? c->src_entry[(size_t)ns - 1].rounds : 0;
   return 0;
 }
 

@@ -8,7 +8,9 @@
 //                                  (c2r_set_sources_external): cells of its box beyond the mesh are vacuum;
 //                                  k_sweep_shell_entry, k_sweep_shell_fast_entry for a batch with a source that has entry
 //                                  columns (c2r_set_source_face_entry): the ghost layer of its face holds the strip of the
-//                                  mesh upstream; k_source_face_exit gathers the exit strips (c2ray_handover.inc)
+//                                  mesh upstream; k_sweep_shell_halo, k_sweep_shell_fast_halo for a batch with a source whose
+//                                  halo has several faces (c2r_set_source_halo): ghost layers, edge lines and the corner
+//                                  (c2ray_halo.hpp); k_source_face_exit gathers the exit strips (c2ray_handover.inc)
 //   rates          k_rates         all cells x all sources of the batch, no dependencies:
 //                                  photoion_rates + accumulation into the rate grids in source order
 //                                  (evolve0D, second half)
@@ -56,6 +58,7 @@
 #include "c2ray_pcurve.hpp"
 #include "c2ray_pside.hpp"
 #include "c2ray_shell.hpp"
+#include "c2ray_halo.hpp"
 
 using namespace c2r;
 
@@ -106,6 +109,10 @@ struct SrcEntry {
   int on;             // 0: the source has no entry; else 1 + face, face = 2 * axis + high
   const double *cols; // its strip: 3 F doubles, species slowest, the face cells with the lower of the two other axes fastest
   int origin[3];      // c2r_set_mesh_origin: the deep mesh's index of this mesh's cell (1,1,1), minus 1, per axis
+  // Read by the halo kernels only (c2r_set_source_halo; k_sweep_shell_halo, k_sweep_shell_fast_halo), filled for every source with
+  // an entry -- one face is the halo of one face:
+  int ghost[3];                     // per axis the 0-based ghost index (-1 or mesh), HALO_INSIDE where the source stands inside
+  const double *part[HALO_ARRAYS];  // the face strips by axis, the edge lines by axis (3 + axis), the corner; null: none
 };
 // The source's position as cinterp sees it: cinterp forms its crossing points from absolute coordinates, so a part of a deep mesh
 // reproduces the deep mesh's bits only with the deep mesh's coordinates -- the source's own, moved by the mesh's origin
@@ -131,6 +138,21 @@ __device__ __forceinline__ void entry_columns(const SrcEntry &E, const Grid &g, 
   c_HI = E.cols[f];
   c_HeI = E.cols[F + f];
   c_HeII = E.cols[2 * F + f];
+}
+// The same for a source with a halo (c2r_set_source_halo): the cell's class, array and entry from halo_classify
+// (c2ray_halo.hpp), the array's address by selects on the record's seven pointers (uniform per source), three loads for a
+// ghost cell and none for a vacuum cell.
+__device__ __forceinline__ void halo_columns(const SrcEntry &E, const Grid &g, int i, int j, int k, double &c_HI, double &c_HeI,
+                                             double &c_HeII) {
+  int array;
+  size_t f, F;
+  if (!halo_classify(i, j, k, g.n1, g.n2, g.n3, E.ghost[0], E.ghost[1], E.ghost[2], array, f, F)) return;
+  const double *face = array == 0 ? E.part[0] : (array == 1 ? E.part[1] : E.part[2]);
+  const double *edge = array == 3 ? E.part[3] : (array == 4 ? E.part[4] : E.part[5]);
+  const double *cols = array < 3 ? face : (array < 6 ? edge : E.part[6]);
+  c_HI = cols[f];
+  c_HeI = cols[F + f];
+  c_HeII = cols[2 * F + f];
 }
 // Is the cell at offset (di, dj, dk) lit by source S?  Uniform branch on S.cut (a scalar register: the record is read through
 // the scalar cache), so a source with neither beam nor horizon costs a wave one scalar compare; the loss and per-cell kernels
@@ -569,9 +591,12 @@ __device__ __forceinline__ void sweep_cell_state(const SweepArgs &A, int i, int 
 // ENTRY (EXT kernels of a batch with a source that has entry columns, c2r_set_source_face_entry; E: its record): a vacuum cell
 // in the ghost layer of the entry's face stores the strip's columns as N_out instead of N_in (entry_columns) -- the one
 // change to the vacuum rule; every other vacuum cell stays vacuum, and nobody downstream of the ghost layer reads one.
-template <bool OPEN, bool EXT = false, bool ENTRY = false>
+// HALO (ENTRY kernels of a batch with a source whose halo has several faces, c2r_set_source_halo): the ghost cells are those of
+// halo_columns -- the ghost layers of up to three faces, the edge lines and the corner cell where they meet.
+template <bool OPEN, bool EXT = false, bool ENTRY = false, bool HALO = false>
 __device__ __forceinline__ void sweep_cell(const SweepArgs &A, const SrcDev &S, int shell, int t, const SrcEntry *E = nullptr) {
   static_assert(EXT || !ENTRY, "entry columns belong to a source outside the mesh");
+  static_assert(ENTRY || !HALO, "a halo is a kind of entry");
   static_assert(OPEN || !EXT, "a source outside the mesh needs an open axis");
   const Grid &g = A.g;
   const StepScalars &sc = A.sc;
@@ -638,7 +663,10 @@ __device__ __forceinline__ void sweep_cell(const SweepArgs &A, const SrcDev &S, 
   double cout_HeI = cin_HeI + u_HeI * path * abu_he;
   double cout_HeII = cin_HeII + u_HeII * path * abu_he;
   if constexpr (ENTRY) {
-    if (E->on && !in_mesh) entry_columns(*E, g, i, j, k, cout_HI, cout_HeI, cout_HeII);
+    if (E->on && !in_mesh) {
+      if constexpr (HALO) halo_columns(*E, g, i, j, k, cout_HI, cout_HeI, cout_HeII);
+      else entry_columns(*E, g, i, j, k, cout_HI, cout_HeI, cout_HeII);
+    }
   }
   store_columns(cs, p, cz, cin_HI, cin_HeI, cin_HeII, cout_HI, cout_HeI, cout_HeII);
 }
@@ -651,9 +679,10 @@ __device__ __forceinline__ void sweep_cell(const SweepArgs &A, const SrcDev &S, 
 // the columns of sweep_cell (tests/test_gpu_parity.py::test_fast_sweep_equals_the_general_sweep runs that one for every
 // shell, C2R_SWEEP_GENERIC=1, in a process of its own and compares the columns).
 // EXT, ENTRY: as in sweep_cell.
-template <bool OPEN, bool EXT = false, bool ENTRY = false>
+template <bool OPEN, bool EXT = false, bool ENTRY = false, bool HALO = false>
 __device__ __forceinline__ void sweep_cell_fast(const SweepArgs &A, const SrcDev &S, const ShellGeom &G, int t, const SrcEntry *E = nullptr) {
   static_assert(EXT || !ENTRY, "entry columns belong to a source outside the mesh");
+  static_assert(ENTRY || !HALO, "a halo is a kind of entry");
   static_assert(OPEN || !EXT, "a source outside the mesh needs an open axis");
   const Grid &g = A.g;
   const StepScalars &sc = A.sc;
@@ -698,7 +727,10 @@ __device__ __forceinline__ void sweep_cell_fast(const SweepArgs &A, const SrcDev
   double cout_HeI = cin_HeI + u_HeI * path * abu_he;
   double cout_HeII = cin_HeII + u_HeII * path * abu_he;
   if constexpr (ENTRY) {
-    if (E->on && !in_mesh) entry_columns(*E, g, i, j, k, cout_HI, cout_HeI, cout_HeII);
+    if (E->on && !in_mesh) {
+      if constexpr (HALO) halo_columns(*E, g, i, j, k, cout_HI, cout_HeI, cout_HeII);
+      else entry_columns(*E, g, i, j, k, cout_HI, cout_HeI, cout_HeII);
+    }
   }
   store_columns(cs, p, cz, cin_HI, cin_HeI, cin_HeII, cout_HI, cout_HeI, cout_HeII);
 }
@@ -793,6 +825,26 @@ k_sweep_shell_fast_entry(SweepArgs A, const SrcDev *__restrict__ src, const int 
   const SrcDev &S = src[b];
   const int t = sweep_block_cell_open(sweep_shell_cells<true>(S, G.s));
   if (t >= 0) sweep_cell_fast<true, true, true>(A, S, G, t, ent + b);
+}
+
+// ... and of a batch that holds a source whose halo has several faces (c2r_set_source_halo): the two above with sweep_cell's HALO.
+// Twins, not a wider entry_columns: the entry kernels keep their registers and their occupancy, and a batch whose entries all
+// have one face launches them as before.
+__global__ void __launch_bounds__(BLOCK, C2R_SWEEP_WAVES)
+k_sweep_shell_halo(SweepArgs A, const SrcDev *__restrict__ src, const int *__restrict__ active, int shell, const SrcEntry *__restrict__ ent) {
+  const int b = active[blockIdx.y];
+  const SrcDev &S = src[b];
+  const int t = sweep_block_cell_open(sweep_shell_cells<true>(S, shell));
+  if (t >= 0) sweep_cell<true, true, true, true>(A, S, shell, t, ent + b);
+}
+
+__global__ void __launch_bounds__(BLOCK, C2R_SWEEP_WAVES)
+k_sweep_shell_fast_halo(SweepArgs A, const SrcDev *__restrict__ src, const int *__restrict__ active, ShellGeom G,
+                        const SrcEntry *__restrict__ ent) {
+  const int b = active[blockIdx.y];
+  const SrcDev &S = src[b];
+  const int t = sweep_block_cell_open(sweep_shell_cells<true>(S, G.s));
+  if (t >= 0) sweep_cell_fast<true, true, true, true>(A, S, G, t, ent + b);
 }
 
 // Exit strips (c2r_select_source_face_exit): N_out of the cells in the layer of `face` from the shell-ordered blocks of the
@@ -1818,9 +1870,16 @@ struct c2r_ctx {
   // Point-source hand-over between stacked meshes (c2ray_handover.inc).
   // c2r_set_source_face_entry: per source (empty: no source has one) the face its entry columns come through (-1: none), the
   // rounds it is traced for and its strip on the device; the records of a batch in flight, per scratch set.
+  // c2r_set_source_halo: the same record for up to three faces -- `face` is then the lowest of them, faces[d] the face of axis d
+  // (-1: the source stands inside along d), and d_cols one allocation that holds the strips, the edge lines and the corner,
+  // array a (c2ray_halo.hpp) at off[a] (HALO_ABSENT: none).  An entry of one face is the halo of one face.
+  static constexpr size_t HALO_ABSENT = ~(size_t)0;
   struct FaceEntry {
     int face = -1, rounds = 0;
     double *d_cols = nullptr;
+    int faces[3] = {-1, -1, -1};
+    size_t off[HALO_ARRAYS] = {HALO_ABSENT, HALO_ABSENT, HALO_ABSENT, HALO_ABSENT, HALO_ABSENT, HALO_ABSENT, HALO_ABSENT};
+    bool several() const { return (faces[0] >= 0) + (faces[1] >= 0) + (faces[2] >= 0) > 1; }
   };
   std::vector<FaceEntry> src_entry;
   // c2r_set_mesh_origin: where this mesh lies in the deep mesh it is a part of (0: it is the deep mesh, or begins at its cell 1)
@@ -3623,6 +3682,8 @@ struct Batch {
   bool entry = false;               // some source of the batch has entry columns (c2r_set_source_face_entry), or the mesh has an
                                     // origin (c2r_set_mesh_origin): the shells are
                                     // k_sweep_shell(_fast)_entry's, the kept losses k_loss_entry's; d_ent[set] holds the records
+  bool halo = false;                // some source of the batch has a halo of several faces (c2r_set_source_halo): entry is set
+                                    // too, and the shells are k_sweep_shell(_fast)_halo's
   std::vector<int> rim_ns;          // horizon loss: the sources (1-based) whose sums queue_horizon_rim has queued, in row order
 };
 
@@ -3750,6 +3811,7 @@ static int place_batch(const PassCtx &P, const std::vector<int> &mine, Batch &B)
   B.curved = false;
   B.external = false;
   B.entry = false;
+  B.halo = false;
   for (bool released = false;;) {
     c->seg_cur[set] = 0;
     c->seg_used[set] = 0;
@@ -3820,8 +3882,14 @@ static int place_batch(const PassCtx &P, const std::vector<int> &mine, Batch &B)
     const bool placed_in_deep = c->origin[0] != 0 || c->origin[1] != 0 || c->origin[2] != 0;
     if (placed_in_deep || !c->src_entry.empty()) { // (either exists: the pinned records do too)
       const c2r_ctx::FaceEntry e = c->src_entry.empty() ? c2r_ctx::FaceEntry() : c->src_entry[(size_t)r.ns - 1];
-      c->h_ent[set][b] = SrcEntry{e.face >= 0 ? 1 + e.face : 0, e.d_cols, {c->origin[0], c->origin[1], c->origin[2]}};
+      SrcEntry &E = c->h_ent[set][b];
+      E = SrcEntry{e.face >= 0 ? 1 + e.face : 0, e.d_cols, {c->origin[0], c->origin[1], c->origin[2]}, {HALO_INSIDE, HALO_INSIDE, HALO_INSIDE}, {}};
+      const int mesh[3] = {c->g.n1, c->g.n2, c->g.n3};
+      for (int d = 0; d < 3; d++)
+        if (e.faces[d] >= 0) E.ghost[d] = halo_ghost_index(p[d], mesh[d]);
+      for (int a = 0; a < HALO_ARRAYS; a++) E.part[a] = e.off[a] == c2r_ctx::HALO_ABSENT ? nullptr : e.d_cols + e.off[a];
       r.entry_rounds = e.face >= 0 ? e.rounds : 0;
+      B.halo = B.halo || e.several();
       // (a mesh with an origin: every batch through the kernels that move cinterp's coordinates, entry or not)
       B.entry = B.entry || e.face >= 0 || placed_in_deep;
     }
@@ -3968,6 +4036,9 @@ static int launch_shells(PassCtx &P, Batch &B, const Box &box, int s_lo, int s_h
     if (fast && c->periodic)
       hipLaunchKernelGGL(k_sweep_shell_fast<false>, dim3(nlaunch, nact), dim3(BLOCK), 0, c->stream, SA, c->d_src[B.set],
                          c->d_list[B.set] + act_off, c->shell_geom[(size_t)s]);
+    else if (fast && B.halo) // (a source with a halo of several faces in the batch: the entry kernels' twins that know edges and corners)
+      hipLaunchKernelGGL(k_sweep_shell_fast_halo, dim3(nlaunch, nact), dim3(BLOCK), 0, c->stream, SA, c->d_src[B.set],
+                         c->d_list[B.set] + act_off, c->shell_geom[(size_t)s], c->d_ent[B.set]);
     else if (fast && B.entry) // (a source with entry columns in the batch: the kernels that know vacuum cells and the ghost layer)
       hipLaunchKernelGGL(k_sweep_shell_fast_entry, dim3(nlaunch, nact), dim3(BLOCK), 0, c->stream, SA, c->d_src[B.set],
                          c->d_list[B.set] + act_off, c->shell_geom[(size_t)s], c->d_ent[B.set]);
@@ -3979,6 +4050,9 @@ static int launch_shells(PassCtx &P, Batch &B, const Box &box, int s_lo, int s_h
                          c->d_list[B.set] + act_off, c->shell_geom[(size_t)s]);
     else if (c->periodic)
       hipLaunchKernelGGL(k_sweep_shell<false>, dim3(nlaunch, nact), dim3(BLOCK), 0, c->stream, SA, c->d_src[B.set], c->d_list[B.set] + act_off, s);
+    else if (B.halo)
+      hipLaunchKernelGGL(k_sweep_shell_halo, dim3(nlaunch, nact), dim3(BLOCK), 0, c->stream, SA, c->d_src[B.set], c->d_list[B.set] + act_off, s,
+                         c->d_ent[B.set]);
     else if (B.entry)
       hipLaunchKernelGGL(k_sweep_shell_entry, dim3(nlaunch, nact), dim3(BLOCK), 0, c->stream, SA, c->d_src[B.set], c->d_list[B.set] + act_off, s,
                          c->d_ent[B.set]);

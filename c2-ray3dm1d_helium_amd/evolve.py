@@ -432,6 +432,45 @@ class HipEngine:
         self._chk(self.lib.c2r_get_source_face_entry(self.h, int(ns), C.byref(face), C.byref(rounds)))
         return face.value, rounds.value
 
+    def set_source_halo(self, ns, faces=None, edges=None, corner=None, rounds=0):
+        """c2r_set_source_halo: the entry of source ns (1-based) where it stands beyond one, two or three faces.  faces: {face:
+        strip} with face = 2 * axis + high and the strip as for set_source_face_entry; edges: {axis: line} with the line along
+        that axis as (3, mesh[axis]), species slowest; corner: 3 values; the source is traced for exactly `rounds` rounds.
+        faces=None clears the halo (or the entry).  handover.edge_of_strip / corner_of_strip cut the lines and the corner out of
+        a neighbour's exit strip.  set_sources clears every halo."""
+        if faces is None:
+            self._chk(self.lib.c2r_set_source_halo(self.h, int(ns), None))
+            return
+        rec, keep = _lib.SourceHalo(), []
+        rec.rounds = int(rounds)
+
+        def pointer(values, count, what):
+            a = _f64(values).reshape(-1)
+            if a.size != 3 * count:
+                raise ValueError(f"set_source_halo: {what}: {a.size} values, expected 3 x {count}")
+            keep.append(a)
+            return _dp(a)
+
+        for face, strip in dict(faces).items():
+            cells = self._source_face_cells(face)
+            if rec.face[int(face) >> 1]:
+                raise ValueError(f"set_source_halo: two faces of axis {int(face) >> 1}")
+            rec.face[int(face) >> 1] = pointer(strip, cells, f"face {face}")
+        for axis, line in dict(edges or {}).items():
+            if not 0 <= int(axis) <= 2:
+                raise C2RayHipError(f"axis {axis} not in 0..2")
+            rec.edge[int(axis)] = pointer(line, self.mesh[int(axis)], f"edge {axis}")
+        if corner is not None:
+            rec.corner = pointer(corner, 1, "corner")
+        self._chk(self.lib.c2r_set_source_halo(self.h, int(ns), C.byref(rec)))
+
+    def source_halo(self, ns):
+        """c2r_get_source_halo: (faces, rounds) of source ns -- the face numbers its halo has strips for, ascending; () and 0
+        while none is set."""
+        faces, rounds = (C.c_int * 3)(), C.c_int(0)
+        self._chk(self.lib.c2r_get_source_halo(self.h, int(ns), faces, C.byref(rounds)))
+        return tuple(int(f) for f in faces if f >= 0), rounds.value
+
     def set_source_beams(self, beams=None):
         """c2r_set_source_beams: one beam per point source, in source order -- None (no beam), a dict or a tuple
         (kind, axis, cos_half) with kind 0 / "none", 1 / "cone" or 2 / "bicone", axis three numbers (any length), cos_half the

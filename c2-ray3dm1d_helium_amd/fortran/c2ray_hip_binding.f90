@@ -238,6 +238,22 @@ module c2ray_hip
        integer(c_int), intent(out) :: face, rounds
      end function c2r_get_source_face_entry
 
+     !> the halo of source ns, which stands beyond one, two or three faces: c_loc of a c2r_source_halo, or c_null_ptr
+     !> to clear it
+     integer(c_int) function c2r_set_source_halo(ctx, ns, halo) bind(C, name="c2r_set_source_halo")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: ctx, halo
+       integer(c_int), value :: ns
+     end function c2r_set_source_halo
+
+     !> faces(d) = 2 (d - 1) + high, or -1 where source ns has no strip along axis d
+     integer(c_int) function c2r_get_source_halo(ctx, ns, faces, rounds) bind(C, name="c2r_get_source_halo")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: ctx
+       integer(c_int), value :: ns
+       integer(c_int), intent(out) :: faces(3), rounds
+     end function c2r_get_source_halo
+
      !> this mesh's index + origin = the deep mesh's index, per axis: cinterp then forms its crossing points from
      !> the deep mesh's coordinates (non-zero along open axes only)
      integer(c_int) function c2r_set_mesh_origin(ctx, origin) bind(C, name="c2r_set_mesh_origin")

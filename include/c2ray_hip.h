@@ -159,7 +159,7 @@ int c2r_set_sources_external(c2r_ctx *ctx, int nsrc, const int *srcpos, const do
  * is open; a multi-device context answers from the device that swept ns.
  *
  * ENTRY.  c2r_set_source_face_entry gives source ns, which must stand outside the mesh beyond `face` along that axis only
- * (its other two coordinates inside the mesh; a neighbour across an edge or a corner is refused), the strip cols3 of the mesh
+ * (its other two coordinates inside the mesh; a neighbour across an edge or a corner is refused by this call: HALO below), the strip cols3 of the mesh
  * upstream and the rounds that mesh traced; cols3 = NULL clears the entry.
  *   Ghost layer: the vacuum rule of c2r_set_sources_external changes in one place for this source -- a cell of its box in the
  * ghost layer of `face` stores N_out = cols3[species][face cell] instead of N_in.  Every other vacuum cell stays vacuum
@@ -197,11 +197,51 @@ int c2r_set_sources_external(c2r_ctx *ctx, int nsrc, const int *srcpos, const do
  * entries; c2r_set_boundaries*, beams, horizons and curves keep them.  The call acts on every device of a multi-device
  * context.  c2r_get_source_face_entry returns face = -1 (and rounds = 0) while none is set.  c2r_get_source_trace keeps
  * counting the vacuum.  Still refused for a source outside the mesh: the escape maps, the horizon loss, c2r_do_source and
- * c2r_evolve0d. */
+ * c2r_evolve0d.
+ *
+ * HALO.  c2r_set_source_halo is the entry of a source that stands beyond two or three faces: the neighbour across an edge or a
+ * corner of a mesh tiled in 2-D or 3-D.  The source ns stands outside the mesh along the axis set B, 1 <= |B| <= 3; for d in B
+ * the side is h_d = 1 if srcpos_d > mesh_d, 0 if srcpos_d < 1, and the ghost index g_d = mesh_d + 1 for h_d = 1, 0 for h_d = 0
+ * (1-based).  Take a cell of the source's box outside the mesh, at mesh index m, and let O be the axes along which m lies
+ * outside 1..mesh.  The cell is a GHOST CELL iff O is a subset of B and m_d = g_d for every d in O; it stores N_out from the halo
+ * instead of its N_in:
+ *   |O| = 1, O = {d}: face[d], the strip of face 2d + h_d, at the cell's face cell -- the ghost layer and the layout of ENTRY;
+ *   |O| = 2:          edge[e], the EDGE LINE along the remaining axis e, 3 mesh[e] doubles, species slowest, at entry m_e - 1;
+ *   |O| = 3:          the CORNER, 3 doubles.
+ * Every other vacuum cell stays vacuum, no LLS fog is added in a ghost cell, mesh cells get the arithmetic they always got.
+ * The rule is complete: every upstream corner of a mesh cell lies at most one step outside the mesh per axis, and only along
+ * axes of B (the upstream cells lie towards the source), so it lies in the mesh or is a ghost cell -- nobody downstream of a
+ * ghost cell reads any other vacuum cell.  Rounds and kept loss are ENTRY's: exactly `rounds` rounds, no deciding loss, no
+ * probe; photon_loss(1) receives only the terms of the surface cells of the final box that are mesh cells.
+ *   A halo is whole: a strip for every d in B, an edge line along e for every e whose two other axes both lie in B, the corner
+ * iff |B| = 3, and nothing else.  An edge line or the corner of a part of W is a cell of the diagonal neighbour's layer and is
+ * read out of that neighbour's exit strip (either of the two strips that hold it); the exit side is unchanged.
+ *   A halo of one face IS the entry of that face: the same bits, the same kernels, and c2r_get_source_face_entry reports it.
+ * c2r_set_source_face_entry replaces a halo, and its cols3 = NULL clears either kind, as halo = NULL does here;
+ * c2r_get_source_face_entry returns, for a halo of several faces, the lowest face number and the rounds.  c2r_get_source_halo
+ * returns faces[d] = 2d + h_d, or -1 where the source has no strip along d; all -1 and rounds = 0 while none is set.
+ *   Kernels: a batch that holds a source whose halo has several faces runs k_sweep_shell_halo and k_sweep_shell_fast_halo
+ * (the entry kernels' twins with the ghost rule above) and k_loss_entry; every other batch launches what it always launched,
+ * with the same bits.  ZERO STRIP holds for a halo whose arrays are all zero; HAND-OVER holds for a W tiled along two or
+ * three axes, each part placed with c2r_set_mesh_origin: every part has W's bits on its cells.
+ *   Everything is checked before anything is kept; refused, with a message that names the source and leaving everything
+ * unchanged: a bad ns, an open slab-wise pass, rounds < 1, a source inside the mesh, a strip, line or corner that is missing,
+ * one that is superfluous (given for an axis the source stands inside along, or for an edge whose two other axes are not both
+ * in B), a negative or non-finite column (the message names the array and the entry).  -0.0 is stored as +0.0.  Lifetime as
+ * for entries: c2r_set_sources* clears halos; boundaries, beams, horizons and curves keep them; the call acts on every device
+ * of a multi-device context. */
+typedef struct {
+  int rounds;               /* >= 1, as for c2r_set_source_face_entry */
+  const double *face[3];    /* face[d]: the strip of face 2d + h_d, or NULL where the source stands inside along d */
+  const double *edge[3];    /* edge[e]: the line along axis e (3 * mesh[e]), needed iff the source stands outside along both other axes */
+  const double *corner;     /* 3 doubles, needed iff the source stands outside along all three */
+} c2r_source_halo;
 int c2r_select_source_face_exit(c2r_ctx *ctx, int face, int nsel, const int *sources);
 int c2r_download_source_face_exit(c2r_ctx *ctx, int face, int ns, double *cols3, int *rounds, int *reached);
 int c2r_set_source_face_entry(c2r_ctx *ctx, int ns, int face, const double *cols3, int rounds);
 int c2r_get_source_face_entry(c2r_ctx *ctx, int ns, int *face, int *rounds);
+int c2r_set_source_halo(c2r_ctx *ctx, int ns, const c2r_source_halo *halo);   /* halo == NULL clears */
+int c2r_get_source_halo(c2r_ctx *ctx, int ns, int faces[3], int *rounds);     /* faces[d] = 2d + h_d, or -1; all -1 and rounds 0 while none */
 int c2r_set_mesh_origin(c2r_ctx *ctx, const int origin[3]);
 int c2r_get_mesh_origin(c2r_ctx *ctx, int origin[3]);
 
